@@ -2,6 +2,13 @@
 """Benchmark of the convexify() hot path on MI355X.
 
     python bench.py --gpus N --steps K --warmup W          (N=1 directly; N>1 under torch.distributed.run)
+    python bench.py ... --dump-outputs DIR                 (also write the last timed step's outputs as DIR/<name>.npy)
+    python bench.py ... --full                             (also the side legs and the CPU baseline: several minutes more)
+
+A plain run sets up, warms up, times the K steps and prints the line (headline, roofline from the profile of the timed
+steps).  --full adds, N=1 only, the side legs after the timed region (unprofiled, host-buffer and fast-exit steps, small
+and large-block configurations, tight mode) and the CPU baseline (oracle/cpu_ipm); --no-extra / --no-small / --no-tight /
+--no-cpu-baseline drop parts of them.
 
 A "step" is one complete batched convexify (pre-check, scaling, SDP Step 1 to tolerance, reconstruction,
 status check) over one synthetic batch of `--batch` tuning problems per GPU, inputs resident in HBM.
@@ -281,6 +288,33 @@ def large_block_configs(HipConvexifier, synthetic):
     return out
 
 
+DUMP_BYTES_MAX = 64 * 2 ** 20      # --dump-outputs: at most 64 MB in all
+DUMP_SAMPLE = 32                    # problems in the sample of the per-stage matrices (Hc, dHc, P: ~1.3 MB per problem at the bench shape)
+
+
+def dump_outputs(res, path):
+    """--dump-outputs: the arrays the timed path handed its caller in its last step (the dict of convexify_batch_device; with N > 1 ranks the
+    gathered Hc / kappa / status) as path/<name>.npy, float64.  Per-problem scalars and info rows are written whole; arrays with per-stage
+    matrices only for a fixed, seeded sample of the problems (the same members for the same --batch), whose indices go to sample_index.npy."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    nb = int(res['status'].shape[0])
+    whole = {k: v for k, v in res.items() if v.dim() <= 2}
+    staged = {k: v for k, v in res.items() if v.dim() > 2}
+    left = DUMP_BYTES_MAX - 8 * (sum(v.numel() for v in whole.values()) + DUMP_SAMPLE)
+    per_problem = 8 * sum(v[0].numel() for v in staged.values())
+    ns = min(nb, DUMP_SAMPLE, left // max(per_problem, 1))
+    if ns < 1:
+        raise SystemExit(f'--dump-outputs: one problem of the per-stage outputs ({per_problem} bytes) exceeds the {DUMP_BYTES_MAX} bytes of the dump')
+    rows = np.sort(np.random.default_rng(20261016).choice(nb, size=ns, replace=False))
+    np.save(os.path.join(path, 'sample_index.npy'), rows.astype(np.float64))
+    for k, v in whole.items():
+        np.save(os.path.join(path, f'{k}.npy'), v.cpu().numpy().astype(np.float64))
+    for k, v in staged.items():
+        idx = torch.as_tensor(rows, device=v.device)
+        np.save(os.path.join(path, f'{k}.npy'), v.index_select(0, idx).cpu().numpy().astype(np.float64))
+
+
 # Everything that libraries print on stdout while the bench runs (RCCL prints its version banner there at communicator creation) goes
 # to stderr: stdout carries exactly one line, the JSON record.
 REAL_STDOUT = os.dup(1)
@@ -297,6 +331,10 @@ def main():
     ap.add_argument('--nx', type=int, default=24)
     ap.add_argument('--mb', type=int, default=8)
     ap.add_argument('--tol', type=float, default=0.0, help='0 = library default')
+    ap.add_argument('--full', action='store_true', help='N = 1: after the timed steps also run the side legs (--no-extra / --no-small / --no-tight) and the CPU baseline '
+                    '(--no-cpu-baseline); without it the line carries the headline and the profile of the timed steps only')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write the outputs of the last timed step as DIR/<name>.npy (float64; the per-stage matrices '
+                    'for a fixed, seeded sample of the problems: dump_outputs)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--lowp-switch', type=float, default=-1.0, help='TMPC_TUNE_LOWP_SWITCH of the handle (single-precision Schur-complement updates while mu / kappa > value; 0: off); < 0: library default')
     ap.add_argument('--backend', default='nccl', choices=['nccl', 'gloo'], help="collective backend; 'gloo' (results staged through the host) lets the multi-rank branch run where RCCL cannot")
@@ -417,10 +455,12 @@ def main():
         it_all = [t.cpu().tolist() for t in it_all]
     else:
         it_all = [it_rank.cpu().tolist()]
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(res, args.dump_outputs)          # before the side legs of --full: they solve into the same output buffers again
 
-    # the same solve WITHOUT the profiling events (the product default), and through the host-buffer entry (H2D + D2H inside), N = 1 only
+    # --full: the same solve WITHOUT the profiling events (the product default), and through the host-buffer entry (H2D + D2H inside), N = 1 only
     extra_rates = {}
-    if world == 1 and not args.no_extra:
+    if args.full and world == 1 and not args.no_extra:
         ne = max(1, min(args.steps, 3))
         h.set_options(tol=args.tol if args.tol > 0 else None, flags=0)
         step(); torch.cuda.synchronize()
@@ -655,7 +695,7 @@ def main():
                 hsh.update(np.ascontiguousarray(res[k].cpu().numpy()).tobytes())
             line["gathered_digest"] = hsh.hexdigest()
             line["gathered_problems"] = int(res['Hc'].shape[0])
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             try:                                                        # the checker's build or run must never cost the GPU measurement its line
                 line["cpu_baseline"] = cpu_baseline(p, nx, mb, args.tol if args.tol > 0 else 2.0 ** -25)
             except Exception as e:      # noqa: BLE001
