@@ -115,11 +115,16 @@ int tmpc_set_options(tmpc_handle* h, double tol, double center_tol, int max_iter
  *   TMPC_TUNE_FUSE_FWD     1 (default): the forward substitution of the predictor pass rides inside the factorisation; 0: separate sweep
  *   TMPC_TUNE_GRAPH        1 (default): problems whose Schur blocks are a single tile (nx <= 10: launch-bound) replay the launch sequence of an iteration as a
  *                          captured hipGraph (one submission instead of ~35; the handle's own streams only); 0: plain launches
- *   TMPC_TUNE_LOWP_SWITCH  value >= 0 (default TMPC_LOWP_SWITCH_DEFAULT): in the main-phase iterations of a problem with mu > value * max(1, kappa) the Schur-complement updates of
+ *   TMPC_TUNE_LOWP_SWITCH  value >= 0 (default TMPC_LOWP_SWITCH_DEFAULT): in the main-phase iterations of a problem with mu > value * max(1, |tau|) (tau: the
+ *                          current objective estimate, kappa at the end; the value is raised to 16 tol if below it) the Schur-complement updates of
  *                          the block factorisation (k_cr_update_dma, a third of a solve) run on float32 copies of their operands with float32 accumulation (fp32 MFMA:
- *                          twice the fp64 matrix rate); Cholesky, triangular solves, substitutions and every later iteration stay fp64.  Same iteration counts, the
+ *                          twice the fp64 matrix rate); the Cholesky of the diagonal blocks and every later iteration stay fp64 (the triangular solves: TMPC_TUNE_LOWP_TRSM).  Same iteration counts, the
  *                          converged point moves by 1e-11 ... 2e-10 (profiles/r6_fp32_*.txt).  Steps 1 and 2 (not Step 3), stage blocks up to 32 x 32, Schur blocks of 80 ... 320; a pivot that freezes under
  *                          them repeats the iteration in fp64 and turns them off for that problem.  0: never (rounds 1-5, bit for bit)
+ *   TMPC_TUNE_LOWP_TRSM    1 (default): in those same iterations the triangular solves O = E L^-T of the factorisation run in single precision as well
+ *                          (k_cr_trsm_dma_f32: fp64 operands rounded on the fragment read, float32 accumulation, only the float32 copy of O is produced -- the one
+ *                          the updates and substitutions of such an iteration read); the Cholesky of the diagonal blocks stays fp64.  0: fp64 solves in every
+ *                          iteration (round 6, bit for bit)
  *   TMPC_TUNE_PERSISTENT   plain-model problems with single-tile Schur blocks and n = nx + mb <= 8 (the reference's own examples) can run their whole
  *                          interior-point loop as ONE launch, one workgroup per problem (tmpc_persist.h).  1 (default): where that is faster -- period
  *                          p <= 8, or at least 96 problems of the call on the chip at once; 0: never (the launch sequence); 2: whenever the shape allows it
@@ -133,6 +138,7 @@ int tmpc_set_options(tmpc_handle* h, double tol, double center_tol, int max_iter
 #define TMPC_TUNE_PERSISTENT 7
 #define TMPC_TUNE_LOWP_SWITCH 8
 #define TMPC_LOWP_SWITCH_DEFAULT 1e-5
+#define TMPC_TUNE_LOWP_TRSM 9
 int tmpc_set_tuning(tmpc_handle* h, int key, double value);
 /* The general constructor: ng / nc rows of G_k / C_k (0: none), step3 != 0: room for T_k, lanes = concurrent half-waves on their own streams
  * (0: automatic -- two for problems whose blocks are a single 64 x 64 tile and chunk >= 2, one otherwise; at most 4). */

@@ -140,7 +140,7 @@ struct tmpc_handle {
   CrSched sched;                 // elimination order of the block factorisation (tmpc_cr.h)
   int* d_sched;                  // device copy: elimination records | update records | orientation
   int rs, mt;                    // rows per workgroup of k_cr_trsm / output tile edge of k_cr_update (0: chosen per launch)
-  int tune_small, tune_pretest, tune_fuse, tune_graph, tune_persist;     // tmpc_set_tuning
+  int tune_small, tune_pretest, tune_fuse, tune_graph, tune_persist, tune_lowp_trsm;     // tmpc_set_tuning
   void* dd_slab;                 // tight mode (tmpc_set_tight): low words of the double-double planes, allocated on first use
   size_t dd_bytes;
   int tight;                     // 1: the tight phase follows the default solve
@@ -480,6 +480,7 @@ static int set_lds_attrs(int device) {
   HIPCHK(hipFuncSetAttribute((const void*)k_cr_trsm<true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, big));
   HIPCHK(hipFuncSetAttribute((const void*)k_cr_trsm<false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, big));
   HIPCHK(hipFuncSetAttribute((const void*)k_cr_trsm_dma, hipFuncAttributeMaxDynamicSharedMemorySize, big));
+  HIPCHK(hipFuncSetAttribute((const void*)k_cr_trsm_dma_f32, hipFuncAttributeMaxDynamicSharedMemorySize, big));
   HIPCHK(hipFuncSetAttribute((const void*)k_cr_potrf_dma, hipFuncAttributeMaxDynamicSharedMemorySize, big));
   HIPCHK(hipFuncSetAttribute((const void*)k_cr_update<true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, big));
   HIPCHK(hipFuncSetAttribute((const void*)k_cr_update<false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, big));
@@ -522,9 +523,8 @@ static int set_lds_attrs(int device) {
 
 // ---------------------------------------------------------------------------------- block factorisation / solves (tmpc_cr.h)
 static unsigned cr_grid(long items) { return (unsigned)((items + 7) / 8 * 8); }
-// host-side bits of Dims::flags (bit 0 = TMPC_FLAG_NO_MFMA is the only one device code reads)
+// host-side bits of Dims::flags (device code reads bit 0 = TMPC_FLAG_NO_MFMA and DF_LOWP / DF_LOWP_TRSM, tmpc_common.h)
 constexpr int DF_NO_SMALL = 2;   // tmpc_set_tuning(TMPC_TUNE_SMALL_BLOCKS, 0): the batched launch sequence also for dp = 16
-constexpr int DF_LOWP = 8;       // single-precision updates may be on for some problems (Opts::lowp_switch > 0 and the handle has the float32 copies): cr_factor launches their forward-substitution steps
 constexpr int DF_NO_DMA = 4;     // TMPC_DEBUG_FLAG_NO_DMA: the register-staged factorisation kernels (the path of blocks wider than 320) for every block size
 
 // Small blocks (dp = 16): one kernel per factorisation / per solve instead of a launch sequence per level (tmpc_cr_small.h); TMPC_SMALL=0: off
@@ -589,8 +589,13 @@ static void cr_factor(const WS& w, const Dims& dm, const CrSched& sc, const int*
     const long it_upd = (long)count * ((long)lv.nupd * (nm * (nm + 1) / 2) + (long)lv.nelim * nm * nm);
     mark(1);
     if (mf && use_dma && dm.nt <= TRR_NT) {
+      // the problems with single-precision updates solve in single precision too (DF_LOWP_TRSM): each kernel leaves the other's problems alone
       const size_t trsm_lds = (size_t)trd_lds_doubles() * sizeof(double);
-      hipLaunchKernelGGL(k_cr_trsm_dma, dim3(cr_grid((long)count * lv.nelim * 2 * nt64)), dim3(256), trsm_lds, st, w, dm, cd, lv.eoff, lv.nelim, count);
+      const bool trsm32 = (dm.flags & DF_LOWP_TRSM) != 0;
+      if (!trsm32 || nlowp < count)
+        hipLaunchKernelGGL(k_cr_trsm_dma, dim3(cr_grid((long)count * lv.nelim * 2 * nt64)), dim3(256), trsm_lds, st, w, dm, cd, lv.eoff, lv.nelim, count);
+      if (trsm32 && nlowp > 0)
+        hipLaunchKernelGGL(k_cr_trsm_dma_f32, dim3(cr_grid((long)count * lv.nelim * 2 * nt64)), dim3(256), (size_t)trf_lds_doubles() * sizeof(double), st, w, dm, cd, lv.eoff, lv.nelim, count);
     }
     else if (mf) hipLaunchKernelGGL((k_cr_trsm<true, 2>), dim3(cr_grid(it_trsm)), dim3(256), factor_lds(), st, w, dm, cd, lv.eoff, lv.nelim, count, rs);
     else hipLaunchKernelGGL((k_cr_trsm<false, 2>), dim3(cr_grid(it_trsm)), dim3(256), factor_lds(), st, w, dm, cd, lv.eoff, lv.nelim, count, rs);
@@ -730,8 +735,11 @@ static int run_chunk(tmpc_handle* h, Lane* ln, int nb, const double* dA, const d
   // (chord steps also with stage-local multipliers since round 3: their rows are part of the frozen blocks like everything else)
   o.fast_exit = (h->flags & TMPC_FLAG_FAST_EXIT) ? 1 : 0;
   if ((h->flags & (TMPC_FLAG_NO_MFMA | TMPC_DEBUG_FLAG_NO_DMA)) || !w.O32 || t3 || dm.dp <= 64 || dm.nt > TRR_NT) o.lowp_switch = 0.0;
+  // a factorisation that can end the centering phase is never a single-precision one: the switch sits at least a factor 16 above mu_t = tol * kappa
+  // (at the defaults, 1e-5 against 2^-25 ~ 3e-8, the clamp does not bind)
+  if (o.lowp_switch > 0.0) o.lowp_switch = fmax(o.lowp_switch, 16.0 * o.tol);
   if (o.lowp_switch > 0.0) {
-    dm.flags |= DF_LOWP;
+    dm.flags |= DF_LOWP | (h->tune_lowp_trsm ? DF_LOWP_TRSM : 0);
     // the float32 copies are laid out by this call's block width; where the last call used another one (a handle with room for rows serving the plain model, or
     // the other way round) its data sit where the zero padding of this call's rows must be
     if (ln->o32_dp != 0 && ln->o32_dp != dm.dp) HIPCHK(hipMemsetAsync(w.O32, 0, 2 * (size_t)h->dm.B * h->dm.p * h->dm.dp * ((h->dm.dp + 31) & ~31) * sizeof(float), st));
@@ -749,7 +757,7 @@ static int run_chunk(tmpc_handle* h, Lane* ln, int nb, const double* dA, const d
   else hipLaunchKernelGGL(k_init_stage, dim3(BPall), dim3(64), slots_bytes(2), st, wall, dm);
   {
     WS wi = wall; wi.alist = alist;      // k_init_prob fills the list (its own index is blockIdx: alist is only written)
-    hipLaunchKernelGGL(k_init_prob, dim3(nb), dim3(64), 0, st, wi, dm);
+    hipLaunchKernelGGL(k_init_prob, dim3(nb), dim3(64), 0, st, wi, dm, o.lowp_switch);
   }
   hipLaunchKernelGGL(k_init_state, dim3(BPall), dim3(64), 0, st, wall, dm);
   if (eq) hipLaunchKernelGGL(k_phi_init, dim3(BPall), dim3(64), 0, st, wall, dm);
@@ -1132,7 +1140,7 @@ static int create_handle(tmpc_handle** out, int chunk, int p, int nx, int mb, in
   h->dm = make_dims(cap, p, nx, mb, ng, nc, step3);
   h->sched = cr_build(p);
   h->rs = 0; h->mt = 0;
-  h->tune_small = 1; h->tune_pretest = 1; h->tune_fuse = 1; h->tune_graph = 1; h->tune_persist = 1;
+  h->tune_small = 1; h->tune_pretest = 1; h->tune_fuse = 1; h->tune_graph = 1; h->tune_persist = 1; h->tune_lowp_trsm = 1;
   h->opt.tol = 0x1p-25; h->opt.center_tol = 1e-9; h->opt.max_iter = 50; h->opt.center_iter = 12;
   h->opt.fast_exit = 0;
   h->opt.lowp_switch = TMPC_LOWP_SWITCH_DEFAULT;
@@ -1214,6 +1222,7 @@ int tmpc_set_tuning(tmpc_handle* h, int key, double value) {
     case TMPC_TUNE_FUSE_FWD: h->tune_fuse = value != 0.0; return TMPC_OK;
     case TMPC_TUNE_GRAPH: h->tune_graph = value != 0.0; return TMPC_OK;
     case TMPC_TUNE_PERSISTENT: if (!(value >= 0.0 && value <= 2.0)) return TMPC_E_ARG; h->tune_persist = (int)value; return TMPC_OK;
+    case TMPC_TUNE_LOWP_TRSM: h->tune_lowp_trsm = value != 0.0; return TMPC_OK;
     default: snprintf(g_err, sizeof(g_err), "tmpc_set_tuning: unknown key %d", key); return TMPC_E_ARG;
   }
 }

@@ -67,6 +67,7 @@ enum {
 typedef double double2_t __attribute__((ext_vector_type(2)));
 typedef double double4_t __attribute__((ext_vector_type(4)));
 typedef float float4_t __attribute__((ext_vector_type(4)));
+typedef float float2_t __attribute__((ext_vector_type(2)));
 enum { KF_XXX = 0, KF_SIXX, KF_KX, KF_KS, KF_FX, KF_FS, KF_PER_LMI = 6 };
 // adjoint slots per stage: 0: G = T1-T2 (rhs), 1: Psi (tau column), 2: PhiH (alpha column)
 enum { ADJ_G = 0, ADJ_PSI, ADJ_PHI, NADJ = 3 };
@@ -79,13 +80,16 @@ struct Dims {
   int d;        // nx(nx+1)/2
   int dp;       // d padded to a multiple of 16
   int nt;       // ceil(dp / TB)
-  int flags;    // bit0: debug - replace MFMA by scalar FMAs; bit3 (DF_LOWP, tmpc_api.hip): single-precision updates are on for this call (k_init_prob: the first iteration)
+  int flags;    // bit 0: debug - replace MFMA by scalar FMAs; DF_LOWP, DF_LOWP_TRSM below; bits 24-26: ablations (TMPC_ABLATE builds); other bits: host side only (tmpc_api.hip)
   int ng;       // rows of the equality-constraint Jacobian G_k per stage (0: none), <= NGM
   int nr;       // row stride of the stage-local multipliers: ng + (max rows of the active-constraint Jacobians C_k, Step 2), <= NRM
   int nz;       // stride of the stage-local variable vector: nr (+ 2 epigraph variables of the norm terms in Step 2)
   int constr;   // 1: Step 2 model (convexifier.py:116-131): multipliers of C_k and the rho-norm terms
   int nT;       // Step 3 (convexifier.py:137-147): n(n+1)/2 entries of the regularisation T_k per stage (0: none); + 1 epigraph variable (tmpc_t3.h)
 };
+// bits of Dims::flags that device code reads
+constexpr int DF_LOWP = 8;        // single-precision updates are on for this call (Opts::lowp_switch > 0, the handle has the float32 copies): k_init_prob decides the first iteration
+constexpr int DF_LOWP_TRSM = 16;  // ... and the triangular solves of those iterations run in single precision too (TMPC_TUNE_LOWP_TRSM): k_cr_trsm_dma_f32
 constexpr int NGM = 31;  // max ng
 constexpr int NCM = 31;  // max rows of C_k
 constexpr int NRM = NGM + NCM, NZM = NRM + 2;      // (nz <= 64: one lane per stage-local variable)

@@ -596,9 +596,278 @@ __global__ void __launch_bounds__(256, 2) k_cr_trsm_dma(WS w, Dims dm, CrDev cr,
   const double* Li = w.Linv + ((size_t)b * dm.p + node) * dm.nt * TB * TB;
   const int r0 = strip * 64;
   const bool lp = cr_lowp(w, b);
+  if (lp && (dm.flags & DF_LOWP_TRSM)) return;               // this problem's solves run in single precision: k_cr_trsm_dma_f32
   const int ld32 = cr_ld32(dm);
   trd_strip<false>(cr_edge(w, dm, b, slot) + (size_t)r0 * dp, Dk, Li, (dp - r0 < 64) ? dp - r0 : 64, dm.nt, dp, it, lds,
                    lp ? cr_edge32(w, dm, b, slot) + (size_t)r0 * ld32 : nullptr, ld32);
+}
+
+// ---- phase 2 in SINGLE precision (round 7): the walk of trd_strip<false> -- same items, same right-looking register-resident sweep, same slab stream --
+// with float32 accumulation on v_mfma_f32_16x16x4f32 (twice the fp64 matrix rate), for the problems whose updates run in single precision this iteration:
+// their O blocks are read only as the float32 copy (k_cr_update_dma_f32, k_cr_fwd_off, k_cr_bwd), so the fp64 arithmetic of the solve bought nothing.
+// E is read in fp64, negated and rounded into the accumulators; the L_ji / Linv_i slabs stream in fp64 exactly as in trd_strip (buffer_load ... lds, the
+// same swizzled 64 x 16 image) and are rounded to float32 on the fragment read (the factor stays the one fp64 copy: no second store in k_cr_potrf_dma, no
+// new workspace).  The parked X_i are float32 already: their A-operand image holds 16 floats per row, 16 KB for four slabs instead of 32 (48 KB of LDS in all).
+// Fragment layout: the OUTPUT is produced transposed -- the L slab is the instruction's A operand and X the B operand, so a lane holds 4 consecutive
+// COLUMNS of one row (row lane & 15 of the fragment, columns 4 (lane >> 4) .. + 3): E comes in as two 16-byte loads, X32 goes out as one float4 store.
+// A lane reads one 16-byte granule (a K pair) of row lane & 15 of both operands and feeds its two elements to two MFMAs -- A and B agree on which k a
+// slot means, the sum over k is the same.  Row lane & 15 of any 16-row group of a slab has the swizzle of row lane & 15, so one offset per half serves
+// every fragment read of the L slabs.  Float32 A image: row r of a slab holds k at float 4 (((k >> 1) & 3) ^ ((r >> 1) & 3)) + 2 (k >> 3) + (k & 1), so the
+// four k a lane feeds (granules fk and 4 + fk of the L slab) are one 16-byte read, and the eight lanes of an LDS cycle (rows fr .. fr + 7) hit distinct banks.
+// Accumulators: four sets of 4 x float4 (64 VGPRs, half of trd_strip's); every product step runs four independent MFMA chains
+// (C layout: the four row fragments; R layout: the column strips) against the 40-cycle dependent-issue latency.
+constexpr int trf_lds_doubles() { return 2048 + TRD_DEPTH * 2048; }       // float32 X_i (four 64 x 16 slabs) + the B steps in flight
+__device__ __forceinline__ void trf_strip(const double* X, const double* Dk, const double* Li, int rows, int nt, int dp, int it, double* lds, float* X32, int ld32) {
+  constexpr int ASL = 64 * 16, DP = TRD_DEPTH;              // floats per A slab
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int ws = (wv + it) & 3, wc0 = ws * 16;              // this wave's column strip ("C") or row fragment ("R"), as in trd_strip
+  const int fk = lane >> 4, fr = lane & 15;
+  const int i1 = (rows + 15) >> 4;
+  const int nlast = nt - 1, nbl = (dp - 64 * nlast < 64) ? dp - 64 * nlast : 64, ncl = nbl >> 4;
+  const int ntd = nt;
+  const bool rw = ws < i1;
+  float* At = (float*)lds;
+  double* Bs = lds + 2048;
+  unsigned voT[2], voL[2];
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int row = wv * 16 + 8 * h + (lane >> 3), c = lane & 7;
+    voT[h] = (unsigned)(row * TB + 2 * (c ^ dma_sw(row))) * 8u;
+    voL[h] = (unsigned)(row * dp + 2 * (c ^ dma_sw(row))) * 8u;
+  }
+  int of[2];                                                // L slab: granule 4 hh + fk of row fr (of any 16-row group), in doubles
+#pragma unroll
+  for (int hh = 0; hh < 2; ++hh) of[hh] = fr * 16 + 2 * ((4 * hh + fk) ^ dma_sw(fr));
+  const int asw = (fr >> 1) & 3, ofa = fr * 16 + 4 * (fk ^ asw);                           // float32 A image: this lane's four k of row fr
+  const int opa0 = 4 * ((2 * fk) & 3 ^ asw) + 2 * (fk >> 1), opa1 = 4 * ((2 * fk + 1) & 3 ^ asw) + 2 * (fk >> 1);    // where columns 4 fk, + 1 / 4 fk + 2, + 3 of a slab go
+  float4_t acc0[4], acc1[4], acc2[4], acc3[4];
+  int vmtot = 0, vmk0 = 0, vmk1 = 0, vmk2 = 0;
+#define TRF_NB(T) ((dp - 64 * (T) < 64) ? dp - 64 * (T) : 64)
+  // C layout: SET[i][r] = T[16 i + fr][wc0 + 4 fk + r] of tile I
+#define TRF_LOAD_C(I, SET)                                                                                  \
+  {                                                                                                         \
+    const bool on_ = wc0 < TRF_NB(I);                                                                       \
+    _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                          \
+      double2_t u0 = (double2_t){0.0, 0.0}, u1 = u0;                                                        \
+      if (on_ && i < i1) {                                                                                  \
+        gcptr2 cp = (gcptr2)(X + (size_t)(16 * i + fr) * dp + 64 * (I) + wc0 + 4 * fk);                     \
+        u0 = cp[0]; u1 = cp[1];                                                                             \
+      }                                                                                                     \
+      SET[i] = (float4_t){(float)-u0[0], (float)-u0[1], (float)-u1[0], (float)-u1[1]};                      \
+    }                                                                                                       \
+    if (on_) vmtot += 2 * i1;                                                                               \
+  }
+  // R layout: SET[c][r] = T[wc0 + fr][16 c + 4 fk + r] of tile I, strips c < NC
+#define TRF_LOAD_R(I, NC, SET)                                                                              \
+  {                                                                                                         \
+    _Pragma("unroll") for (int c = 0; c < 4; ++c) {                                                          \
+      double2_t u0 = (double2_t){0.0, 0.0}, u1 = u0;                                                        \
+      if (rw && c < (NC)) {                                                                                 \
+        gcptr2 cp = (gcptr2)(X + (size_t)(wc0 + fr) * dp + 64 * (I) + 16 * c + 4 * fk);                     \
+        u0 = cp[0]; u1 = cp[1];                                                                             \
+      }                                                                                                     \
+      SET[c] = (float4_t){(float)-u0[0], (float)-u0[1], (float)-u1[0], (float)-u1[1]};                      \
+    }                                                                                                       \
+    if (rw) vmtot += 2 * (NC);                                                                              \
+  }
+#define TRF_STORE_R(I, NC, SET)                                                                             \
+  if (rw) {                                                                                                 \
+    typedef float4_t __attribute__((address_space(1)))* gptr4;                                              \
+    _Pragma("unroll") for (int c = 0; c < 4; ++c)                                                            \
+      if (c < (NC)) *(gptr4)(X32 + (size_t)(wc0 + fr) * ld32 + 64 * (I) + 16 * c + 4 * fk) = SET[c];        \
+    vmtot += (NC);                                                                                          \
+  }
+  // (+-) set -> A operand (float32 image).  C: slab = this wave's strip, rows 16 i + fr; R: row wc0 + fr of the slabs c < NC
+#define TRF_PARK_C(SET)      /* negated */                                                                  \
+  {                                                                                                         \
+    _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                          \
+      float* q = At + ws * ASL + (16 * i + fr) * 16;                                                        \
+      *(float2_t*)(q + opa0) = (float2_t){-SET[i][0], -SET[i][1]};                                           \
+      *(float2_t*)(q + opa1) = (float2_t){-SET[i][2], -SET[i][3]};                                           \
+    }                                                                                                       \
+  }
+#define TRF_PARK_R(NC, SET, SG)                                                                             \
+  if (rw) {                                                                                                 \
+    _Pragma("unroll") for (int c = 0; c < 4; ++c) {                                                          \
+      if (c < (NC)) {                                                                                       \
+        float* q = At + c * ASL + (wc0 + fr) * 16;                                                          \
+        *(float2_t*)(q + opa0) = (float2_t){SG SET[c][0], SG SET[c][1]};                                     \
+        *(float2_t*)(q + opa1) = (float2_t){SG SET[c][2], SG SET[c][3]};                                     \
+      }                                                                                                     \
+    }                                                                                                       \
+  }
+#define TRF_ZERO(SET) { _Pragma("unroll") for (int i = 0; i < 4; ++i) SET[i] = (float4_t){0.f, 0.f, 0.f, 0.f}; }
+  int ii = 0, ij = 0, is = 0, nissued = 0, ndone = 0;
+#define TRF_ISSUE()          /* the slab stream of trd_strip */                                             \
+  {                                                                                                         \
+    if (ii < ntd) {                                                                                         \
+      double* dst_ = Bs + (nissued % DP) * 2048 + wv * 256;                                                 \
+      const int nsl_ = (ij == ii) ? (TRF_NB(ii) >> 4) : 4;                                                  \
+      const bool two_ = 2 * is + 1 < nsl_;                                                                  \
+      if (ij == ii) {                                                                                       \
+        const int nb_ = TRF_NB(ii);                                                                         \
+        const __amdgpu_buffer_rsrc_t rs_ = __builtin_amdgcn_make_buffer_rsrc((void*)(Li + (size_t)ii * TB * TB), 0, (int)(((unsigned)(nb_ - 1) * TB + (unsigned)nb_) * 8u), 0x00020000); \
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_, (lds_vptr)(dst_), 16, voT[0], is * 256, 0, 0);        \
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_, (lds_vptr)(dst_ + 128), 16, voT[1], is * 256, 0, 0);  \
+        if (two_) {                                                                                         \
+          __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_, (lds_vptr)(dst_ + 1024), 16, voT[0], is * 256 + 128, 0, 0);       \
+          __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_, (lds_vptr)(dst_ + 1024 + 128), 16, voT[1], is * 256 + 128, 0, 0); \
+        }                                                                                                   \
+      } else {                                                                                              \
+        const int nb_ = TRF_NB(ij);                                                                         \
+        const __amdgpu_buffer_rsrc_t rs_ = __builtin_amdgcn_make_buffer_rsrc((void*)(Dk + (size_t)(64 * ij) * dp + 64 * ii), 0, (int)(((unsigned)(nb_ - 1) * (unsigned)dp + 64u) * 8u), 0x00020000); \
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_, (lds_vptr)(dst_), 16, voL[0], is * 256, 0, 0);        \
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_, (lds_vptr)(dst_ + 128), 16, voL[1], is * 256, 0, 0);  \
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_, (lds_vptr)(dst_ + 1024), 16, voL[0], is * 256 + 128, 0, 0);         \
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_, (lds_vptr)(dst_ + 1024 + 128), 16, voL[1], is * 256 + 128, 0, 0);   \
+      }                                                                                                     \
+      vmtot += (ij == ii && !two_) ? 2 : 4;                                                                 \
+      { const int k_ = nissued % DP; if (k_ == 0) vmk0 = vmtot; else if (k_ == 1) vmk1 = vmtot; else vmk2 = vmtot; }  \
+      ++nissued;                                                                                            \
+      if (++is == ((nsl_ + 1) >> 1)) { is = 0; if (++ij >= ntd) { ++ii; ij = ii; } }                        \
+    }                                                                                                       \
+  }
+  // one 16-deep slab into TGT: the fp64 granules of the L slab rounded to float32, element e of granule 4 hh + fk into MFMA 2 hh + e, against element
+  // 2 hh + e of the lane's float4 of the A image.  C: the four row fragments x this wave's strip; R: this wave's fragment x the strips C0 <= c < NC
+#define TRF_MMA_C(TGT, AS, BS)                                                                              \
+  {                                                                                                         \
+    float4_t a_[4];                                                                                          \
+    _Pragma("unroll") for (int i = 0; i < 4; ++i) a_[i] = *(const float4_t*)((AS) + i * 256 + ofa);         \
+    _Pragma("unroll") for (int hh = 0; hh < 2; ++hh) {                                                      \
+      const double2_t b_ = *(const double2_t*)((BS) + wc0 * 16 + of[hh]);                                   \
+      _Pragma("unroll") for (int e = 0; e < 2; ++e) {                                                        \
+        const float bf_ = (float)b_[e];                                                                      \
+        _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                        \
+          TGT[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(bf_, a_[i][2 * hh + e], TGT[i], 0, 0, 0);           \
+      }                                                                                                     \
+    }                                                                                                       \
+  }
+#define TRF_MMA_R(TGT, AS, BS, C0, NC)                                                                      \
+  {                                                                                                         \
+    const float4_t a_ = *(const float4_t*)((AS) + wc0 * 16 + ofa);                                          \
+    _Pragma("unroll") for (int hh = 0; hh < 2; ++hh) {                                                      \
+      double2_t b_[4];                                                                                       \
+      _Pragma("unroll") for (int c = 0; c < 4; ++c)                                                          \
+        if (c >= (C0) && c < (NC)) b_[c] = *(const double2_t*)((BS) + c * 256 + of[hh]);                    \
+      _Pragma("unroll") for (int e = 0; e < 2; ++e) {                                                        \
+        _Pragma("unroll") for (int c = 0; c < 4; ++c)                                                        \
+          if (c >= (C0) && c < (NC)) TGT[c] = __builtin_amdgcn_mfma_f32_16x16x4f32((float)b_[c][e], a_[2 * hh + e], TGT[c], 0, 0, 0); \
+      }                                                                                                     \
+    }                                                                                                       \
+  }
+#define TRF_STEP_C(TGT) { TRF_MMA_C(TGT, A0, Bc) TRF_MMA_C(TGT, A0 + ASL, Bc + 1024) }
+#define TRF_STEP_D0(TGT) { TRF_MMA_R(TGT, At, Bc, 0, 4) TRF_MMA_R(TGT, At + ASL, Bc + 1024, 1, 4) }
+#define TRF_STEP_D1(TGT) { TRF_MMA_R(TGT, At + 2 * ASL, Bc, 2, 4) TRF_MMA_R(TGT, At + 3 * ASL, Bc + 1024, 3, 4) }
+#define TRF_STEP_RL(N) { TRF_MMA_R(acc0, A0, Bc, 0, N) TRF_MMA_R(acc0, A0 + ASL, Bc + 1024, 0, N) }
+
+  __syncthreads();
+  TRF_ISSUE()
+  if (DP > 2) TRF_ISSUE()
+  TRF_LOAD_C(0, acc0)
+  if (nt > 2) TRF_LOAD_C(1, acc1) else TRF_ZERO(acc1)
+  if (nt > 3) TRF_LOAD_C(2, acc2) else TRF_ZERO(acc2)
+  if (nt > 4) TRF_LOAD_C(3, acc3) else TRF_ZERO(acc3)
+  TRF_PARK_C(acc0)                                          // T_0 = E_0 (the set holds -E_0)
+  TRF_ZERO(acc0)
+#define TRF_STEP_BEGIN()                                                                                    \
+    { const int k_ = ndone % DP; vm_wait_le(vmtot - (k_ == 0 ? vmk0 : k_ == 1 ? vmk1 : vmk2)); }            \
+    __builtin_amdgcn_s_barrier();                                                                           \
+    TRF_ISSUE()                                                                                             \
+    const double* Bc = Bs + (ndone % DP) * 2048;                                                            \
+    ++ndone;
+#define TRF_PAIR_C(TGT)                                                                                     \
+  _Pragma("unroll 1") for (int cs = 0; cs < 2; ++cs) {                                                      \
+    TRF_STEP_BEGIN()                                                                                        \
+    const float* A0 = At + 2 * cs * ASL;                                                                    \
+    TRF_STEP_C(TGT)                                                                                         \
+  }
+#define TRF_PAIR_RL(N)                                                                                      \
+  _Pragma("unroll 1") for (int cs = 0; cs < 2; ++cs) {                                                      \
+    TRF_STEP_BEGIN()                                                                                        \
+    const float* A0 = At + 2 * cs * ASL;                                                                    \
+    if (rw) TRF_STEP_RL(N)                                                                                  \
+  }
+#define TRF_DIAG(TGT)                                                                                       \
+  {                                                                                                         \
+    { TRF_STEP_BEGIN() if (rw) TRF_STEP_D0(TGT) }                                                           \
+    { TRF_STEP_BEGIN() if (rw) TRF_STEP_D1(TGT) }                                                           \
+    TRF_STORE_R(ci, 4, TGT)                                                                                 \
+    if (ci + 1 < nt) {                                                                                      \
+      __builtin_amdgcn_s_barrier();                         /* every wave is done with T_i */               \
+      TRF_PARK_R(4, TGT, +)                                                                                 \
+    }                                                                                                       \
+  }
+  for (int ci = 0; ci < ntd; ++ci) {
+    const int nci = TRF_NB(ci) >> 4;
+    if (nci == 4) {
+      if (ci == 0 || ci == nlast) TRF_DIAG(acc0) else if (ci == 1) TRF_DIAG(acc1) else if (ci == 2) TRF_DIAG(acc2) else TRF_DIAG(acc3)
+    } else {                                                // a narrow last tile (always set 0): run-time strip range
+      for (int cs = 0; cs < ((nci + 1) >> 1); ++cs) {
+        TRF_STEP_BEGIN()
+        const float* A0 = At + 2 * cs * ASL;
+        if (rw) {
+          TRF_MMA_R(acc0, A0, Bc, 2 * cs, nci)
+          if (2 * cs + 1 < nci) TRF_MMA_R(acc0, A0 + ASL, Bc + 1024, 2 * cs + 1, nci)
+        }
+      }
+      TRF_STORE_R(ci, nci, acc0)
+    }
+    if (ci == 0 && nt > 1) TRF_LOAD_R(nlast, ncl, acc0)     // E_last: lands during the updates of the tiles before it
+    if (ci + 1 >= nt) break;
+    if (ci < 1 && 1 < nlast) TRF_PAIR_C(acc1)
+    if (ci < 2 && 2 < nlast) TRF_PAIR_C(acc2)
+    if (ci < 3 && 3 < nlast) TRF_PAIR_C(acc3)
+    if (ncl == 3) TRF_PAIR_RL(3) else if (ncl == 4) TRF_PAIR_RL(4) else if (ncl == 2) TRF_PAIR_RL(2) else TRF_PAIR_RL(1)
+    const int t = ci + 1;
+    __builtin_amdgcn_s_barrier();                           // every wave is done with X_i
+    if (t == nlast) { TRF_PARK_R(ncl, acc0, -) TRF_ZERO(acc0) }
+    else if (t == 1) { TRF_PARK_C(acc1) TRF_ZERO(acc1) }
+    else if (t == 2) { TRF_PARK_C(acc2) TRF_ZERO(acc2) }
+    else { TRF_PARK_C(acc3) TRF_ZERO(acc3) }
+  }
+#undef TRF_DIAG
+#undef TRF_PAIR_RL
+#undef TRF_PAIR_C
+#undef TRF_STEP_BEGIN
+#undef TRF_STEP_RL
+#undef TRF_STEP_D1
+#undef TRF_STEP_D0
+#undef TRF_STEP_C
+#undef TRF_MMA_R
+#undef TRF_MMA_C
+#undef TRF_ISSUE
+#undef TRF_ZERO
+#undef TRF_PARK_R
+#undef TRF_PARK_C
+#undef TRF_STORE_R
+#undef TRF_LOAD_R
+#undef TRF_LOAD_C
+#undef TRF_NB
+}
+
+// The items of k_cr_trsm_dma for the problems with single-precision updates this iteration (cr_lowp) when the call has the float32 solves on (DF_LOWP_TRSM):
+// X_x = T[x,i] L_i^-T in float32 into the float32 O copy only; the fp64 O blocks of such a problem are neither written nor read in that iteration.
+__global__ void __launch_bounds__(256, 2) k_cr_trsm_dma_f32(WS w, Dims dm, CrDev cr, int eoff, int nelim, int count) {
+  const int dp = dm.dp;
+  const int nst = (dp + 63) / 64;
+  const int per = 2 * nst;
+  const int it = cr_item(count * nelim * per);
+  if (it < 0) return;
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  const int g = it / per, r = it - g * per;
+  const int b = cr.alist[g / nelim];
+  if (!cr_lowp(w, b)) return;                               // this problem's solves run in fp64: k_cr_trsm_dma
+  const int* er = cr.elim + (size_t)(eoff + g % nelim) * CR_EW;
+  const int which = r / nst, strip = r - which * nst;
+  const int slot = which ? er[CE_EB] : er[CE_EA];
+  if (slot < 0) return;
+  const int node = er[CE_NODE];
+  const double* Dk = w.D + ((size_t)b * dm.p + node) * (size_t)dp * dp;
+  const double* Li = w.Linv + ((size_t)b * dm.p + node) * dm.nt * TB * TB;
+  const int r0 = strip * 64;
+  const int ld32 = cr_ld32(dm);
+  trf_strip(cr_edge(w, dm, b, slot) + (size_t)r0 * dp, Dk, Li, (dp - r0 < 64) ? dp - r0 : 64, dm.nt, dp, it, lds, cr_edge32(w, dm, b, slot) + (size_t)r0 * ld32, ld32);
 }
 
 // ---- phase 1 on the same sweep: block row r of the factor is the triangular solve of the row strip r of D against the rows above it,
@@ -758,9 +1027,10 @@ __global__ void __launch_bounds__(256, 4) k_cr_update_dma(WS w, Dims dm, CrDev c
   }
 }
 
-// The same items for the problems whose Schur-complement updates run in SINGLE precision this iteration (I_LOWP, set by k_ctrl_a while mu / kappa > Opts::lowp_switch in
-// the first LOWP_ITERS iterations): float32 copies of the O blocks (written next to the fp64 ones by k_cr_trsm_dma), float32 accumulation on v_mfma_f32_16x16x4f32
-// (wg_tile_dma_f32), the result subtracted from / stored into the fp64 blocks.  No fused right-hand sides: k_cr_fwd_off runs for these problems (cr_factor).
+// The same items for the problems whose Schur-complement updates run in SINGLE precision this iteration (I_LOWP, decided one iteration ahead by k_ctrl_d -- by
+// k_init_prob for the first -- while the predicted mu > Opts::lowp_switch * max(1, |tau|)): float32 copies of the O blocks (written INSTEAD of the fp64 ones by
+// k_cr_trsm_dma_f32, or by k_cr_trsm_dma with TMPC_TUNE_LOWP_TRSM = 0), float32 accumulation on v_mfma_f32_16x16x4f32 (wg_tile_dma_f32), the result subtracted
+// from / stored into the fp64 blocks.  No fused right-hand sides: k_cr_fwd_off runs for these problems (cr_factor).
 __global__ void __launch_bounds__(256, 5) k_cr_update_dma_f32(WS w, Dims dm, CrDev cr, int eoff, int nelim, int uoff, int nupd, int count) {
   const int dp = dm.dp;
   const int nm = (dp + 63) / 64;

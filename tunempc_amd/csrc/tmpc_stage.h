@@ -77,7 +77,7 @@ __global__ void __launch_bounds__(64) k_init_stage(WS w, Dims dm) {
   }
 }
 
-__global__ void __launch_bounds__(64) k_init_prob(WS w, Dims dm) {
+__global__ void __launch_bounds__(64) k_init_prob(WS w, Dims dm, double lowp_switch) {
   const int b = blockIdx.x, lane = threadIdx.x;
   double lo = 1e300, amin = 1e10 /* convexifier.py:383 */, amax = 0.0;
   for (int k = lane; k < dm.p; k += 64) {
@@ -100,8 +100,10 @@ __global__ void __launch_bounds__(64) k_init_prob(WS w, Dims dm) {
     ip[I_PHASE] = early ? PH_DONE : PH_MAIN;
     ip[I_IPMSTATUS] = early ? IPM_OPTIMAL : IPM_MAXITER;
     if (!early) { const int slot = atomicAdd(w.active, 1); w.alist[slot] = b; w.flist[slot] = b; }
-    // the first factorisation with single-precision updates when the call has them on (later iterations: k_ctrl_d)
-    if (!early && (dm.flags & 8) && w.O32) { ip[I_LOWP] = 1; atomicAdd(w.active + 4, 1); }
+    // the first factorisation: single precision when the call has it on and the starting point passes the test of k_ctrl_d (later iterations), mu > lowp_switch *
+    // max(1, |tau|) -- with the lower bound 2 / N of the starting mu (X1 = x0 I, S1 = I, X2 = x0 S2 with S2 = tau I - alpha Hb >= I: every stage adds at least 2 n x0 to the
+    // trace; N = 2 p n + 1 is the plain model's cone dimension -- the multiplier cones of the models with rows add to both sides)
+    if (!early && (dm.flags & DF_LOWP) && w.O32 && 2.0 / (double)(2 * dm.p * dm.n + 1) > lowp_switch * fmax(1.0, fabs(pr[P_TAU]))) { ip[I_LOWP] = 1; atomicAdd(w.active + 4, 1); }
   }
 }
 
