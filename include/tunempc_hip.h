@@ -269,6 +269,30 @@ int tmpc_eig_scan_host(tmpc_handle* h, int nb, const double* H, double* out);
  * orthogonalise the vectors to the rounding level (~2 sqrt(n) eps); the outputs then hold the last iterate. */
 int tmpc_eig_clip_host(int nb, int n, const double* A, double tol, double* out, double* evals, double* reg, int32_t* sweeps);
 
+/* Periodic LQR gains: the local feedback law of a (tuned) scheme, its cost-to-go and closed-loop monodromy (reference: convexifier.py:44-45, the LQR
+ * problems on H and on Hc = H + dHc share their feedback law; examples/convex_lqr.py:52-58).  Stage k of problem b, indices mod p, x block of H first:
+ *     E = [A_k B_k],  Hb = H_k + E' Pi_{k+1} E,  S = Hb_uu,  M = Hb_ux,  K_k = S^-1 M  (u = -K_k x, the sign of scipy / control.dare),
+ *     Pi_k = sym(Hb_xx - M' K_k).
+ * A sweep runs k = p-1 ... 0 starting from Pi = Pi0 [nb][p][nx][nx] (NULL: zero; the sweep reads Pi0_0 first, the other stages only enter the change
+ * measure); sweeps repeat until max_k max|Pi_k - Pi_k(previous sweep)| / max(1, max|Pi_k|) <= tol or max_sweeps is reached, all inside one launch.
+ * A [nb][p][nx][nx], B [nb][p][nx][mb], H [nb][p][n][n] (n = nx + mb <= TMPC_LQR_NMAX, any p, nb >= 1).  Outputs: K [nb][p][mb][nx], Pi [nb][p][nx][nx],
+ * Phi [nb][nx][nx] (optional) = (A_{p-1} - B_{p-1} K_{p-1}) ... (A_0 - B_0 K_0), and per problem info [nb][8]:
+ *   [0] status: 0 converged, 1 max_sweeps reached (K, Pi, Phi hold the last iterate), 2 S numerically singular at a stage, 3 non-finite iterate
+ *       (2, 3: the problem stops there, Phi is NaN, K / Pi hold what was written until then; other problems are not affected),
+ *   [1] sweeps used, [2] last relative change, [3] / [4] smallest / largest |pivot| of S over the last sweep,
+ *   [5] 1.0 if the elimination of the last sweep never left a positive diagonal pivot (S positive definite at every stage; 0.0: not shown),
+ *   [6] the same over EVERY sweep of the call (at a converged Pi the S of the H side equals the positive definite S of the Hc side, so [5] reads 1 there
+ *       whatever the path was; [6] tells whether the path from Pi0 met an indefinite S), [7] reserved.
+ * S is solved by elimination with row pivoting, so a symmetric indefinite S (the usual case from Pi0 = 0 with an indefinite H) is handled.
+ * With the P of a convexification (Hc_k = H_k + calH_k(P)) the H-recursion from Pi0 = +P is the Hc-recursion from zero shifted by P, iterate by iterate.
+ * Returns TMPC_OK when the call ran; TMPC_E_UNSUPPORTED for nx + mb > TMPC_LQR_NMAX (checked before the device is touched).
+ * _host: host pointers (device scratch kept between calls).  _device: device pointers, current device, null stream, synchronised before returning. */
+#define TMPC_LQR_NMAX 64
+int tmpc_periodic_lqr_batch_host(int nb, int p, int nx, int mb, const double* A, const double* B, const double* H, const double* Pi0, double tol,
+                                 int max_sweeps, double* K, double* Pi, double* Phi, double* info);
+int tmpc_periodic_lqr_batch_device(int nb, int p, int nx, int mb, const double* A, const double* B, const double* H, const double* Pi0, double tol,
+                                   int max_sweeps, double* K, double* Pi, double* Phi, double* info);
+
 /* Accumulated hipEvent timings since the last call (ms) when TMPC_FLAG_PROFILE is set, 16 doubles:
  * out[0] stage_pre+ctrl, [1] schur assembly, [2] block factorisation (all kernels of tmpc_cr.h's factor phase), [3] predictor
  * pass, [4] corrector pass + update, [5] number of factorisation phases (= IPM iterations of the chunks), [6] total ms of the

@@ -1,0 +1,99 @@
+"""Device-resident timing of the periodic LQR kernel and of the feedback-equivalence certificate (tunempc_amd/lqr.py, csrc/tmpc_lqr.h):
+  - the bench batch: 512 problems of synthetic.gen_batch(100000, ., 64, 24, 8), certificate on the Hc / P of convexify_batch,
+  - c1 (tests/golden/c1_convex_lqr.npz) at batch 1: 214 dependent sweeps, the latency case,
+  - c3 (tests/golden/c3_evaporation_shape.npz, its three members tiled) at batch 256.
+Inputs live in HBM; HIP events around (a) the C entry alone (`entry_ms`: launch + synchronise), (b) periodic_lqr_batch (`call_ms`: plus the spectral radii
+on the host) and (c) feedback_equivalence_batch (`certificate_ms`: two recursions and the comparison).  Warm-up, then the median of --reps calls.
+Compared with: the numpy statement of the recursion on this host (tests/lqr_reference.py, one pass) and the convexify step of the same batch (BENCH_r06.json).
+
+    python scripts/lqr_timing.py [--reps 15] [--batch 512] [--out profiles/lqr_timing.json]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, 'tests'))
+import lqr_reference as lr  # noqa: E402
+from tunempc_amd import _lib, convexifier, lqr, synthetic  # noqa: E402
+
+
+def median_ms(fn, reps, warmup=3):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(); fn(); e1.record(); e1.synchronize()
+        ts.append(e0.elapsed_time(e1))
+    ts.sort()
+    return dict(median=ts[len(ts) // 2], min=ts[0], max=ts[-1], reps=reps)
+
+
+def measure(tag, A, B, H, Hc, P, reps, numpy_members):
+    dev = [torch.from_numpy(np.ascontiguousarray(x)).cuda() for x in (A, B, H, Hc, P)]
+    dA, dB, dH, dHc, dP = dev
+    out = lqr.periodic_lqr_batch(dA, dB, dH)
+    cert = lqr.feedback_equivalence_batch(dA, dB, dH, dHc)
+    certP = lqr.feedback_equivalence_batch(dA, dB, dH, dHc, P=dP)
+    res = dict(shape=dict(nb=int(A.shape[0]), p=int(A.shape[1]), nx=int(A.shape[2]), nu=int(B.shape[3])),
+               sweeps=[int(out['sweeps'].min()), int(out['sweeps'].max())], converged=int((out['status'] == 0).sum()),
+               dK_max=float(cert['dK'].max()), dK_max_from_P=float(certP['dK'].max()), rho_max=float(np.nanmax(out['rho'])),
+               S_positive_definite_on_path=dict(from_zero=int((cert['posdef_H'] == 1.0).sum()), from_P=int((certP['posdef_H'] == 1.0).sum())))
+    res['entry_ms'] = median_ms(lambda: _lib.periodic_lqr_batch_device(dA, dB, dH, None, 1e-13, 5000), reps)
+    res['call_ms'] = median_ms(lambda: lqr.periodic_lqr_batch(dA, dB, dH), reps)
+    res['certificate_ms'] = median_ms(lambda: lqr.feedback_equivalence_batch(dA, dB, dH, dHc), reps)
+    res['certificate_from_P_ms'] = median_ms(lambda: lqr.feedback_equivalence_batch(dA, dB, dH, dHc, P=dP), reps)
+    m = min(numpy_members, A.shape[0])
+    t = time.perf_counter(); lr.periodic_lqr_batch(A[:m], B[:m], H[:m]); el = time.perf_counter() - t
+    res['numpy_reference_ms'] = dict(members_timed=m, ms_for_them=el * 1e3, ms_scaled_to_batch=el * 1e3 * A.shape[0] / m, note='one CPU thread, one pass')
+    print(tag, json.dumps(res))
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--reps', type=int, default=15)
+    ap.add_argument('--batch', type=int, default=512)
+    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'lqr_timing.json'))
+    ap.add_argument('--kernel-only', action='store_true', help='one pass over the three inputs without timing (for a kernel trace)')
+    args = ap.parse_args()
+    assert args.reps >= 10 or args.kernel_only
+    cases = {}
+    A, B, H = synthetic.gen_batch(100000, args.batch, 64, 24, 8)
+    conv, tconv = dict(Hc=H, P=A), 0.0
+    if not args.kernel_only:
+        t = time.perf_counter(); conv = convexifier.convexify_batch(A, B, H); tconv = (time.perf_counter() - t) * 1e3
+    cases['bench batch %d x (p 64, nx 24, nu 8)' % args.batch] = (A, B, H, conv['Hc'], conv['P'], 32)
+    g = lr.load_golden('c1_convex_lqr')
+    cases['c1 batch 1 (p 1, nx 3, nu 1)'] = (g['A'], g['B'], g['H'], g['Hc'], g['P'], 1)
+    g = lr.load_golden('c3_evaporation_shape')
+    tile = lambda x: np.tile(x, (86, 1, 1, 1))[:256].copy()
+    cases['c3 batch 256 (p 50, nx 2, nu 2)'] = tuple(tile(g[k]) for k in ('A', 'B', 'H', 'Hc', 'P')) + (256,)
+    if args.kernel_only:
+        for tag, (A_, B_, H_, Hc_, P_, _) in cases.items():
+            d = [torch.from_numpy(np.ascontiguousarray(x)).cuda() for x in (A_, B_, H_)]
+            for _ in range(3):
+                lqr.periodic_lqr_batch(*d)
+        return
+    out = dict(device=torch.cuda.get_device_name(0), reps=args.reps,
+               compared_with=dict(convexify_step_ms_BENCH_r06=json.load(open(os.path.join(ROOT, 'BENCH_r06.json')))['parsed']['ms_per_step'],
+                                  convexify_batch_host_entry_ms_this_run=tconv, optimal_members=int((conv['status'] == 0).sum())),
+               cases={tag: measure(tag, *c[:5], args.reps, c[5]) for tag, c in cases.items()})
+    bench = next(iter(out['cases'].values()))
+    out['certificate_share_of_convexify_step'] = bench['certificate_ms']['median'] / out['compared_with']['convexify_step_ms_BENCH_r06']
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, 'w') as f:
+        json.dump(out, f, indent=1)
+    print('wrote', args.out, 'certificate / convexify step = %.4f' % out['certificate_share_of_convexify_step'])
+
+
+if __name__ == '__main__':
+    main()

@@ -29,6 +29,7 @@
 #include "tmpc_phi.h"
 #include "tmpc_t3.h"
 #include "tmpc_eig.h"
+#include "tmpc_lqr.h"
 #include "tmpc_dd.h"
 #include "tmpc_big.h"
 
@@ -1066,6 +1067,7 @@ static bool rows_ok(int nx, int ng, int nc) {
 // stage blocks beyond NBM = 64: the plain model only (the multiplier and Step 3 kernels keep one lane per entry of an n-vector)
 static bool model_dims_ok(int nx, int mb, int ng, int nc, int step3) { return nx + mb <= NBM || (ng == 0 && nc == 0 && !step3); }
 static_assert(AEL == TMPC_ARROW_LD, "tunempc_hip.h: leading dimension of the exported arrow blocks");
+static_assert(LQR_NMAX == TMPC_LQR_NMAX, "tunempc_hip.h: largest stage block of the periodic LQR recursion");
 static_assert(NGM == TMPC_MAX_ROWS && NCM == TMPC_MAX_ROWS, "tunempc_hip.h: row limits");
 static uint64_t workspace_bytes(int chunk, int p, int nx, int mb, int ng, int nc, int step3) {
   if (chunk < 1 || !dims_ok(p, nx, mb) || !rows_ok(nx, ng, nc) || !model_dims_ok(nx, mb, ng, nc, step3)) return 0;
@@ -1722,6 +1724,66 @@ int tmpc_eig_clip_host(int nb, int n, const double* A, double tol, double* out, 
     snprintf(g_err, sizeof(g_err), "tmpc_eig_clip_host: %d Jacobi sweeps without convergence (largest relative off-diagonal %.3e, threshold %.3e)", sw, worst, thr);
     return TMPC_E_NOCONV;
   }
+  return TMPC_OK;
+}
+
+// Periodic LQR gains by backward Riccati sweeps (tmpc_lqr.h): the whole iteration of a problem is one workgroup of one launch.
+// No handle; the device is the current one.  Sizes are refused before any HIP call.
+static int lqr_check(const char* who, int nb, int p, int nx, int mb, const void* A, const void* B, const void* H, double tol, int max_sweeps,
+                     const void* K, const void* Pi, const void* info) {
+  if (nb < 1 || p < 1 || nx < 1 || mb < 1 || !A || !B || !H || !K || !Pi || !info || !(tol >= 0.0) || max_sweeps < 1) {
+    snprintf(g_err, sizeof(g_err), "%s: bad argument (nb, p, nx, nu >= 1, max_sweeps >= 1, tol >= 0, non-null A, B, H, K, Pi, info)", who);
+    return TMPC_E_ARG;
+  }
+  if (nx + mb > LQR_NMAX) {
+    snprintf(g_err, sizeof(g_err), "%s: the periodic LQR recursion handles stage blocks up to nx + nu = %d (got %d)", who, LQR_NMAX, nx + mb);
+    return TMPC_E_UNSUPPORTED;
+  }
+  return TMPC_OK;
+}
+
+static int lqr_launch(int nb, int p, int nx, int mb, const double* A, const double* B, const double* H, const double* Pi0, double tol, int max_sweeps,
+                      double* K, double* Pi, double* Phi, double* info) {
+  const LqrLds L = lqr_lds(nx, mb);
+  const size_t lds_bytes = (size_t)L.total * sizeof(double);
+  static const int lds_max = [] { int m = 0; for (int x = 1; x < LQR_NMAX; ++x) m = std::max(m, lqr_lds(x, LQR_NMAX - x).total); return m * (int)sizeof(double); }();
+  HIPCHK(hipFuncSetAttribute((const void*)k_periodic_lqr, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));      // (the same value from every thread and call)
+  int lcw = 0;
+  while ((1 << lcw) < nx + mb) ++lcw;
+  hipLaunchKernelGGL(k_periodic_lqr, dim3(nb), dim3(LQR_NT), lds_bytes, 0, p, nx, mb, lcw, A, B, H, Pi0, tol, max_sweeps, K, Pi, Phi, info);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(0));
+  return TMPC_OK;
+}
+
+int tmpc_periodic_lqr_batch_device(int nb, int p, int nx, int mb, const double* A, const double* B, const double* H, const double* Pi0, double tol,
+                                   int max_sweeps, double* K, double* Pi, double* Phi, double* info) {
+  const int rc = lqr_check("tmpc_periodic_lqr_batch_device", nb, p, nx, mb, A, B, H, tol, max_sweeps, K, Pi, info);
+  if (rc != TMPC_OK) return rc;
+  return lqr_launch(nb, p, nx, mb, A, B, H, Pi0, tol, max_sweeps, K, Pi, Phi, info);
+}
+
+static thread_local EigScratch g_lqr_scratch;      // device images of the host entry, kept between calls and grown on demand
+
+int tmpc_periodic_lqr_batch_host(int nb, int p, int nx, int mb, const double* A, const double* B, const double* H, const double* Pi0, double tol,
+                                 int max_sweeps, double* K, double* Pi, double* Phi, double* info) {
+  const int rc = lqr_check("tmpc_periodic_lqr_batch_host", nb, p, nx, mb, A, B, H, tol, max_sweeps, K, Pi, info);
+  if (rc != TMPC_OK) return rc;
+  const size_t n = (size_t)nx + mb, st = (size_t)nb * p;
+  const size_t cA = st * nx * nx, cB = st * nx * mb, cH = st * n * n, cPhi = (size_t)nb * nx * nx, cI = (size_t)nb * 8;
+  HIPCHK(g_lqr_scratch.reserve((3 * cA + 2 * cB + cH + cPhi + cI) * 8));      // A | B | H | Pi0 | K | Pi | Phi | info
+  double* dA = (double*)g_lqr_scratch.p; double* dB = dA + cA; double* dH = dB + cB; double* dP0 = dH + cH; double* dK = dP0 + cA; double* dPi = dK + cB;
+  double* dPhi = dPi + cA; double* dI = dPhi + cPhi;
+  HIPCHK(hipMemcpy(dA, A, cA * 8, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dB, B, cB * 8, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dH, H, cH * 8, hipMemcpyHostToDevice));
+  if (Pi0) HIPCHK(hipMemcpy(dP0, Pi0, cA * 8, hipMemcpyHostToDevice));
+  const int rl = lqr_launch(nb, p, nx, mb, dA, dB, dH, Pi0 ? dP0 : nullptr, tol, max_sweeps, dK, dPi, Phi ? dPhi : nullptr, dI);
+  if (rl != TMPC_OK) return rl;
+  HIPCHK(hipMemcpy(K, dK, cB * 8, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(Pi, dPi, cA * 8, hipMemcpyDeviceToHost));
+  if (Phi) HIPCHK(hipMemcpy(Phi, dPhi, cPhi * 8, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(info, dI, cI * 8, hipMemcpyDeviceToHost));
   return TMPC_OK;
 }
 

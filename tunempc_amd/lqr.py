@@ -1,0 +1,179 @@
+"""Periodic LQR gains on the GPU and the feedback-equivalence certificate of a convexification.
+
+The convexifier promises (reference convexifier.py:44-45) that the LQR problem on the convexified Hessian H + dH has the same feedback
+law as the one on the indefinite H; the reference checks it once, at p = 1, with two `dare` calls (examples/convex_lqr.py:52-58).  This
+module computes the gains K_k of a p-periodic problem by backward Riccati sweeps (one launch per batch, csrc/tmpc_lqr.h) and measures
+that sentence on any batch:
+
+    periodic_lqr_batch(A, B, H, Pi0=None, tol=1e-13, max_sweeps=5000)     batched arrays (numpy -> host entry, torch GPU tensors -> device entry)
+    periodic_lqr(A, B, Q, R, N)                                           the reference's calling style -> (K_list, Pi_list, rho)
+    feedback_equivalence_batch(A, B, H, Hc, P=None)                       max |K(H) - K(Hc)| per problem, both closed-loop spectral radii
+    feedback_equivalence(A, B, Q, R, N, dHc)                              the same on what `convexify` takes and returns
+
+Conventions: stage cost 1/2 [x;u]' H_k [x;u] with H_k = [[Q_k, N_k], [N_k', R_k]] (x block first, the layout of convexify_batch),
+x_{k+1} = A_k x_k + B_k u_k, and u = -K_k x: the sign of scipy.linalg.solve_discrete_are / control.dare.
+There is no CPU path: the recursion runs in the HIP library or the call raises.
+"""
+import numpy as np
+
+from . import _lib
+from . import preprocessing
+from .convexifier import _to_array
+
+STATUS_NAMES = {0: 'Converged', 1: 'MaxSweeps', 2: 'SingularS', 3: 'NonFinite'}
+
+
+def _is_torch(x):
+    return type(x).__module__.split('.')[0] == 'torch'
+
+
+def _validate(A, B, H, extra=()):
+    """Shapes and dtypes of a batch, before any device call.  extra: (name, array-or-None, 'A' | 'H') further arrays of the shape of A or of H.
+    Returns (use_torch, nb, p, nx, mb)."""
+    named = [('A', A), ('B', B), ('H', H)] + [(nm, x) for nm, x, _ in extra if x is not None]
+    use_torch = _is_torch(A)
+    for nm, x in named:
+        if _is_torch(x) != use_torch:
+            raise ValueError('periodic_lqr_batch: A, B, H (and Pi0 / Hc / P) must be all numpy arrays or all torch tensors ({} differs)'.format(nm))
+        if x is None or not hasattr(x, 'shape') or not hasattr(x, 'dtype'):
+            raise ValueError('periodic_lqr_batch: {} must be an array'.format(nm))
+        if use_torch:
+            import torch
+            if x.dtype != torch.float64 or not x.is_cuda or x.device != A.device:
+                raise ValueError('periodic_lqr_batch: torch tensors must be float64 tensors of one GPU ({}: {}, {})'.format(nm, x.dtype, x.device))
+        elif np.asarray(x).dtype != np.float64:
+            raise ValueError('periodic_lqr_batch: fp64 arrays expected ({} has dtype {})'.format(nm, np.asarray(x).dtype))
+    if len(A.shape) != 4 or A.shape[2] != A.shape[3]:
+        raise ValueError('periodic_lqr_batch: A [nb, p, nx, nx] expected, got {}'.format(tuple(A.shape)))
+    nb, p, nx, _ = (int(v) for v in A.shape)
+    if len(B.shape) != 4 or tuple(B.shape[:3]) != (nb, p, nx):
+        raise ValueError('periodic_lqr_batch: B [nb, p, nx, nu] = [{}, {}, {}, nu] expected, got {}'.format(nb, p, nx, tuple(B.shape)))
+    mb = int(B.shape[3])
+    if nb < 1 or p < 1 or nx < 1 or mb < 1:
+        raise ValueError('periodic_lqr_batch: nb, p, nx, nu >= 1 expected, got nb = {}, p = {}, nx = {}, nu = {}'.format(nb, p, nx, mb))
+    n = nx + mb
+    if tuple(H.shape) != (nb, p, n, n):
+        raise ValueError('periodic_lqr_batch: H [nb, p, nx + nu, nx + nu] = {} expected, got {}'.format((nb, p, n, n), tuple(H.shape)))
+    for nm, x, like in extra:
+        want = (nb, p, nx, nx) if like == 'A' else (nb, p, n, n)
+        if x is not None and tuple(x.shape) != want:
+            raise ValueError('periodic_lqr_batch: {} {} expected, got {}'.format(nm, want, tuple(x.shape)))
+    return use_torch, nb, p, nx, mb
+
+
+def _contig(x, use_torch):
+    if x is None:
+        return None
+    return x.contiguous() if use_torch else np.ascontiguousarray(x, dtype=np.float64)
+
+
+def _rho(Phi):
+    """Spectral radius of each closed-loop monodromy (host, numpy.linalg.eigvals: nb small matrices); nan where Phi is not finite."""
+    Phi = np.asarray(Phi)
+    out = np.full(Phi.shape[0], np.nan)
+    ok = np.isfinite(Phi).all(axis=(1, 2))
+    if ok.any():
+        out[ok] = np.abs(np.linalg.eigvals(Phi[ok])).max(axis=1)
+    return out
+
+
+def periodic_lqr_batch(A, B, H, Pi0=None, tol=1e-13, max_sweeps=5000):
+    """Gains of nb p-periodic LQ problems.  A [nb,p,nx,nx], B [nb,p,nx,nu], H [nb,p,n,n] (n = nx + nu <= 64), fp64; per stage, indices mod p,
+
+        E = [A_k B_k],  Hb = H_k + E' Pi_{k+1} E,  S = Hb_uu,  M = Hb_ux,  K_k = S^-1 M  (u = -K_k x),  Pi_k = sym(Hb_xx - M' K_k),
+
+    swept k = p-1 ... 0 from Pi = Pi0 [nb,p,nx,nx] (None: zero) until max_k max|dPi_k| / max(1, max|Pi_k|) <= tol or max_sweeps sweeps.
+    S is solved by elimination with row pivoting: it need not be positive definite (from zero it usually is not for an indefinite H).
+
+    numpy arrays run through the host entry; torch tensors on a GPU through the device entry (torch tensors out, A / B / H are not copied).
+    Returns dict: K [nb,p,nu,nx], Pi [nb,p,nx,nx], Phi [nb,nx,nx] (closed-loop monodromy (A-BK)_{p-1} ... (A-BK)_0), rho [nb] (numpy: its
+    spectral radius, nan where Phi is not finite), status [nb] (0 converged, 1 max_sweeps reached, 2 singular S, 3 non-finite iterate),
+    sweeps [nb], info [nb,8] (status, sweeps, last relative change, smallest / largest |pivot| of S in the last sweep, 1.0 if S was shown
+    positive definite at every stage of the last sweep, the same over every sweep of the call, reserved).  ValueError: shapes / dtypes; NotImplementedError: n > 64."""
+    use_torch, nb, p, nx, mb = _validate(A, B, H, (('Pi0', Pi0, 'A'),))
+    if not (float(tol) >= 0.0) or int(max_sweeps) < 1:
+        raise ValueError('periodic_lqr_batch: tol >= 0 and max_sweeps >= 1 expected, got {}, {}'.format(tol, max_sweeps))
+    A, B, H, Pi0 = (_contig(x, use_torch) for x in (A, B, H, Pi0))
+    if use_torch:
+        K, Pi, Phi, info = _lib.periodic_lqr_batch_device(A, B, H, Pi0, tol, max_sweeps)       # (either entry refuses n > 64 before it touches the device)
+        rho = _rho(Phi.cpu().numpy())
+        import torch
+        status = info[:, 0].to(torch.int32); sweeps = info[:, 1].to(torch.int32)
+    else:
+        K, Pi, Phi, info = _lib.periodic_lqr_batch_host(A, B, H, Pi0, tol, max_sweeps)
+        rho = _rho(Phi)
+        status = info[:, 0].astype(np.int32); sweeps = info[:, 1].astype(np.int32)
+    return dict(K=K, Pi=Pi, Phi=Phi, rho=rho, status=status, sweeps=sweeps, info=info)
+
+
+def _stack_stages(A, B, Q, R, N):
+    """The reference's calling style (single matrices or lists of length p, np.matrix / CasADi DM accepted) -> A, B, H [1,p,...]."""
+    arg = preprocessing.input_checks({'A': A, 'B': B, 'Q': Q, 'R': R, 'N': N})
+    As = np.stack([_to_array(a) for a in arg['A']]); Bs = np.stack([_to_array(b) for b in arg['B']])
+    period, nx, _ = As.shape
+    nu = Bs.shape[2]
+    Hs = np.zeros((period, nx + nu, nx + nu))
+    for k in range(period):
+        Qk, Rk, Nk = _to_array(arg['Q'][k]), _to_array(arg['R'][k]), _to_array(arg['N'][k])
+        if Qk.shape != (nx, nx) or Rk.shape != (nu, nu) or Nk.shape != (nx, nu) or Bs[k].shape != (nx, nu):
+            raise ValueError('periodic_lqr: A (nx,nx), B (nx,nu), Q (nx,nx), R (nu,nu), N (nx,nu) expected at stage {}'.format(k))
+        Hs[k, :nx, :nx] = Qk; Hs[k, nx:, nx:] = Rk; Hs[k, :nx, nx:] = Nk; Hs[k, nx:, :nx] = Nk.T
+    return As[None], Bs[None], Hs[None]
+
+
+def periodic_lqr(A, B, Q, R, N, tol=1e-13, max_sweeps=5000):
+    """The gains of one problem in the reference's calling style: A, B, Q, R, N single matrices (p = 1) or lists of length p, as `convexify`
+    takes them -> (K_list, Pi_list, rho): p gains K_k (nu x nx, u = -K_k x), p cost-to-go matrices, the closed-loop spectral radius.
+    RuntimeError when the recursion did not converge (status of periodic_lqr_batch != 0)."""
+    As, Bs, Hs = _stack_stages(A, B, Q, R, N)
+    r = periodic_lqr_batch(As, Bs, Hs, tol=tol, max_sweeps=max_sweeps)
+    st = int(r['status'][0])
+    if st != 0:
+        raise RuntimeError('periodic_lqr: Riccati recursion ended with status {} ({}) after {} sweeps'.format(st, STATUS_NAMES.get(st), int(r['sweeps'][0])))
+    p = As.shape[1]
+    return [r['K'][0, k].copy() for k in range(p)], [r['Pi'][0, k].copy() for k in range(p)], float(r['rho'][0])
+
+
+def feedback_equivalence_batch(A, B, H, Hc, P=None, tol=1e-13, max_sweeps=5000):
+    """The certificate: gains of the LQ problems on H and on Hc (two recursions), compared.  A, B, H as in periodic_lqr_batch, Hc [nb,p,n,n]
+    (the `Hc` of convexify_batch, or H + dHc), numpy or torch GPU tensors.  Returns dict: dK [nb] = max_k max|K_k(H) - K_k(Hc)|,
+    dK_rel = dK / max(1, max|K(Hc)|), rho_H, rho_Hc (numpy), status_H, status_Hc, sweeps_H, sweeps_Hc, posdef_H (info[6] of the H side: 1.0 if S was positive definite on its whole path), K, Kc.
+
+    P [nb,p,nx,nx] (optional): the `P` of the convexification.  With the supplement map of the library (tmpc_supplement_batch_host, reference convexifier.py:191-194),
+    Hc_k = H_k + [A_k B_k]' P_{k+1} [A_k B_k] - diag(P_k, 0), so the H-recursion started at Pi0 = +P is the Hc-recursion started at zero
+    shifted by P, iterate by iterate (Pi_k(H) = Pi_k(Hc) + P_k): the H side then solves the positive definite S of the Hc side instead of
+    the indefinite one it meets on the way from zero.  (The sweep counts agree unless convergence is slow: the stop measure divides by
+    max(1, max|Pi_k|), which the shift changes -- c1 stops at sweep 211 from P and at 214 on the Hc side.)
+
+    What it says: for the plain model (Step 1 without rows) dK at rounding level and both rho < 1 certify that dHc has the calH(P) structure
+    and that both schemes stabilise.  It does NOT say that kappa is minimal (the SDP may be solved badly and still pass).  After Step 3
+    (`force`) dHc contains the regularisation T_k, the gains differ on purpose and dK MEASURES what T_k changed.  With rows of G / C the
+    equivalence holds only on the null space of the active rows: not covered here."""
+    use_torch, nb, p, nx, mb = _validate(A, B, H, (('Hc', Hc, 'H'), ('P', P, 'A')))
+    rH = periodic_lqr_batch(A, B, H, Pi0=P, tol=tol, max_sweeps=max_sweeps)
+    rC = periodic_lqr_batch(A, B, Hc, tol=tol, max_sweeps=max_sweeps)
+    d = (rH['K'] - rC['K']).abs() if use_torch else np.abs(rH['K'] - rC['K'])
+    kc = rC['K'].abs() if use_torch else np.abs(rC['K'])
+    if use_torch:
+        dK = d.reshape(nb, -1).max(dim=1).values.cpu().numpy(); kmax = kc.reshape(nb, -1).max(dim=1).values.cpu().numpy()
+        posdef = rH['info'][:, 6].cpu().numpy()
+    else:
+        dK = d.reshape(nb, -1).max(axis=1); kmax = kc.reshape(nb, -1).max(axis=1)
+        posdef = rH['info'][:, 6].copy()
+    return dict(dK=dK, dK_rel=dK / np.maximum(1.0, kmax), rho_H=rH['rho'], rho_Hc=rC['rho'], status_H=rH['status'], status_Hc=rC['status'],
+                sweeps_H=rH['sweeps'], sweeps_Hc=rC['sweeps'], posdef_H=posdef, K=rH['K'], Kc=rC['K'])
+
+
+def feedback_equivalence(A, B, Q, R, N, dHc, tol=1e-13, max_sweeps=5000):
+    """feedback_equivalence_batch for one problem in the calling style of `convexify`: dHc is its first return value (list of p supplements,
+    Hc_k = H_k + dHc_k).  Returns the dict of the batched call with scalars for dK, dK_rel, rho_H, rho_Hc, status_H, status_Hc and lists of
+    p gains for K, Kc."""
+    As, Bs, Hs = _stack_stages(A, B, Q, R, N)
+    dH = np.stack([_to_array(d) for d in (dHc if isinstance(dHc, (list, tuple)) else [dHc])])[None]      # (convexify returns a list also at p = 1)
+    if dH.shape != Hs.shape:
+        raise ValueError('feedback_equivalence: dHc must hold p matrices (nx+nu, nx+nu), got {}'.format(dH.shape[1:]))
+    r = feedback_equivalence_batch(As, Bs, Hs, Hs + dH, tol=tol, max_sweeps=max_sweeps)
+    p = As.shape[1]
+    out = {k: (float(v[0]) if k.startswith(('dK', 'rho', 'posdef')) else int(v[0])) for k, v in r.items() if k not in ('K', 'Kc')}
+    out['K'] = [r['K'][0, k].copy() for k in range(p)]; out['Kc'] = [r['Kc'][0, k].copy() for k in range(p)]
+    return out
