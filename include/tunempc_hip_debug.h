@@ -40,6 +40,31 @@ int tmpc_debug_gemm_nt(tmpc_handle* h, double* C, const double* A, const double*
  * D [p][d][d] diagonal blocks, Ccpl [p][d][d] with Ccpl[k] = T[block k, block k+1 mod p], rhs/x [p][d]. */
 int tmpc_debug_block_solve(tmpc_handle* h, int p, int d, const double* D, const double* Ccpl, const double* rhs, double* x, int32_t* nshift);
 
+/* The block factorisation and its substitutions AS THE SOLVER DRIVES THEM (cr_factor / cr_solve, dd_factor / dd_solve), with the factor read back:
+ * nb distinct systems in one workspace, an ordered problem list (any subset of 0..nb-1, uploaded as the compacted list of the kernels), a per-problem
+ * precision, the pass, the forward sweep fused into the factorisation or not.  Unit tests of the float32 and double-double kernels (tests/test_gpu_factor_kernels.py).
+ * The no-MFMA flag and TMPC_DEBUG_FLAG_NO_DMA of the handle are honoured (the latter at every block size, unlike tmpc_debug_block_solve).
+ * A combination the solver itself never runs (float32 without the LDS-DMA kernels or outside 64 < dp <= 320, a fused sweep at p = 1 or on the small-block kernel,
+ * float32 or a fused sweep in double-double) is TMPC_E_ARG, never a quiet change of path. */
+#define TMPC_DEBUG_FACTOR_PASS1 1       /* pass 1: three right-hand sides per problem, interleaved as in W3 [p][dp][3]; else pass 2: one, in Z [p][dp] */
+#define TMPC_DEBUG_FACTOR_FUSE_FWD1 2   /* pass 1 only: the forward sweep rides inside the factorisation (cr_factor fuse_fwd1, cr_solve skip_fwd) */
+#define TMPC_DEBUG_FACTOR_LOWP_TRSM 4   /* DF_LOWP_TRSM for this call: the problems with lowp[b] != 0 also solve in float32 (k_cr_trsm_dma_f32) */
+#define TMPC_DEBUG_FACTOR_DD 8          /* dd_factor + dd_solve on hi (+ lo) words; right-hand sides are fp64 numbers (dd_solve clears their low words) */
+typedef struct {
+  /* in: D, Ccpl [nb][p][d][d] (Ccpl[b][k] = T_b[block k, block k+1 mod p]), rhs [nb][p][d][nc] with nc = 3 (pass 1) or 1; Dlo / Clo: low words (double-double
+   * only; NULL = zero); list [count]; lowp [nb]: 1 = this problem's updates in float32 (I_LOWP; NULL = none) */
+  const double *D, *Ccpl, *Dlo, *Clo, *rhs;
+  const int32_t *list, *lowp;
+  /* out, every problem of the batch whether listed or not, the padded device images as they are (any pointer may be NULL): D (-> L), O (edge slots), F (fill
+   * slots) [nb][p][dp][dp]; O32 [nb][2p][dp][ld32] (calls with a float32 problem only); Ddiag [nb][p][dp]; X [nb][p][dp][nc]; the low words of D, O, F, X
+   * (double-double only); nshift [nb]; dims [4] = dp, ld32, nc, 1 if O32 exists; orient [p]: 0 = edge slot k holds T[k+1,k], 1 = T[k,k+1] */
+  double *oD, *oO, *oF, *oDdiag, *oX;
+  float* oO32;
+  double *oDl, *oOl, *oFl, *oXl;
+  int32_t *nshift, *dims, *orient;
+} tmpc_debug_factor_io;
+int tmpc_debug_block_factor(tmpc_handle* h, int nb, int p, int d, int count, int mode, const tmpc_debug_factor_io* io);
+
 /* The elimination schedule for period p (host only, no device needed): out = [nlev, prep, nelim, nupd, nlev x (eoff, nelim,
  * uoff, nupd), nelim x 8 ints (node, na, nb, ea, eb, fill, fx, facc), nupd x 8 ints (node, e0, src0, e1, src1, 0, 0, 0),
  * p x orientation].  Returns the number of ints; call with out = NULL to size the buffer. */

@@ -29,8 +29,17 @@ EXPORTS = [
 # ... and in include/tunempc_hip_debug.h (unit-test / diagnostic entries)
 DEBUG_EXPORTS = [
     'tmpc_debug_gemm_nt', 'tmpc_debug_block_solve', 'tmpc_debug_cr_schedule', 'tmpc_debug_get_multipliers', 'tmpc_debug_get_array',
-    'tmpc_debug_min_eig', 'tmpc_debug_min_eig_lane', 'tmpc_debug_factor_bench',
+    'tmpc_debug_min_eig', 'tmpc_debug_min_eig_lane', 'tmpc_debug_factor_bench', 'tmpc_debug_block_factor',
 ]
+FLAG_DEBUG_NO_DMA = 32      # tunempc_hip_debug.h: TMPC_DEBUG_FLAG_NO_DMA
+# mode bits of tmpc_debug_block_factor (tunempc_hip_debug.h)
+FACTOR_PASS1, FACTOR_FUSE_FWD1, FACTOR_LOWP_TRSM, FACTOR_DD = 1, 2, 4, 8
+
+
+class _FactorIO(C.Structure):
+    _fields_ = ([(n, C.POINTER(C.c_double)) for n in ('D', 'Ccpl', 'Dlo', 'Clo', 'rhs')] + [(n, C.POINTER(C.c_int32)) for n in ('list', 'lowp')] +
+                [(n, C.POINTER(C.c_double)) for n in ('oD', 'oO', 'oF', 'oDdiag', 'oX')] + [('oO32', C.POINTER(C.c_float))] +
+                [(n, C.POINTER(C.c_double)) for n in ('oDl', 'oOl', 'oFl', 'oXl')] + [(n, C.POINTER(C.c_int32)) for n in ('nshift', 'dims', 'orient')])
 
 
 def library_path():
@@ -137,6 +146,8 @@ def load_library():
     lib.tmpc_tracking_reference_host.argtypes = [vp, C.c_int, dp, dp, dp, C.c_double, dp, dp, ip]
     lib.tmpc_debug_cr_schedule.restype = C.c_int
     lib.tmpc_debug_cr_schedule.argtypes = [C.c_int, ip, C.c_int]
+    lib.tmpc_debug_block_factor.restype = C.c_int
+    lib.tmpc_debug_block_factor.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_FactorIO)]
     lib.tmpc_debug_factor_bench.restype = C.c_int
     lib.tmpc_debug_factor_bench.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, dp]
     lib.tmpc_debug_min_eig.restype = C.c_int
@@ -549,6 +560,47 @@ class HipConvexifier:
         x = np.empty((p, d)); ns = np.zeros(1, np.int32)
         _check(self.lib, self.lib.tmpc_debug_block_solve(self._h, p, d, _dptr(D), _dptr(Ccpl), _dptr(rhs), _dptr(x), _iptr(ns)), 'tmpc_debug_block_solve')
         return x, int(ns[0])
+
+    def debug_block_factor(self, D, Ccpl, rhs, plist=None, lowp=None, pass1=False, fuse_fwd1=False, lowp_trsm=False, dd=False, Dlo=None, Clo=None):
+        """tmpc_debug_block_factor: the block factorisation and its substitutions as the solver drives them, on nb distinct systems
+        D, Ccpl [nb, p, d, d], rhs [nb, p, d] (pass 2) or [nb, p, d, 3] (pass1=True), for the problems of `plist` (ordered subset of range(nb); default all),
+        lowp [nb]: 1 = float32 updates for that problem, lowp_trsm: their solves in float32 too; dd: in double-double (Dlo / Clo: low words).
+        Returns, for EVERY problem of the batch: L [nb, p, d, d] (lower triangle of D after the call), D, O, F (un-padded block arrays; O, F in the slot
+        orientation `orient`), O32 [nb, 2p, d, d] or None, Ddiag, x, the low words Dl / Ol / Fl / xl (dd), nshift [nb], and under 'raw' the padded device
+        images with dp, ld32."""
+        f64 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)
+        D, Ccpl, rhs, Dlo, Clo = f64(D), f64(Ccpl), f64(rhs), f64(Dlo), f64(Clo)
+        nb, p, d, _ = D.shape
+        nc = 3 if pass1 else 1
+        if Ccpl.shape != D.shape or rhs.shape != ((nb, p, d, 3) if pass1 else (nb, p, d)):
+            raise ValueError('debug_block_factor: D, Ccpl [nb, p, d, d] and rhs [nb, p, d] (pass 2) / [nb, p, d, 3] (pass 1) expected')
+        plist = np.ascontiguousarray(np.arange(nb) if plist is None else plist, dtype=np.int32)
+        lowp = None if lowp is None else np.ascontiguousarray(lowp, dtype=np.int32)
+        if lowp is not None and lowp.shape != (nb,):
+            raise ValueError('debug_block_factor: lowp [nb] expected')
+        mode = (FACTOR_PASS1 if pass1 else 0) | (FACTOR_FUSE_FWD1 if fuse_fwd1 else 0) | (FACTOR_LOWP_TRSM if lowp_trsm else 0) | (FACTOR_DD if dd else 0)
+        dp = (d + 15) // 16 * 16; ld32 = (dp + 31) // 32 * 32
+        has32 = bool(lowp_trsm or (lowp is not None and lowp.any()))
+        raw = dict(D=np.empty((nb, p, dp, dp)), O=np.empty((nb, p, dp, dp)), F=np.empty((nb, p, dp, dp)), Ddiag=np.empty((nb, p, dp)), X=np.empty((nb, p, dp, nc)),
+                   O32=np.empty((nb, 2 * p, dp, ld32), np.float32) if has32 else None)
+        if dd:
+            raw.update(Dl=np.empty((nb, p, dp, dp)), Ol=np.empty((nb, p, dp, dp)), Fl=np.empty((nb, p, dp, dp)), Xl=np.empty((nb, p, dp, nc)))
+        nshift = np.zeros(nb, np.int32); dims = np.zeros(4, np.int32); orient = np.zeros(p, np.int32)
+        io = _FactorIO(D=_dptr(D), Ccpl=_dptr(Ccpl), Dlo=_dptr(Dlo), Clo=_dptr(Clo), rhs=_dptr(rhs), list=_iptr(plist), lowp=_iptr(lowp),
+                       oD=_dptr(raw['D']), oO=_dptr(raw['O']), oF=_dptr(raw['F']), oDdiag=_dptr(raw['Ddiag']), oX=_dptr(raw['X']),
+                       oO32=raw['O32'].ctypes.data_as(C.POINTER(C.c_float)) if has32 else None,
+                       oDl=_dptr(raw.get('Dl')), oOl=_dptr(raw.get('Ol')), oFl=_dptr(raw.get('Fl')), oXl=_dptr(raw.get('Xl')),
+                       nshift=_iptr(nshift), dims=_iptr(dims), orient=_iptr(orient))
+        _check(self.lib, self.lib.tmpc_debug_block_factor(self._h, nb, p, d, len(plist), mode, C.byref(io)), 'tmpc_debug_block_factor')
+        assert (int(dims[0]), int(dims[1]), int(dims[2]), bool(dims[3])) == (dp, ld32, nc, has32), dims
+        raw.update(dp=dp, ld32=ld32)
+        cut = lambda a: None if a is None else a[:, :, :d, :d].copy()
+        vec = lambda a: None if a is None else (a[:, :, :d, :].copy() if pass1 else a[:, :, :d, 0].copy())
+        out = dict(raw=raw, orient=orient, nshift=nshift, D=cut(raw['D']), L=np.tril(cut(raw['D'])), O=cut(raw['O']), F=cut(raw['F']), O32=cut(raw['O32']),
+                   Ddiag=raw['Ddiag'][:, :, :d].copy(), x=vec(raw['X']))
+        if dd:
+            out.update(Dl=cut(raw['Dl']), Ll=np.tril(cut(raw['Dl'])), Ol=cut(raw['Ol']), Fl=cut(raw['Fl']), xl=vec(raw['Xl']))
+        return out
 
 
 def eig_clip(A, tol):

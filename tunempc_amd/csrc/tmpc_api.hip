@@ -1965,6 +1965,116 @@ int tmpc_debug_block_solve(tmpc_handle* h, int p, int d, const double* D, const 
   return TMPC_OK;
 }
 
+// The factorisation and its substitutions as run_chunk drives them, on nb distinct systems, with the factor read back (tunempc_hip_debug.h): the problem list,
+// the per-problem I_LOWP, DF_LOWP_TRSM, nlowp, fuse_fwd1 / skip_fwd and the pass reach cr_factor / cr_solve (dd_factor / dd_solve) exactly as they do from there.
+int tmpc_debug_block_factor(tmpc_handle* h, int nb, int p, int d, int count, int mode, const tmpc_debug_factor_io* io) {
+  if (!h || !io || nb < 1 || p < 1 || d < 1 || count < 0 || count > nb || !io->D || !io->Ccpl || !io->rhs || (count > 0 && !io->list)) return TMPC_E_ARG;
+  if (mode & ~(TMPC_DEBUG_FACTOR_PASS1 | TMPC_DEBUG_FACTOR_FUSE_FWD1 | TMPC_DEBUG_FACTOR_LOWP_TRSM | TMPC_DEBUG_FACTOR_DD)) return TMPC_E_ARG;
+  const bool pass1 = (mode & TMPC_DEBUG_FACTOR_PASS1) != 0, fuse = (mode & TMPC_DEBUG_FACTOR_FUSE_FWD1) != 0, ddm = (mode & TMPC_DEBUG_FACTOR_DD) != 0;
+  std::vector<char> seen(nb, 0);
+  int nlowp = 0, anylowp = 0;
+  for (int i = 0; i < count; ++i) {
+    const int b = io->list[i];
+    if (b < 0 || b >= nb || seen[b]) { snprintf(g_err, sizeof(g_err), "tmpc_debug_block_factor: list entry %d is out of range or repeated", i); return TMPC_E_ARG; }
+    seen[b] = 1;
+    if (io->lowp && io->lowp[b]) ++nlowp;           // (run_chunk: cnt[4], the members of the list that k_ctrl_d / k_init_prob marked)
+  }
+  for (int b = 0; b < nb && io->lowp; ++b) anylowp |= io->lowp[b] != 0;
+  ON_DEVICE(h);
+  CrBench cb;
+  int rc = cb.init(nb, p, d, h->flags, false);
+  if (rc != TMPC_OK) return rc;
+  Dims& dm = cb.dm; WS& w = cb.w;
+  if (h->flags & TMPC_DEBUG_FLAG_NO_DMA) dm.flags |= DF_NO_DMA;
+  if (!h->tune_small) dm.flags |= DF_NO_SMALL;
+  const int dp = dm.dp, ld32 = (dp + 31) & ~31, nc = pass1 ? 3 : 1;
+  const size_t bs = (size_t)dp * dp, per = (size_t)p * bs, vl = (size_t)p * dp;
+  if (solve_lds(dm) > 160 * 1024) return TMPC_E_UNSUPPORTED;
+  // the conditions under which run_chunk takes each path: anything else is refused
+  const bool lowp_ok = !(dm.flags & (1 | DF_NO_DMA)) && dp > 64 && dm.nt <= TRR_NT;
+  const bool fuse_ok = pass1 && !(dm.flags & (1 | DF_NO_DMA)) && p > 1 && dm.nt <= TRR_NT && !cr_small_levels(dm, cb.sc, nullptr);
+  if ((anylowp || (mode & TMPC_DEBUG_FACTOR_LOWP_TRSM)) && (!lowp_ok || ddm)) { snprintf(g_err, sizeof(g_err), "tmpc_debug_block_factor: no float32 path at dp = %d with these flags", dp); return TMPC_E_ARG; }
+  if (fuse && (!fuse_ok || ddm)) { snprintf(g_err, sizeof(g_err), "tmpc_debug_block_factor: no fused forward sweep at p = %d, dp = %d with these flags", p, dp); return TMPC_E_ARG; }
+  DevBuf O32b, Dlb, Olb, Flb, Lilb, W3lb, Zlb;
+  const size_t n32 = 2 * (size_t)nb * p * dp * ld32;
+  if (anylowp || (mode & TMPC_DEBUG_FACTOR_LOWP_TRSM)) {
+    if (O32b.alloc(n32 * sizeof(float)) != hipSuccess) return TMPC_E_NOMEM;
+    HIPCHK(hipMemset(O32b.p, 0, n32 * sizeof(float)));            // (the workspace of a handle: zero when created, the padding stays so)
+    w.O32 = O32b.as<float>();
+    dm.flags |= DF_LOWP | ((mode & TMPC_DEBUG_FACTOR_LOWP_TRSM) ? DF_LOWP_TRSM : 0);
+  }
+  if (ddm) {
+    if (Dlb.alloc(nb * per * 8) != hipSuccess || Olb.alloc(nb * per * 8) != hipSuccess || Flb.alloc(nb * per * 8) != hipSuccess ||
+        Lilb.alloc((size_t)nb * p * dm.nt * TB * TB * 8) != hipSuccess || W3lb.alloc((size_t)nb * vl * 3 * 8) != hipSuccess || Zlb.alloc((size_t)nb * vl * 8) != hipSuccess)
+      return TMPC_E_NOMEM;
+    w.Dl = Dlb.as<double>(); w.Ol = Olb.as<double>(); w.Fl = Flb.as<double>(); w.Linvl = Lilb.as<double>(); w.W3l = W3lb.as<double>(); w.Zl = Zlb.as<double>();
+    HIPCHK(hipMemset(w.Fl, 0, nb * per * 8)); HIPCHK(hipMemset(w.Linvl, 0, (size_t)nb * p * dm.nt * TB * TB * 8));
+    HIPCHK(hipMemset(w.W3l, 0, (size_t)nb * vl * 3 * 8)); HIPCHK(hipMemset(w.Zl, 0, (size_t)nb * vl * 8));
+  }
+  HIPCHK(hipMemset(w.F, 0, nb * per * 8)); HIPCHK(hipMemset(w.Linv, 0, (size_t)nb * p * dm.nt * TB * TB * 8));
+  HIPCHK(hipMemset(w.Z, 0, (size_t)nb * vl * 8)); HIPCHK(hipMemset(w.W3, 0, (size_t)nb * vl * 3 * 8));
+  double* X = pass1 ? w.W3 : w.Z; double* Xl = pass1 ? w.W3l : w.Zl;
+  {
+    std::vector<double> hD, hO, hdd, hz(vl * nc), hDl, hOl, hdl;
+    const size_t dd_ = (size_t)p * d * d;
+    const std::vector<double> zero(ddm && (!io->Dlo || !io->Clo) ? dd_ : 0, 0.0);
+    for (int b = 0; b < nb; ++b) {
+      cr_pack(cb.sc, p, d, dp, io->D + b * dd_, io->Ccpl + b * dd_, hD, hO, hdd);
+      std::fill(hz.begin(), hz.end(), 0.0);
+      for (int k = 0; k < p; ++k) for (int i = 0; i < d; ++i) for (int q = 0; q < nc; ++q) hz[((size_t)k * dp + i) * nc + q] = io->rhs[(((size_t)b * p + k) * d + i) * nc + q];
+      HIPCHK(hipMemcpy(w.D + b * per, hD.data(), per * 8, hipMemcpyHostToDevice));
+      HIPCHK(hipMemcpy(w.O + b * per, hO.data(), per * 8, hipMemcpyHostToDevice));
+      HIPCHK(hipMemcpy(w.Ddiag + b * vl, hdd.data(), vl * 8, hipMemcpyHostToDevice));
+      HIPCHK(hipMemcpy(X + b * vl * nc, hz.data(), vl * nc * 8, hipMemcpyHostToDevice));
+      if (ddm) {
+        cr_pack(cb.sc, p, d, dp, io->Dlo ? io->Dlo + b * dd_ : zero.data(), io->Clo ? io->Clo + b * dd_ : zero.data(), hDl, hOl, hdl);
+        for (int k = 0; k < p; ++k) for (int i = d; i < dp; ++i) hDl[k * bs + (size_t)i * dp + i] = 0.0;      // (the identity padding has no low word)
+        HIPCHK(hipMemcpy(w.Dl + b * per, hDl.data(), per * 8, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(w.Ol + b * per, hOl.data(), per * 8, hipMemcpyHostToDevice));
+      }
+    }
+  }
+  if (count > 0) HIPCHK(hipMemcpy(w.alist, io->list, (size_t)count * sizeof(int), hipMemcpyHostToDevice));
+  if (anylowp) {
+    std::vector<int> hi((size_t)nb * IS, 0);
+    for (int b = 0; b < nb; ++b) hi[(size_t)b * IS + I_LOWP] = io->lowp[b] ? 1 : 0;
+    HIPCHK(hipMemcpy(w.iprob, hi.data(), hi.size() * sizeof(int), hipMemcpyHostToDevice));
+  }
+  if (count > 0) {
+    const int pass = pass1 ? 1 : 2;
+    if (ddm) {
+      dd_factor(w, dm, cb.sc, cb.d_sched, w.alist, count, 0);
+      rc = dd_solve(w, dm, cb.sc, cb.d_sched, w.alist, count, 0, pass, nb);
+      if (rc != TMPC_OK) return rc;
+    } else {
+      cr_factor(w, dm, cb.sc, cb.d_sched, w.alist, count, 0, h->rs, h->mt, nullptr, nullptr, fuse ? 1 : 0, nlowp);
+      cr_solve(w, dm, cb.sc, cb.d_sched, w.alist, count, 0, pass, fuse);
+    }
+  }
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipGetLastError());
+  if (io->oD) HIPCHK(hipMemcpy(io->oD, w.D, nb * per * 8, hipMemcpyDeviceToHost));
+  if (io->oO) HIPCHK(hipMemcpy(io->oO, w.O, nb * per * 8, hipMemcpyDeviceToHost));
+  if (io->oF) HIPCHK(hipMemcpy(io->oF, w.F, nb * per * 8, hipMemcpyDeviceToHost));
+  if (io->oDdiag) HIPCHK(hipMemcpy(io->oDdiag, w.Ddiag, nb * vl * 8, hipMemcpyDeviceToHost));
+  if (io->oX) HIPCHK(hipMemcpy(io->oX, X, nb * vl * nc * 8, hipMemcpyDeviceToHost));
+  if (io->oO32 && w.O32) HIPCHK(hipMemcpy(io->oO32, w.O32, n32 * sizeof(float), hipMemcpyDeviceToHost));
+  if (ddm) {
+    if (io->oDl) HIPCHK(hipMemcpy(io->oDl, w.Dl, nb * per * 8, hipMemcpyDeviceToHost));
+    if (io->oOl) HIPCHK(hipMemcpy(io->oOl, w.Ol, nb * per * 8, hipMemcpyDeviceToHost));
+    if (io->oFl) HIPCHK(hipMemcpy(io->oFl, w.Fl, nb * per * 8, hipMemcpyDeviceToHost));
+    if (io->oXl) HIPCHK(hipMemcpy(io->oXl, Xl, nb * vl * nc * 8, hipMemcpyDeviceToHost));
+  }
+  if (io->nshift) {
+    std::vector<int> hi((size_t)nb * IS);
+    HIPCHK(hipMemcpy(hi.data(), w.iprob, hi.size() * sizeof(int), hipMemcpyDeviceToHost));
+    for (int b = 0; b < nb; ++b) io->nshift[b] = hi[(size_t)b * IS + I_NSHIFT];
+  }
+  if (io->dims) { io->dims[0] = dp; io->dims[1] = ld32; io->dims[2] = nc; io->dims[3] = w.O32 ? 1 : 0; }
+  if (io->orient) for (int k = 0; k < p; ++k) io->orient[k] = cb.sc.orient[k];
+  return TMPC_OK;
+}
+
 // Isolated timing of the block factorisation and of one single-right-hand-side solve: nb copies of one random SPD
 // block-cyclic-tridiagonal system (restored before every repetition).  ms_out2[0] = factorisation, [1] = solve, averages over `reps`.
 int tmpc_debug_factor_bench(tmpc_handle* h, int nb, int p, int d, int reps, double* ms_out2) {
