@@ -293,6 +293,29 @@ int tmpc_periodic_lqr_batch_host(int nb, int p, int nx, int mb, const double* A,
 int tmpc_periodic_lqr_batch_device(int nb, int p, int nx, int mb, const double* A, const double* B, const double* H, const double* Pi0, double tol,
                                    int max_sweeps, double* K, double* Pi, double* Phi, double* info);
 
+/* The same recursion for the models with rows: stage k holds J_k [x_k; u_k] = 0 with J_k = [G_k; C_k[:ncnt_k]] = [Jx | Ju] (first nx | last mb columns),
+ * r_k = ng + ncnt_k rows -- the J / ncnt layout of tmpc_convexify_step2_batch_host.  Per stage
+ *     [ S   Ju' ] [ K_k   ]   [ M  ]
+ *     [ Ju  0   ] [ Lam_k ] = [ Jx ]       u = -K_k x,   Pi_k = sym(Hb_xx - [M; Jx]' [K_k; Lam_k]),   Jx - Ju K_k = 0.
+ * Hc_k = H_k + calH_k(P) + J_k' diag(phi_k) J_k and the last term vanishes on J_k w = 0: the constrained problems on H (from Pi0 = +P) and on Hc (from zero)
+ * have the same K_k and Pi_k(H) = Pi_k(Hc) + P_k iterate by iterate, which the unconstrained ones lose as soon as a multiplier phi is non-zero.
+ * Arguments of the plain entries plus: nr row capacity per stage (>= ng), ng rows present at every stage, J [nb][p][nr][n] (rows beyond r_k are not read),
+ * ncnt int32 [nb][p] (NULL: ng rows at every stage), Lam [nb][p][nr][nx] (optional; the multiplier gains, zero beyond r_k).
+ * Served: r_k <= mb with Ju of full row rank.  info as above, with
+ *   [0] status 4: r_k > mb (or r_k > nr, ncnt_k < 0) at some stage, decided before the first sweep ([1] = 0; K, Lam zero, Pi = Pi0, Phi NaN);
+ *       status 2 also covers a rank-deficient Ju (in particular rows on the state alone: they need a constraint-to-go recursion, not provided),
+ *   [3] / [4] pivots of the whole KKT matrix, [5] / [6] 1.0 if every elimination took mb positive and then r_k negative diagonal pivots (S positive
+ *       definite and Ju of full row rank: a convex stage problem), [7] max_k max|Jx - Ju K_k| of the returned gains (0 when status >= 2).
+ * With r_k = 0 at every stage the outputs are those of the plain entry, bit for bit.  TMPC_E_ARG: nr < ng, (host entry) ncnt outside 0 .. nr - ng;
+ * TMPC_E_UNSUPPORTED (before the device is touched): nx + mb > TMPC_LQR_NMAX, or (nx, mb, nr) beyond 160 KB of LDS -- n <= 32 fits with any nr <= 66,
+ * 32 < n <= 64 with any nr <= 15 and with more where the split of n leaves room (nx = mb = nr = 32 fits). */
+int tmpc_periodic_lqr_rows_batch_host(int nb, int p, int nx, int mb, int nr, int ng, const double* A, const double* B, const double* H, const double* J,
+                                      const int32_t* ncnt, const double* Pi0, double tol, int max_sweeps, double* K, double* Pi, double* Phi, double* Lam,
+                                      double* info);
+int tmpc_periodic_lqr_rows_batch_device(int nb, int p, int nx, int mb, int nr, int ng, const double* A, const double* B, const double* H, const double* J,
+                                        const int32_t* ncnt, const double* Pi0, double tol, int max_sweeps, double* K, double* Pi, double* Phi, double* Lam,
+                                        double* info);
+
 /* Accumulated hipEvent timings since the last call (ms) when TMPC_FLAG_PROFILE is set, 16 doubles:
  * out[0] stage_pre+ctrl, [1] schur assembly, [2] block factorisation (all kernels of tmpc_cr.h's factor phase), [3] predictor
  * pass, [4] corrector pass + update, [5] number of factorisation phases (= IPM iterations of the chunks), [6] total ms of the

@@ -5,8 +5,10 @@
 Inputs live in HBM; HIP events around (a) the C entry alone (`entry_ms`: launch + synchronise), (b) periodic_lqr_batch (`call_ms`: plus the spectral radii
 on the host) and (c) feedback_equivalence_batch (`certificate_ms`: two recursions and the comparison).  Warm-up, then the median of --reps calls.
 Compared with: the numpy statement of the recursion on this host (tests/lqr_reference.py, one pass) and the convexify step of the same batch (BENCH_r06.json).
+The rows leg (csrc/tmpc_lqr_rows.h) times, in the same run on the same inputs (the Hc of the bench batch), the plain entry, the rows entry with 2 + 0..3 random
+rows per stage and the rows entry with room for 5 rows that no stage uses, and the certificate with rows -> profiles/lqr_rows_timing.json.
 
-    python scripts/lqr_timing.py [--reps 15] [--batch 512] [--out profiles/lqr_timing.json]
+    python scripts/lqr_timing.py [--reps 15] [--batch 512] [--out profiles/lqr_timing.json] [--rows-out profiles/lqr_rows_timing.json] [--rows-only]
 """
 import argparse
 import json
@@ -58,11 +60,38 @@ def measure(tag, A, B, H, Hc, P, reps, numpy_members):
     return res
 
 
+def measure_rows(A, B, H, Hc, P, reps):
+    """Plain entry, rows entry (2 + 0..3 rows) and rows entry with zero rows on the Hc side of one batch, interleaved in one run; the certificate with rows."""
+    import lqr_rows_reference as lrr
+    nb, p, nx, _ = A.shape
+    n = H.shape[2]
+    J, ncnt = lrr.gen_rows(100001, nb, p, n, 2, 3)
+    dA, dB, dH, dHc, dP, dJ, dn = (torch.from_numpy(np.ascontiguousarray(x)).cuda() for x in (A, B, H, Hc, P, J, ncnt))
+    zero = torch.zeros_like(dn)
+    plain = lambda: _lib.periodic_lqr_batch_device(dA, dB, dHc, None, 1e-13, 5000)
+    rows = lambda: _lib.periodic_lqr_rows_batch_device(dA, dB, dHc, dJ, dn, 2, None, 1e-13, 5000)
+    norows = lambda: _lib.periodic_lqr_rows_batch_device(dA, dB, dHc, dJ, zero, 0, None, 1e-13, 5000)
+    o_plain, o_rows, o_zero = plain(), rows(), norows()
+    res = dict(shape=dict(nb=int(nb), p=int(p), nx=int(nx), nu=int(n - nx), ng=2, nc=3, mean_rows_per_stage=float(2 + ncnt.mean())),
+               sweeps=dict(plain=[int(o_plain[3][:, 1].min()), int(o_plain[3][:, 1].max())], rows=[int(o_rows[4][:, 1].min()), int(o_rows[4][:, 1].max())]),
+               converged=dict(plain=int((o_plain[3][:, 0] == 0).sum()), rows=int((o_rows[4][:, 0] == 0).sum())),
+               zero_rows_bit_equal_to_plain=bool(all(torch.equal(a, b) for a, b in zip(o_plain[:3], o_zero[:3])) and torch.equal(o_plain[3], o_zero[4])),
+               feas_max=float(o_rows[4][:, 7].max()))
+    for rnd in range(2):                                     # two interleaved rounds: drift of the box shows as a difference between them
+        res['round%d' % rnd] = dict(plain_entry_ms=median_ms(plain, reps), rows_entry_zero_rows_ms=median_ms(norows, reps), rows_entry_ms=median_ms(rows, reps))
+    res['certificate_with_rows_ms'] = median_ms(lambda: lqr.feedback_equivalence_batch(dA, dB, dH, dHc, P=dP, J=dJ, ncnt=dn, ng=2), reps)
+    res['certificate_plain_ms'] = median_ms(lambda: lqr.feedback_equivalence_batch(dA, dB, dH, dHc, P=dP), reps)
+    print('rows leg', json.dumps(res))
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reps', type=int, default=15)
     ap.add_argument('--batch', type=int, default=512)
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'lqr_timing.json'))
+    ap.add_argument('--rows-out', default=os.path.join(ROOT, 'profiles', 'lqr_rows_timing.json'))
+    ap.add_argument('--rows-only', action='store_true', help='only the rows leg (it times the plain entry itself)')
     ap.add_argument('--kernel-only', action='store_true', help='one pass over the three inputs without timing (for a kernel trace)')
     args = ap.parse_args()
     assert args.reps >= 10 or args.kernel_only
@@ -72,6 +101,17 @@ def main():
     if not args.kernel_only:
         t = time.perf_counter(); conv = convexifier.convexify_batch(A, B, H); tconv = (time.perf_counter() - t) * 1e3
     cases['bench batch %d x (p 64, nx 24, nu 8)' % args.batch] = (A, B, H, conv['Hc'], conv['P'], 32)
+    if not args.kernel_only:
+        step_ms = json.load(open(os.path.join(ROOT, 'BENCH_r06.json')))['parsed']['ms_per_step']
+        rows = dict(device=torch.cuda.get_device_name(0), reps=args.reps, convexify_step_ms_BENCH_r06=step_ms, optimal_members=int((conv['status'] == 0).sum()),
+                    bench=measure_rows(A, B, H, conv['Hc'], conv['P'], args.reps))
+        rows['certificate_with_rows_share_of_convexify_step'] = rows['bench']['certificate_with_rows_ms']['median'] / step_ms
+        os.makedirs(os.path.dirname(os.path.abspath(args.rows_out)), exist_ok=True)
+        with open(args.rows_out, 'w') as f:
+            json.dump(rows, f, indent=1)
+        print('wrote', args.rows_out)
+        if args.rows_only:
+            return
     g = lr.load_golden('c1_convex_lqr')
     cases['c1 batch 1 (p 1, nx 3, nu 1)'] = (g['A'], g['B'], g['H'], g['Hc'], g['P'], 1)
     g = lr.load_golden('c3_evaporation_shape')

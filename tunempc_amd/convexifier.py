@@ -278,6 +278,26 @@ def _log_solution(res):
     return status
 
 
+def pack_rows(arg, period, n):
+    """The rows of a checked argument dict (preprocessing.input_checks) in the layout of the batched calls -> (Gs, Cp, rows): Gs [p,ng,n] (None without
+    'G' or with empty G_k), Cp [p,nc,n] the C_k zero-padded to nc = max(1, max rows) and rows [p] the rows present per stage, 0 where C_k is None
+    (both None without 'C').  Shared by `convexify` and by the calls of tunempc_amd.lqr that take G, C."""
+    Gs = None
+    if 'G' in arg:
+        Gs = np.stack([_to_array(g) for g in arg['G']])
+        if Gs.shape[1] == 0:
+            Gs = None
+    Cp = rows = None
+    if 'C' in arg:
+        Cl = [None if c is None else _to_array(c) for c in arg['C']]
+        rows = [0 if c is None else c.shape[0] for c in Cl]
+        Cp = np.zeros((period, max(1, max(rows)), n))
+        for k, c in enumerate(Cl):
+            if rows[k]:
+                Cp[k, :rows[k]] = c
+    return Gs, Cp, rows
+
+
 def convexify(A, B, Q, R, N, G=None, C=None, opts={'rho': 1e-3, 'solver': 'hip', 'force': False}):
     """ Convexify the indefinite Hessian "H" of the system with the discrete time dynamics
 
@@ -330,17 +350,8 @@ def convexify(A, B, Q, R, N, G=None, C=None, opts={'rho': 1e-3, 'solver': 'hip',
         raise ValueError("unknown objective '{}' ('paper': beta + rho * norm terms, 'beta': beta alone)".format(objective))
     rho2 = 0.0 if objective == 'beta' else (opts or {}).get('rho', 1e-3)      # Step 2: rho = 0 is the beta-only model
 
-    Gs = None
-    if 'G' in arg:        # the multipliers Fg_k >= 0 belong to every step, Step 1 included (convexifier.py:249-255)
-        Gs = np.stack([_to_array(g) for g in arg['G']])
-        if Gs.shape[1] == 0:
-            Gs = None
-    Cl = rows = None
-    nc = 0
-    if 'C' in arg:
-        Cl = [None if c is None else _to_array(c) for c in arg['C']]
-        rows = [0 if c is None else c.shape[0] for c in Cl]
-        nc = max(1, max(rows))
+    Gs, Cp, rows = pack_rows(arg, period, nx + nu)        # the multipliers Fg_k >= 0 belong to every step, Step 1 included (convexifier.py:249-255)
+    nc = 0 if Cp is None else Cp.shape[1]
 
     if Gs is not None and Gs.shape[1] > NG_MAX:
         raise NotImplementedError('the HIP path handles up to {} equality-constraint rows per stage (got {})'.format(NG_MAX, Gs.shape[1]))
@@ -371,10 +382,6 @@ def convexify(A, B, Q, R, N, G=None, C=None, opts={'rho': 1e-3, 'solver': 'hip',
     if status == 'Infeasible' and 'C' in arg:        # convexifier.py:116-131
         Logger.logger.info(50 * '*')
         Logger.logger.info('Step 2: (η_F = 1), (η_T = 0)')
-        Cp = np.zeros((period, nc, nx + nu))
-        for k, c in enumerate(Cl):
-            if rows[k]:
-                Cp[k, :rows[k]] = c
         Logger.logger.info('solving SDP...')
         res = convexify_step2_batch(As[None], Bs[None], Hs[None], Cp[None], np.asarray(rows, np.int32)[None],
                                     rho2, G=None if Gs is None else Gs[None], tight=(opts or {}).get('tight'))
@@ -399,10 +406,6 @@ def convexify(A, B, Q, R, N, G=None, C=None, opts={'rho': 1e-3, 'solver': 'hip',
             Logger.logger.info('Enforcing convexification...')
             Logger.logger.info('solving SDP...')
             if 'C' in arg:                                                    # convexifier.py:144: constr = constraint_contribution
-                Cp = np.zeros((period, nc, nx + nu))
-                for k, c in enumerate(Cl):
-                    if rows[k]:
-                        Cp[k, :rows[k]] = c
                 res = convexify_step3_batch(As[None], Bs[None], Hs[None], (opts or {}).get('rho', 1e-3), G=None if Gs is None else Gs[None],
                                             C=Cp[None], ncnt=np.asarray(rows, np.int32)[None])
             else:

@@ -10,6 +10,10 @@ that sentence on any batch:
     feedback_equivalence_batch(A, B, H, Hc, P=None)                       max |K(H) - K(Hc)| per problem, both closed-loop spectral radii
     feedback_equivalence(A, B, Q, R, N, dHc)                              the same on what `convexify` takes and returns
 
+For the models with rows (Step 1 with G, Steps 2 / 3 with C) the equivalence holds for the LQ problems that keep J_k [x_k; u_k] = 0, J_k = [G_k; C_k]:
+every call takes the rows (J=, ncnt=, ng= in the layout of convexify_step2_batch's library call; G=, C= as `convexify` takes them) and then runs the
+recursion with the rows held as equalities (csrc/tmpc_lqr_rows.h).  Without them the calls are the plain ones, bit for bit.
+
 Conventions: stage cost 1/2 [x;u]' H_k [x;u] with H_k = [[Q_k, N_k], [N_k', R_k]] (x block first, the layout of convexify_batch),
 x_{k+1} = A_k x_k + B_k u_k, and u = -K_k x: the sign of scipy.linalg.solve_discrete_are / control.dare.
 There is no CPU path: the recursion runs in the HIP library or the call raises.
@@ -18,9 +22,9 @@ import numpy as np
 
 from . import _lib
 from . import preprocessing
-from .convexifier import _to_array
+from .convexifier import _to_array, pack_rows
 
-STATUS_NAMES = {0: 'Converged', 1: 'MaxSweeps', 2: 'SingularS', 3: 'NonFinite'}
+STATUS_NAMES = {0: 'Converged', 1: 'MaxSweeps', 2: 'SingularS', 3: 'NonFinite', 4: 'RowsExceedInputs'}
 
 
 def _is_torch(x):
@@ -61,6 +65,41 @@ def _validate(A, B, H, extra=()):
     return use_torch, nb, p, nx, mb
 
 
+def _validate_rows(J, ncnt, ng, use_torch, ref, nb, p, n):
+    """Shapes, dtypes and ranges of the rows, before any device call -> (nr, ng).  J [nb,p,nr,n] fp64; ncnt [nb,p] int32 or None (ng rows at every
+    stage); ng None: nr without ncnt, 0 with it.  ng > nr is left to the library (its message)."""
+    if ng is not None and (isinstance(ng, bool) or not isinstance(ng, (int, np.integer))):
+        raise ValueError('periodic_lqr_batch: ng must be an int, got {!r}'.format(ng))
+    for nm, x in (('J', J), ('ncnt', ncnt)):
+        if x is None:
+            continue
+        if not hasattr(x, 'shape') or not hasattr(x, 'dtype') or _is_torch(x) != use_torch:
+            raise ValueError('periodic_lqr_batch: {} must be {} like A, B, H'.format(nm, 'a torch tensor' if use_torch else 'a numpy array'))
+        if use_torch and (not x.is_cuda or x.device != ref.device):
+            raise ValueError('periodic_lqr_batch: torch tensors must be tensors of one GPU ({}: {})'.format(nm, x.device))
+    import_torch = None
+    if use_torch:
+        import torch as import_torch
+    if J.dtype != (import_torch.float64 if use_torch else np.float64):
+        raise ValueError('periodic_lqr_batch: fp64 arrays expected (J has dtype {})'.format(J.dtype))
+    if len(J.shape) != 4 or (int(J.shape[0]), int(J.shape[1]), int(J.shape[3])) != (nb, p, n):
+        raise ValueError('periodic_lqr_batch: J [nb, p, nr, nx + nu] = [{}, {}, nr, {}] expected, got {}'.format(nb, p, n, tuple(J.shape)))
+    nr = int(J.shape[2])
+    if ng is None:
+        ng = nr if ncnt is None else 0
+    ng = int(ng)
+    if ng < 0:
+        raise ValueError('periodic_lqr_batch: ng >= 0 expected, got {}'.format(ng))
+    if ncnt is not None:
+        if ncnt.dtype != (import_torch.int32 if use_torch else np.int32):
+            raise ValueError('periodic_lqr_batch: ncnt must be int32 (got dtype {})'.format(ncnt.dtype))
+        if tuple(ncnt.shape) != (nb, p):
+            raise ValueError('periodic_lqr_batch: ncnt [nb, p] = {} expected, got {}'.format((nb, p), tuple(ncnt.shape)))
+        if ng <= nr and (bool((ncnt < 0).any()) or bool((ncnt > nr - ng).any())):
+            raise ValueError('periodic_lqr_batch: 0 <= ncnt <= J.shape[2] - ng = {} expected'.format(nr - ng))
+    return nr, ng
+
+
 def _contig(x, use_torch):
     if x is None:
         return None
@@ -77,7 +116,7 @@ def _rho(Phi):
     return out
 
 
-def periodic_lqr_batch(A, B, H, Pi0=None, tol=1e-13, max_sweeps=5000):
+def periodic_lqr_batch(A, B, H, Pi0=None, tol=1e-13, max_sweeps=5000, J=None, ncnt=None, ng=None):
     """Gains of nb p-periodic LQ problems.  A [nb,p,nx,nx], B [nb,p,nx,nu], H [nb,p,n,n] (n = nx + nu <= 64), fp64; per stage, indices mod p,
 
         E = [A_k B_k],  Hb = H_k + E' Pi_{k+1} E,  S = Hb_uu,  M = Hb_ux,  K_k = S^-1 M  (u = -K_k x),  Pi_k = sym(Hb_xx - M' K_k),
@@ -89,10 +128,37 @@ def periodic_lqr_batch(A, B, H, Pi0=None, tol=1e-13, max_sweeps=5000):
     Returns dict: K [nb,p,nu,nx], Pi [nb,p,nx,nx], Phi [nb,nx,nx] (closed-loop monodromy (A-BK)_{p-1} ... (A-BK)_0), rho [nb] (numpy: its
     spectral radius, nan where Phi is not finite), status [nb] (0 converged, 1 max_sweeps reached, 2 singular S, 3 non-finite iterate),
     sweeps [nb], info [nb,8] (status, sweeps, last relative change, smallest / largest |pivot| of S in the last sweep, 1.0 if S was shown
-    positive definite at every stage of the last sweep, the same over every sweep of the call, reserved).  ValueError: shapes / dtypes; NotImplementedError: n > 64."""
+    positive definite at every stage of the last sweep, the same over every sweep of the call, reserved).  ValueError: shapes / dtypes; NotImplementedError: n > 64.
+
+    With rows -- J [nb,p,nr,n] fp64, ncnt [nb,p] int32 (None: ng rows at every stage), ng (None: nr without ncnt, 0 with it); stage k holds
+    J_k [x_k; u_k] = 0 for its first r_k = ng + ncnt_k rows J_k = [Jx | Ju], the layout of the Step 2 / Step 3 library calls -- the stage solve is
+
+        [[S, Ju'], [Ju, 0]] [K_k; Lam_k] = [M; Jx],   Pi_k = sym(Hb_xx - [M; Jx]' [K_k; Lam_k]),   so that Jx - Ju K_k = 0,
+
+    and the dict gains Lam [nb,p,nr,nx] (zero beyond r_k) and feas [nb] = info[:, 7] = max_k max|Jx - Ju K_k|; info[:, 5:7] then read 1.0 when every
+    stage problem was shown convex (S positive definite and Ju of full row rank).  Served: r_k <= nu with Ju of full row rank.  status 4
+    (RowsExceedInputs): r_k > nu at some stage -- sweeps 0, K and Lam zero, Pi = Pi0, Phi NaN; status 2 also covers a rank-deficient Ju.  Rows that
+    constrain the state alone (Ju = 0) would need a constraint-to-go recursion: not provided, they end with status 2.  NotImplementedError also for
+    (nx, nu, nr) beyond the 160 KB of LDS (n <= 32: never for nr <= 66; 32 < n <= 64: never for nr <= 15).  With J=None the plain entry is called."""
     use_torch, nb, p, nx, mb = _validate(A, B, H, (('Pi0', Pi0, 'A'),))
     if not (float(tol) >= 0.0) or int(max_sweeps) < 1:
         raise ValueError('periodic_lqr_batch: tol >= 0 and max_sweeps >= 1 expected, got {}, {}'.format(tol, max_sweeps))
+    if J is None and (ncnt is not None or ng is not None):
+        raise ValueError('periodic_lqr_batch: ncnt / ng describe the rows of J, which is None')
+    if J is not None:
+        nr, ng = _validate_rows(J, ncnt, ng, use_torch, A, nb, p, nx + mb)
+        A, B, H, Pi0, J, ncnt = (_contig(x, use_torch) if x is not ncnt else (x if x is None else (x.contiguous() if use_torch else np.ascontiguousarray(x)))
+                                 for x in (A, B, H, Pi0, J, ncnt))
+        if use_torch:
+            import torch
+            K, Pi, Phi, Lam, info = _lib.periodic_lqr_rows_batch_device(A, B, H, J, ncnt, ng, Pi0, tol, max_sweeps)
+            rho = _rho(Phi.cpu().numpy())
+            status = info[:, 0].to(torch.int32); sweeps = info[:, 1].to(torch.int32); feas = info[:, 7].clone()
+        else:
+            K, Pi, Phi, Lam, info = _lib.periodic_lqr_rows_batch_host(A, B, H, J, ncnt, ng, Pi0, tol, max_sweeps)
+            rho = _rho(Phi)
+            status = info[:, 0].astype(np.int32); sweeps = info[:, 1].astype(np.int32); feas = info[:, 7].copy()
+        return dict(K=K, Pi=Pi, Phi=Phi, rho=rho, status=status, sweeps=sweeps, info=info, Lam=Lam, feas=feas)
     A, B, H, Pi0 = (_contig(x, use_torch) for x in (A, B, H, Pi0))
     if use_torch:
         K, Pi, Phi, info = _lib.periodic_lqr_batch_device(A, B, H, Pi0, tol, max_sweeps)       # (either entry refuses n > 64 before it touches the device)
@@ -106,9 +172,15 @@ def periodic_lqr_batch(A, B, H, Pi0=None, tol=1e-13, max_sweeps=5000):
     return dict(K=K, Pi=Pi, Phi=Phi, rho=rho, status=status, sweeps=sweeps, info=info)
 
 
-def _stack_stages(A, B, Q, R, N):
-    """The reference's calling style (single matrices or lists of length p, np.matrix / CasADi DM accepted) -> A, B, H [1,p,...]."""
-    arg = preprocessing.input_checks({'A': A, 'B': B, 'Q': Q, 'R': R, 'N': N})
+def _stack_stages(A, B, Q, R, N, G=None, C=None):
+    """The reference's calling style (single matrices or lists of length p, np.matrix / CasADi DM accepted) -> A, B, H [1,p,...] and the rows of
+    G, C (as `convexify` takes them: per-stage None allowed in C) as keyword arguments J=, ncnt=, ng= of the batched calls ({} without rows)."""
+    arg = {'A': A, 'B': B, 'Q': Q, 'R': R, 'N': N}
+    if G is not None:
+        arg['G'] = G
+    if C is not None:
+        arg['C'] = C
+    arg = preprocessing.input_checks(arg)
     As = np.stack([_to_array(a) for a in arg['A']]); Bs = np.stack([_to_array(b) for b in arg['B']])
     period, nx, _ = As.shape
     nu = Bs.shape[2]
@@ -118,15 +190,25 @@ def _stack_stages(A, B, Q, R, N):
         if Qk.shape != (nx, nx) or Rk.shape != (nu, nu) or Nk.shape != (nx, nu) or Bs[k].shape != (nx, nu):
             raise ValueError('periodic_lqr: A (nx,nx), B (nx,nu), Q (nx,nx), R (nu,nu), N (nx,nu) expected at stage {}'.format(k))
         Hs[k, :nx, :nx] = Qk; Hs[k, nx:, nx:] = Rk; Hs[k, :nx, nx:] = Nk; Hs[k, nx:, :nx] = Nk.T
-    return As[None], Bs[None], Hs[None]
+    Gs, Cp, cnt = pack_rows(arg, period, nx + nu)        # (the packing of `convexify`)
+    for nm, x in (('G', Gs), ('C', Cp)):
+        if x is not None and x.shape[2] != nx + nu:
+            raise ValueError('periodic_lqr: rows of {} must have nx + nu = {} columns, got {}'.format(nm, nx + nu, x.shape[2]))
+    rows = {}
+    if Cp is not None:
+        rows = dict(J=(Cp if Gs is None else np.concatenate([Gs, Cp], axis=1))[None], ncnt=np.asarray(cnt, np.int32)[None], ng=0 if Gs is None else Gs.shape[1])
+    elif Gs is not None:
+        rows = dict(J=Gs[None], ng=Gs.shape[1])
+    return As[None], Bs[None], Hs[None], rows
 
 
-def periodic_lqr(A, B, Q, R, N, tol=1e-13, max_sweeps=5000):
+def periodic_lqr(A, B, Q, R, N, tol=1e-13, max_sweeps=5000, G=None, C=None):
     """The gains of one problem in the reference's calling style: A, B, Q, R, N single matrices (p = 1) or lists of length p, as `convexify`
     takes them -> (K_list, Pi_list, rho): p gains K_k (nu x nx, u = -K_k x), p cost-to-go matrices, the closed-loop spectral radius.
+    G, C (as `convexify` takes them): the rows held as equalities, see periodic_lqr_batch.
     RuntimeError when the recursion did not converge (status of periodic_lqr_batch != 0)."""
-    As, Bs, Hs = _stack_stages(A, B, Q, R, N)
-    r = periodic_lqr_batch(As, Bs, Hs, tol=tol, max_sweeps=max_sweeps)
+    As, Bs, Hs, rows = _stack_stages(A, B, Q, R, N, G, C)
+    r = periodic_lqr_batch(As, Bs, Hs, tol=tol, max_sweeps=max_sweeps, **rows)
     st = int(r['status'][0])
     if st != 0:
         raise RuntimeError('periodic_lqr: Riccati recursion ended with status {} ({}) after {} sweeps'.format(st, STATUS_NAMES.get(st), int(r['sweeps'][0])))
@@ -134,7 +216,7 @@ def periodic_lqr(A, B, Q, R, N, tol=1e-13, max_sweeps=5000):
     return [r['K'][0, k].copy() for k in range(p)], [r['Pi'][0, k].copy() for k in range(p)], float(r['rho'][0])
 
 
-def feedback_equivalence_batch(A, B, H, Hc, P=None, tol=1e-13, max_sweeps=5000):
+def feedback_equivalence_batch(A, B, H, Hc, P=None, tol=1e-13, max_sweeps=5000, J=None, ncnt=None, ng=None):
     """The certificate: gains of the LQ problems on H and on Hc (two recursions), compared.  A, B, H as in periodic_lqr_batch, Hc [nb,p,n,n]
     (the `Hc` of convexify_batch, or H + dHc), numpy or torch GPU tensors.  Returns dict: dK [nb] = max_k max|K_k(H) - K_k(Hc)|,
     dK_rel = dK / max(1, max|K(Hc)|), rho_H, rho_Hc (numpy), status_H, status_Hc, sweeps_H, sweeps_Hc, posdef_H (info[6] of the H side: 1.0 if S was positive definite on its whole path), K, Kc.
@@ -147,11 +229,16 @@ def feedback_equivalence_batch(A, B, H, Hc, P=None, tol=1e-13, max_sweeps=5000):
 
     What it says: for the plain model (Step 1 without rows) dK at rounding level and both rho < 1 certify that dHc has the calH(P) structure
     and that both schemes stabilise.  It does NOT say that kappa is minimal (the SDP may be solved badly and still pass).  After Step 3
-    (`force`) dHc contains the regularisation T_k, the gains differ on purpose and dK MEASURES what T_k changed.  With rows of G / C the
-    equivalence holds only on the null space of the active rows: not covered here."""
+    (`force`) dHc contains the regularisation T_k, the gains differ on purpose and dK MEASURES what T_k changed.  The models with rows (Step 1 with
+    G, Step 2) are covered when the rows of the solve are passed as J / ncnt / ng (see periodic_lqr_batch): both recursions then hold
+    J_k [x_k; u_k] = 0, the term J_k' diag(phi_k) J_k of Hc drops out and dK is at rounding level again (without J the unconstrained gains of H and
+    Hc differ by design once a multiplier is non-zero -- a wrong alarm); the dict gains feas_H, feas_Hc (max|Jx - Ju K_k|), convex_Hc (info[6] of the
+    Hc side: every stage problem shown convex) and Lam, Lamc.  After Step 3 with rows dK measures T_k as it does without rows.  Not covered: rows
+    that constrain the state alone (Ju without full row rank: status 2) and stages with more rows than inputs (status 4)."""
     use_torch, nb, p, nx, mb = _validate(A, B, H, (('Hc', Hc, 'H'), ('P', P, 'A')))
-    rH = periodic_lqr_batch(A, B, H, Pi0=P, tol=tol, max_sweeps=max_sweeps)
-    rC = periodic_lqr_batch(A, B, Hc, tol=tol, max_sweeps=max_sweeps)
+    rows = {} if J is None and ncnt is None and ng is None else dict(J=J, ncnt=ncnt, ng=ng)
+    rH = periodic_lqr_batch(A, B, H, Pi0=P, tol=tol, max_sweeps=max_sweeps, **rows)
+    rC = periodic_lqr_batch(A, B, Hc, tol=tol, max_sweeps=max_sweeps, **rows)
     d = (rH['K'] - rC['K']).abs() if use_torch else np.abs(rH['K'] - rC['K'])
     kc = rC['K'].abs() if use_torch else np.abs(rC['K'])
     if use_torch:
@@ -160,20 +247,24 @@ def feedback_equivalence_batch(A, B, H, Hc, P=None, tol=1e-13, max_sweeps=5000):
     else:
         dK = d.reshape(nb, -1).max(axis=1); kmax = kc.reshape(nb, -1).max(axis=1)
         posdef = rH['info'][:, 6].copy()
-    return dict(dK=dK, dK_rel=dK / np.maximum(1.0, kmax), rho_H=rH['rho'], rho_Hc=rC['rho'], status_H=rH['status'], status_Hc=rC['status'],
-                sweeps_H=rH['sweeps'], sweeps_Hc=rC['sweeps'], posdef_H=posdef, K=rH['K'], Kc=rC['K'])
+    out = dict(dK=dK, dK_rel=dK / np.maximum(1.0, kmax), rho_H=rH['rho'], rho_Hc=rC['rho'], status_H=rH['status'], status_Hc=rC['status'],
+               sweeps_H=rH['sweeps'], sweeps_Hc=rC['sweeps'], posdef_H=posdef, K=rH['K'], Kc=rC['K'])
+    if rows:
+        host = (lambda x: x.cpu().numpy()) if use_torch else (lambda x: x.copy())
+        out.update(feas_H=host(rH['feas']), feas_Hc=host(rC['feas']), convex_Hc=host(rC['info'][:, 6]), Lam=rH['Lam'], Lamc=rC['Lam'])
+    return out
 
 
-def feedback_equivalence(A, B, Q, R, N, dHc, tol=1e-13, max_sweeps=5000):
+def feedback_equivalence(A, B, Q, R, N, dHc, tol=1e-13, max_sweeps=5000, G=None, C=None):
     """feedback_equivalence_batch for one problem in the calling style of `convexify`: dHc is its first return value (list of p supplements,
     Hc_k = H_k + dHc_k).  Returns the dict of the batched call with scalars for dK, dK_rel, rho_H, rho_Hc, status_H, status_Hc and lists of
-    p gains for K, Kc."""
-    As, Bs, Hs = _stack_stages(A, B, Q, R, N)
+    p gains for K, Kc.  G, C: the rows `convexify` was called with (then also feas_H, feas_Hc, convex_Hc as scalars)."""
+    As, Bs, Hs, rows = _stack_stages(A, B, Q, R, N, G, C)
     dH = np.stack([_to_array(d) for d in (dHc if isinstance(dHc, (list, tuple)) else [dHc])])[None]      # (convexify returns a list also at p = 1)
     if dH.shape != Hs.shape:
         raise ValueError('feedback_equivalence: dHc must hold p matrices (nx+nu, nx+nu), got {}'.format(dH.shape[1:]))
-    r = feedback_equivalence_batch(As, Bs, Hs, Hs + dH, tol=tol, max_sweeps=max_sweeps)
+    r = feedback_equivalence_batch(As, Bs, Hs, Hs + dH, tol=tol, max_sweeps=max_sweeps, **rows)
     p = As.shape[1]
-    out = {k: (float(v[0]) if k.startswith(('dK', 'rho', 'posdef')) else int(v[0])) for k, v in r.items() if k not in ('K', 'Kc')}
+    out = {k: (float(v[0]) if k.startswith(('dK', 'rho', 'posdef', 'feas', 'convex')) else int(v[0])) for k, v in r.items() if k not in ('K', 'Kc', 'Lam', 'Lamc')}
     out['K'] = [r['K'][0, k].copy() for k in range(p)]; out['Kc'] = [r['Kc'][0, k].copy() for k in range(p)]
     return out
