@@ -316,6 +316,31 @@ int tmpc_periodic_lqr_rows_batch_device(int nb, int p, int nx, int mb, int nr, i
                                         const int32_t* ncnt, const double* Pi0, double tol, int max_sweeps, double* K, double* Pi, double* Phi, double* Lam,
                                         double* info);
 
+/* The recursion with rows for ANY rows: more rows than inputs (r_k > mb), rows on the state alone, dependent rows (tmpc_lqr_ctg.h).  What the rows of stage k
+ * and of the stages after it say about x_k alone is carried backwards as a constraint-to-go Hn_k x_k = 0 (c_k orthonormal rows, empty at the start):
+ *     Cf = [J_k; Hn_{k+1} [A_k B_k]] is split by elimination with full pivoting on its u columns -- a pivot is accepted while the largest remaining |entry|
+ *     exceeds rank_tol * max(1, max|Cf|) -- into rho <= mb rows [Jx~ | Ju~] of full row rank and rows with a zero u part, whose x parts are compressed
+ *     (Gram-Schmidt with row pivoting, same threshold) to Hn_k;  [[S, Ju~'], [Ju~, 0]] [K; Lam] = [M; Jx~] as in the rows entry (rho = mb allowed);
+ *     Pz = I - Hn_k' Hn_k,  K_k = K Pz,  Pi_k = sym(Pz (Hb_xx - [M; Jx~]' [K; Lam]) Pz)    (unique; off the feasible subspace u = -K_k x says nothing).
+ * Sweeps stop when the change measure of the plain entry is <= tol and no c_k changed during the sweep.
+ * Arguments of the rows entries plus rank_tol (> 0; 1e-9 is the library's default in Python); no Lam (the multipliers are not unique).  Outputs:
+ * K, Pi as before; Phi (optional) = (A-BK)_{p-1} ... (A-BK)_0 Pz_0; Hn [nb][p][nx][nx], rows beyond c_k zero; cnt int32 [nb][p] = c_k; info [nb][12]:
+ *   [0] status 0 .. 3 as above (2: singular reduced Hessian of a stage), 5 no feasible subspace (c_k reached nx: only x_k = 0 satisfies the rows; the problem
+ *       stops there, Phi NaN); status 4 is never returned, ncnt is clamped to 0 .. nr - ng;
+ *   [1] .. [6] as in the rows entry (the rows enter the elimination scaled to the largest diagonal entry of S, so they compete with its diagonal for the pivot
+ *       and [5] / [6] read 0, "not shown", more often than in the rows entry), [7] max_k max(|(Jx - Ju K_k) Pz_k|, |Hn_{k+1} (A_k - B_k K_k) Pz_k|) of the returned gains (0 when status >= 2),
+ *   [8] sum_k c_k and [9] max_k c_k of the last sweep, [10] smallest accepted and [11] largest rejected pivot of all splits and compressions of the call,
+ *       relative to the stage scale max(1, max|Cf|) ([10] = inf, [11] = 0 when there was none): a decision is safe when [11] << rank_tol << [10].
+ * TMPC_E_ARG: nr < ng, rank_tol <= 0, NULL Hn / cnt, (host entry) ncnt outside 0 .. nr - ng.  TMPC_E_UNSUPPORTED (before the device is touched):
+ * nx + mb > TMPC_LQR_NMAX, or (nx, mb, nr) beyond 160 KB of LDS -- the layout holds the stack twice, [max(nr + nx, mb)][n], and Hn twice. */
+#define TMPC_LQR_CTG_INFO 12
+int tmpc_periodic_lqr_ctg_batch_host(int nb, int p, int nx, int mb, int nr, int ng, const double* A, const double* B, const double* H, const double* J,
+                                     const int32_t* ncnt, const double* Pi0, double tol, double rank_tol, int max_sweeps, double* K, double* Pi, double* Phi,
+                                     double* Hn, int32_t* cnt, double* info);
+int tmpc_periodic_lqr_ctg_batch_device(int nb, int p, int nx, int mb, int nr, int ng, const double* A, const double* B, const double* H, const double* J,
+                                       const int32_t* ncnt, const double* Pi0, double tol, double rank_tol, int max_sweeps, double* K, double* Pi, double* Phi,
+                                       double* Hn, int32_t* cnt, double* info);
+
 /* Accumulated hipEvent timings since the last call (ms) when TMPC_FLAG_PROFILE is set, 16 doubles:
  * out[0] stage_pre+ctrl, [1] schur assembly, [2] block factorisation (all kernels of tmpc_cr.h's factor phase), [3] predictor
  * pass, [4] corrector pass + update, [5] number of factorisation phases (= IPM iterations of the chunks), [6] total ms of the

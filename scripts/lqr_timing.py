@@ -7,8 +7,11 @@ on the host) and (c) feedback_equivalence_batch (`certificate_ms`: two recursion
 Compared with: the numpy statement of the recursion on this host (tests/lqr_reference.py, one pass) and the convexify step of the same batch (BENCH_r06.json).
 The rows leg (csrc/tmpc_lqr_rows.h) times, in the same run on the same inputs (the Hc of the bench batch), the plain entry, the rows entry with 2 + 0..3 random
 rows per stage and the rows entry with room for 5 rows that no stage uses, and the certificate with rows -> profiles/lqr_rows_timing.json.
+The ctg leg (--ctg; csrc/tmpc_lqr_ctg.h) times, on the Hc side of the same batch with 5 random rows at every stage, the rows entry and the constraint-to-go
+entry next to each other (the rows fit the inputs, so both serve them), and the two certificates -> profiles/lqr_ctg_timing.json; nothing else is run.
 
     python scripts/lqr_timing.py [--reps 15] [--batch 512] [--out profiles/lqr_timing.json] [--rows-out profiles/lqr_rows_timing.json] [--rows-only]
+    python scripts/lqr_timing.py --ctg [--reps 15] [--batch 512] [--ctg-out profiles/lqr_ctg_timing.json]
 """
 import argparse
 import json
@@ -85,6 +88,34 @@ def measure_rows(A, B, H, Hc, P, reps):
     return res
 
 
+def measure_ctg(A, B, H, Hc, P, reps):
+    """Rows entry and constraint-to-go entry on the Hc side of one batch with 5 rows at every stage, interleaved in one run; the two certificates."""
+    nb, p, nx, _ = A.shape
+    n = H.shape[2]
+    J = np.random.default_rng(100002).standard_normal((nb, p, 5, n))
+    dA, dB, dH, dHc, dP, dJ = (torch.from_numpy(np.ascontiguousarray(x)).cuda() for x in (A, B, H, Hc, P, J))
+    # random rows are not the rows Hc was convexified with: a member whose change per sweep stalls above the tolerance would run every timed call to
+    # max_sweeps, so the leg stops at 1e-10 and bounds the sweeps; the counts are printed before anything is timed
+    tol, max_sweeps = 1e-10, 200
+    rows = lambda: _lib.periodic_lqr_rows_batch_device(dA, dB, dHc, dJ, None, 5, None, tol, max_sweeps)
+    ctg = lambda: _lib.periodic_lqr_ctg_batch_device(dA, dB, dHc, dJ, None, 5, None, tol, 1e-9, max_sweeps)
+    o_rows, o_ctg = rows(), ctg()
+    print('ctg leg: sweeps rows', int(o_rows[4][:, 1].min()), int(o_rows[4][:, 1].max()), 'ctg', int(o_ctg[5][:, 1].min()), int(o_ctg[5][:, 1].max()), flush=True)
+    ok = (o_rows[4][:, 0] == 0) & (o_ctg[5][:, 0] == 0)
+    kmax = o_rows[0].abs().reshape(nb, -1).max(dim=1).values.clamp(min=1.0)
+    res = dict(shape=dict(nb=int(nb), p=int(p), nx=int(nx), nu=int(n - nx), rows_per_stage=5), tol=tol, max_sweeps=max_sweeps,
+               sweeps=dict(rows=[int(o_rows[4][:, 1].min()), int(o_rows[4][:, 1].max())], ctg=[int(o_ctg[5][:, 1].min()), int(o_ctg[5][:, 1].max())]),
+               converged=dict(rows=int((o_rows[4][:, 0] == 0).sum()), ctg=int((o_ctg[5][:, 0] == 0).sum())),
+               K_rel_diff_max=float((((o_rows[0] - o_ctg[0]).abs().reshape(nb, -1).max(dim=1).values / kmax)[ok]).max()) if bool(ok.any()) else None,
+               ctg_counts_sum=int(o_ctg[4].sum()), feas_max=dict(rows=float(o_rows[4][:, 7].max()), ctg=float(o_ctg[5][:, 7].max())))
+    for rnd in range(2):                                     # two interleaved rounds: drift of the box shows as a difference between them
+        res['round%d' % rnd] = dict(rows_entry_ms=median_ms(rows, reps), ctg_entry_ms=median_ms(ctg, reps))
+    res['certificate_with_rows_ms'] = median_ms(lambda: lqr.feedback_equivalence_batch(dA, dB, dH, dHc, P=dP, J=dJ, ng=5, tol=tol, max_sweeps=max_sweeps), reps)
+    res['certificate_state_rows_ms'] = median_ms(lambda: lqr.feedback_equivalence_batch(dA, dB, dH, dHc, P=dP, J=dJ, ng=5, tol=tol, max_sweeps=max_sweeps, state_rows=True), reps)
+    print('ctg leg', json.dumps(res))
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reps', type=int, default=15)
@@ -92,6 +123,8 @@ def main():
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'lqr_timing.json'))
     ap.add_argument('--rows-out', default=os.path.join(ROOT, 'profiles', 'lqr_rows_timing.json'))
     ap.add_argument('--rows-only', action='store_true', help='only the rows leg (it times the plain entry itself)')
+    ap.add_argument('--ctg', action='store_true', help='only the constraint-to-go leg: rows entry against ctg entry with 5 rows per stage')
+    ap.add_argument('--ctg-out', default=os.path.join(ROOT, 'profiles', 'lqr_ctg_timing.json'))
     ap.add_argument('--kernel-only', action='store_true', help='one pass over the three inputs without timing (for a kernel trace)')
     args = ap.parse_args()
     assert args.reps >= 10 or args.kernel_only
@@ -101,6 +134,15 @@ def main():
     if not args.kernel_only:
         t = time.perf_counter(); conv = convexifier.convexify_batch(A, B, H); tconv = (time.perf_counter() - t) * 1e3
     cases['bench batch %d x (p 64, nx 24, nu 8)' % args.batch] = (A, B, H, conv['Hc'], conv['P'], 32)
+    if args.ctg:
+        assert not args.kernel_only
+        out = dict(device=torch.cuda.get_device_name(0), reps=args.reps, optimal_members=int((conv['status'] == 0).sum()),
+                   bench=measure_ctg(A, B, H, conv['Hc'], conv['P'], args.reps))
+        os.makedirs(os.path.dirname(os.path.abspath(args.ctg_out)), exist_ok=True)
+        with open(args.ctg_out, 'w') as f:
+            json.dump(out, f, indent=1)
+        print('wrote', args.ctg_out)
+        return
     if not args.kernel_only:
         step_ms = json.load(open(os.path.join(ROOT, 'BENCH_r06.json')))['parsed']['ms_per_step']
         rows = dict(device=torch.cuda.get_device_name(0), reps=args.reps, convexify_step_ms_BENCH_r06=step_ms, optimal_members=int((conv['status'] == 0).sum()),

@@ -24,6 +24,7 @@ EXPORTS = [
     'tmpc_convexify_con_batch_device', 'tmpc_workspace_bytes_step3', 'tmpc_create_step3', 'tmpc_convexify_step3_batch_host', 'tmpc_workspace_bytes_step3_con', 'tmpc_create_step3_con', 'tmpc_convexify_step3_con_batch_host', 'tmpc_convexify_step3_batch_device', 'tmpc_convexify_step3_con_batch_device', 'tmpc_supplement_batch_host', 'tmpc_supplement_terms_batch_host',
     'tmpc_tracking_reference_host', 'tmpc_eig_scan_host', 'tmpc_get_profile', 'tmpc_get_trace', 'tmpc_get_dual_host', 'tmpc_get_dual_con_host', 'tmpc_pack_sensitivities_host', 'tmpc_eig_clip_host',
     'tmpc_periodic_lqr_batch_host', 'tmpc_periodic_lqr_batch_device', 'tmpc_periodic_lqr_rows_batch_host', 'tmpc_periodic_lqr_rows_batch_device',
+    'tmpc_periodic_lqr_ctg_batch_host', 'tmpc_periodic_lqr_ctg_batch_device',
     'tmpc_last_error', 'tmpc_version',
 ]
 # ... and in include/tunempc_hip_debug.h (unit-test / diagnostic entries)
@@ -132,6 +133,10 @@ def load_library():
     lib.tmpc_periodic_lqr_rows_batch_host.argtypes = [C.c_int] * 6 + [dp] * 4 + [ip, dp, C.c_double, C.c_int] + [dp] * 5
     lib.tmpc_periodic_lqr_rows_batch_device.restype = C.c_int
     lib.tmpc_periodic_lqr_rows_batch_device.argtypes = [C.c_int] * 6 + [vp] * 6 + [C.c_double, C.c_int] + [vp] * 5
+    lib.tmpc_periodic_lqr_ctg_batch_host.restype = C.c_int
+    lib.tmpc_periodic_lqr_ctg_batch_host.argtypes = [C.c_int] * 6 + [dp] * 4 + [ip, dp, C.c_double, C.c_double, C.c_int] + [dp] * 4 + [ip, dp]
+    lib.tmpc_periodic_lqr_ctg_batch_device.restype = C.c_int
+    lib.tmpc_periodic_lqr_ctg_batch_device.argtypes = [C.c_int] * 6 + [vp] * 6 + [C.c_double, C.c_double, C.c_int] + [vp] * 6
     lib.tmpc_get_profile.restype = C.c_int
     lib.tmpc_get_profile.argtypes = [vp, dp]
     lib.tmpc_get_trace.restype = C.c_int
@@ -179,6 +184,7 @@ class EigNotConverged(RuntimeError):
 E_NOCONV = -6
 E_UNSUPPORTED = -2
 LQR_INFO_STRIDE = 8
+LQR_CTG_INFO_STRIDE = 12
 
 
 def _check(lib, rc, what):
@@ -698,6 +704,43 @@ def periodic_lqr_rows_batch_device(A, B, H, J, ncnt, ng, Pi0, tol, max_sweeps):
         raise ValueError(lib.tmpc_last_error().decode())
     _check_lqr(lib, rc, 'tmpc_periodic_lqr_rows_batch_device')
     return K, Pi, Phi, Lam, info
+
+
+def periodic_lqr_ctg_batch_host(A, B, H, J, ncnt, ng, Pi0, tol, rank_tol, max_sweeps):
+    """tmpc_periodic_lqr_ctg_batch_host on validated, contiguous numpy arrays (fp64; ncnt int32 or None) -> (K, Pi, Phi, Hn, cnt, info)."""
+    lib = load_library()
+    nb, p, nx, mb = B.shape
+    nr = J.shape[2]
+    K = np.empty((nb, p, mb, nx)); Pi = np.empty((nb, p, nx, nx)); Phi = np.empty((nb, nx, nx)); Hn = np.zeros((nb, p, nx, nx))
+    cnt = np.zeros((nb, p), np.int32); info = np.zeros((nb, LQR_CTG_INFO_STRIDE))
+    rc = lib.tmpc_periodic_lqr_ctg_batch_host(nb, p, nx, mb, nr, int(ng), _dptr(A), _dptr(B), _dptr(H), _dptr(J), _iptr(ncnt), _dptr(Pi0), float(tol),
+                                              float(rank_tol), int(max_sweeps), _dptr(K), _dptr(Pi), _dptr(Phi), _dptr(Hn), _iptr(cnt), _dptr(info))
+    if rc == -1:      # TMPC_E_ARG: the library's message names the argument
+        raise ValueError(lib.tmpc_last_error().decode())
+    _check_lqr(lib, rc, 'tmpc_periodic_lqr_ctg_batch_host')
+    return K, Pi, Phi, Hn, cnt, info
+
+
+def periodic_lqr_ctg_batch_device(A, B, H, J, ncnt, ng, Pi0, tol, rank_tol, max_sweeps):
+    """tmpc_periodic_lqr_ctg_batch_device on validated, contiguous torch tensors of one GPU (fp64; ncnt int32 or None) -> (K, Pi, Phi, Hn, cnt, info)
+    tensors; A / B / H / J never leave HBM."""
+    import torch
+    lib = load_library()
+    nb, p, nx, mb = B.shape
+    nr = J.shape[2]
+    dev = A.device
+    f64 = lambda *sh: torch.empty(sh, dtype=torch.float64, device=dev)
+    K, Pi, Phi, info = f64(nb, p, mb, nx), f64(nb, p, nx, nx), f64(nb, nx, nx), torch.zeros((nb, LQR_CTG_INFO_STRIDE), dtype=torch.float64, device=dev)
+    Hn = torch.zeros((nb, p, nx, nx), dtype=torch.float64, device=dev); cnt = torch.zeros((nb, p), dtype=torch.int32, device=dev)
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+    with torch.cuda.device(dev):
+        torch.cuda.current_stream(dev).synchronize()      # the entry runs on the null stream: the inputs must be complete
+        rc = lib.tmpc_periodic_lqr_ctg_batch_device(nb, p, nx, mb, nr, int(ng), ptr(A), ptr(B), ptr(H), ptr(J), ptr(ncnt), ptr(Pi0), float(tol),
+                                                    float(rank_tol), int(max_sweeps), ptr(K), ptr(Pi), ptr(Phi), ptr(Hn), ptr(cnt), ptr(info))
+    if rc == -1:
+        raise ValueError(lib.tmpc_last_error().decode())
+    _check_lqr(lib, rc, 'tmpc_periodic_lqr_ctg_batch_device')
+    return K, Pi, Phi, Hn, cnt, info
 
 
 def cr_schedule(p):

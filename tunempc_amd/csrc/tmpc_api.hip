@@ -31,6 +31,7 @@
 #include "tmpc_eig.h"
 #include "tmpc_lqr.h"
 #include "tmpc_lqr_rows.h"
+#include "tmpc_lqr_ctg.h"
 #include "tmpc_dd.h"
 #include "tmpc_big.h"
 
@@ -1857,6 +1858,88 @@ int tmpc_periodic_lqr_rows_batch_host(int nb, int p, int nx, int mb, int nr, int
   HIPCHK(hipMemcpy(Pi, dPi, cA * 8, hipMemcpyDeviceToHost));
   if (Phi) HIPCHK(hipMemcpy(Phi, dPhi, cPhi * 8, hipMemcpyDeviceToHost));
   if (Lam && cL) HIPCHK(hipMemcpy(Lam, dL, cL * 8, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(info, dI, cI * 8, hipMemcpyDeviceToHost));
+  return TMPC_OK;
+}
+
+// The recursion with a constraint-to-go (tmpc_lqr_ctg.h): any rows.  Its own layout function decides what fits the LDS.
+static_assert(LQR_CTG_INFO == TMPC_LQR_CTG_INFO, "tunempc_hip.h: info stride of the constraint-to-go entries");
+
+static int lqr_ctg_check(const char* who, int nb, int p, int nx, int mb, int nr, int ng, const void* A, const void* B, const void* H, const void* J,
+                         double tol, double rank_tol, int max_sweeps, const void* K, const void* Pi, const void* Hn, const void* cnt, const void* info) {
+  const int rc = lqr_check(who, nb, p, nx, mb, A, B, H, tol, max_sweeps, K, Pi, info);
+  if (rc != TMPC_OK) return rc;
+  if (nr < 0 || ng < 0 || nr < ng || (nr > 0 && !J)) {
+    snprintf(g_err, sizeof(g_err), "%s: bad argument (0 <= ng <= nr, the row capacity per stage; non-null J when nr > 0; got ng = %d, nr = %d)", who, ng, nr);
+    return TMPC_E_ARG;
+  }
+  if (!(rank_tol > 0.0) || !(rank_tol < INFINITY) || !Hn || !cnt) {
+    snprintf(g_err, sizeof(g_err), "%s: bad argument (finite rank_tol > 0, non-null Hn, cnt; got rank_tol = %g)", who, rank_tol);
+    return TMPC_E_ARG;
+  }
+  const long long bytes = (long long)lqr_ctg_lds(nx, mb, nr < 4096 ? nr : 4096).total * (long long)sizeof(double);
+  if (bytes > LQR_LDS_BYTES) {
+    snprintf(g_err, sizeof(g_err), "%s: nx = %d, nu = %d with room for %d rows per stage and a constraint-to-go needs %lld bytes of LDS (limit %d)", who, nx, mb,
+             nr, bytes, LQR_LDS_BYTES);
+    return TMPC_E_UNSUPPORTED;
+  }
+  return TMPC_OK;
+}
+
+static int lqr_ctg_launch(int nb, int p, int nx, int mb, int nr, int ng, const double* A, const double* B, const double* H, const double* J,
+                          const int32_t* ncnt, const double* Pi0, double tol, double rank_tol, int max_sweeps, double* K, double* Pi, double* Phi, double* Hn,
+                          int32_t* cnt, double* info) {
+  const size_t lds_bytes = (size_t)lqr_ctg_lds(nx, mb, nr).total * sizeof(double);
+  HIPCHK(hipFuncSetAttribute((const void*)k_periodic_lqr_ctg, hipFuncAttributeMaxDynamicSharedMemorySize, LQR_LDS_BYTES));      // (the same value from every thread and call)
+  int lcw = 0;
+  while ((1 << lcw) < nx + mb) ++lcw;
+  hipLaunchKernelGGL(k_periodic_lqr_ctg, dim3(nb), dim3(LQR_NT), lds_bytes, 0, p, nx, mb, nr, ng, lcw, A, B, H, J, (const int*)ncnt, Pi0, tol, rank_tol,
+                     max_sweeps, K, Pi, Phi, Hn, (int*)cnt, info);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(0));
+  return TMPC_OK;
+}
+
+int tmpc_periodic_lqr_ctg_batch_device(int nb, int p, int nx, int mb, int nr, int ng, const double* A, const double* B, const double* H, const double* J,
+                                       const int32_t* ncnt, const double* Pi0, double tol, double rank_tol, int max_sweeps, double* K, double* Pi, double* Phi,
+                                       double* Hn, int32_t* cnt, double* info) {
+  const int rc = lqr_ctg_check("tmpc_periodic_lqr_ctg_batch_device", nb, p, nx, mb, nr, ng, A, B, H, J, tol, rank_tol, max_sweeps, K, Pi, Hn, cnt, info);
+  if (rc != TMPC_OK) return rc;
+  return lqr_ctg_launch(nb, p, nx, mb, nr, ng, A, B, H, J, ncnt, Pi0, tol, rank_tol, max_sweeps, K, Pi, Phi, Hn, cnt, info);
+}
+
+static thread_local EigScratch g_lqr_ctg_scratch;      // device images of the host entry, kept between calls and grown on demand
+
+int tmpc_periodic_lqr_ctg_batch_host(int nb, int p, int nx, int mb, int nr, int ng, const double* A, const double* B, const double* H, const double* J,
+                                     const int32_t* ncnt, const double* Pi0, double tol, double rank_tol, int max_sweeps, double* K, double* Pi, double* Phi,
+                                     double* Hn, int32_t* cnt, double* info) {
+  const char* who = "tmpc_periodic_lqr_ctg_batch_host";
+  const int rc = lqr_ctg_check(who, nb, p, nx, mb, nr, ng, A, B, H, J, tol, rank_tol, max_sweeps, K, Pi, Hn, cnt, info);
+  if (rc != TMPC_OK) return rc;
+  const size_t n = (size_t)nx + mb, st = (size_t)nb * p;
+  if (ncnt) for (size_t i = 0; i < st; ++i) if (ncnt[i] < 0 || ncnt[i] > nr - ng) {
+    snprintf(g_err, sizeof(g_err), "%s: ncnt[%zu][%zu] = %d outside 0 .. nr - ng = %d", who, i / p, i % p, (int)ncnt[i], nr - ng);
+    return TMPC_E_ARG;
+  }
+  const size_t cA = st * nx * nx, cB = st * nx * mb, cH = st * n * n, cPhi = (size_t)nb * nx * nx, cI = (size_t)nb * LQR_CTG_INFO, cJ = st * nr * n;
+  const size_t cN = (st + 1) / 2;                          // ncnt, cnt: int32, counted in doubles
+  HIPCHK(g_lqr_ctg_scratch.reserve((4 * cA + 2 * cB + cH + cPhi + cI + cJ + 2 * cN) * 8));      // A | B | H | Pi0 | K | Pi | Hn | Phi | info | J | ncnt | cnt
+  double* dA = (double*)g_lqr_ctg_scratch.p; double* dB = dA + cA; double* dH = dB + cB; double* dP0 = dH + cH; double* dK = dP0 + cA; double* dPi = dK + cB;
+  double* dHn = dPi + cA; double* dPhi = dHn + cA; double* dI = dPhi + cPhi; double* dJ = dI + cI; int32_t* dN = (int32_t*)(dJ + cJ); int32_t* dC = (int32_t*)(dJ + cJ + cN);
+  HIPCHK(hipMemcpy(dA, A, cA * 8, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dB, B, cB * 8, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dH, H, cH * 8, hipMemcpyHostToDevice));
+  if (cJ) HIPCHK(hipMemcpy(dJ, J, cJ * 8, hipMemcpyHostToDevice));
+  if (ncnt) HIPCHK(hipMemcpy(dN, ncnt, st * sizeof(int32_t), hipMemcpyHostToDevice));
+  if (Pi0) HIPCHK(hipMemcpy(dP0, Pi0, cA * 8, hipMemcpyHostToDevice));
+  const int rl = lqr_ctg_launch(nb, p, nx, mb, nr, ng, dA, dB, dH, dJ, ncnt ? dN : nullptr, Pi0 ? dP0 : nullptr, tol, rank_tol, max_sweeps, dK, dPi,
+                                Phi ? dPhi : nullptr, dHn, dC, dI);
+  if (rl != TMPC_OK) return rl;
+  HIPCHK(hipMemcpy(K, dK, cB * 8, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(Pi, dPi, cA * 8, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(Hn, dHn, cA * 8, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(cnt, dC, st * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (Phi) HIPCHK(hipMemcpy(Phi, dPhi, cPhi * 8, hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(info, dI, cI * 8, hipMemcpyDeviceToHost));
   return TMPC_OK;
 }

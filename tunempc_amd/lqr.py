@@ -14,6 +14,11 @@ For the models with rows (Step 1 with G, Steps 2 / 3 with C) the equivalence hol
 every call takes the rows (J=, ncnt=, ng= in the layout of convexify_step2_batch's library call; G=, C= as `convexify` takes them) and then runs the
 recursion with the rows held as equalities (csrc/tmpc_lqr_rows.h).  Without them the calls are the plain ones, bit for bit.
 
+That recursion serves r_k <= nu rows with an input part of full row rank.  state_rows=True (with rank_tol=) selects the constraint-to-go recursion
+(csrc/tmpc_lqr_ctg.h) for everything else: more rows than inputs, rows on the state alone, dependent rows.  What the rows say about x_k alone is carried
+backwards as Hn_k x_k = 0; gains and cost-to-go are returned projected on the feasible subspace, Pz_k = I - Hn_k' Hn_k, where they are unique, and the
+certificate compares the projected gains and the subspaces of the two sides.  An empty feasible subspace ends a problem with status 5.
+
 Conventions: stage cost 1/2 [x;u]' H_k [x;u] with H_k = [[Q_k, N_k], [N_k', R_k]] (x block first, the layout of convexify_batch),
 x_{k+1} = A_k x_k + B_k u_k, and u = -K_k x: the sign of scipy.linalg.solve_discrete_are / control.dare.
 There is no CPU path: the recursion runs in the HIP library or the call raises.
@@ -24,7 +29,7 @@ from . import _lib
 from . import preprocessing
 from .convexifier import _to_array, pack_rows
 
-STATUS_NAMES = {0: 'Converged', 1: 'MaxSweeps', 2: 'SingularS', 3: 'NonFinite', 4: 'RowsExceedInputs'}
+STATUS_NAMES = {0: 'Converged', 1: 'MaxSweeps', 2: 'SingularS', 3: 'NonFinite', 4: 'RowsExceedInputs', 5: 'NoFeasibleSubspace'}
 
 
 def _is_torch(x):
@@ -116,7 +121,17 @@ def _rho(Phi):
     return out
 
 
-def periodic_lqr_batch(A, B, H, Pi0=None, tol=1e-13, max_sweeps=5000, J=None, ncnt=None, ng=None):
+def _subspace_diff(nH, nC, use_torch):
+    """max_k max|Pz_k(H side) - Pz_k(Hc side)| per problem from the two Hn [nb,p,nx,nx] (Pz = I - Hn' Hn), computed where the arrays live -> numpy [nb]."""
+    if use_torch:
+        import torch
+        d = (torch.einsum('bkji,bkjl->bkil', nH, nH) - torch.einsum('bkji,bkjl->bkil', nC, nC)).abs()
+        return d.reshape(d.shape[0], -1).max(dim=1).values.cpu().numpy()
+    d = np.abs(np.einsum('bkji,bkjl->bkil', nH, nH) - np.einsum('bkji,bkjl->bkil', nC, nC))
+    return d.reshape(d.shape[0], -1).max(axis=1)
+
+
+def periodic_lqr_batch(A, B, H, Pi0=None, tol=1e-13, max_sweeps=5000, J=None, ncnt=None, ng=None, state_rows=False, rank_tol=1e-9):
     """Gains of nb p-periodic LQ problems.  A [nb,p,nx,nx], B [nb,p,nx,nu], H [nb,p,n,n] (n = nx + nu <= 64), fp64; per stage, indices mod p,
 
         E = [A_k B_k],  Hb = H_k + E' Pi_{k+1} E,  S = Hb_uu,  M = Hb_ux,  K_k = S^-1 M  (u = -K_k x),  Pi_k = sym(Hb_xx - M' K_k),
@@ -139,16 +154,44 @@ def periodic_lqr_batch(A, B, H, Pi0=None, tol=1e-13, max_sweeps=5000, J=None, nc
     stage problem was shown convex (S positive definite and Ju of full row rank).  Served: r_k <= nu with Ju of full row rank.  status 4
     (RowsExceedInputs): r_k > nu at some stage -- sweeps 0, K and Lam zero, Pi = Pi0, Phi NaN; status 2 also covers a rank-deficient Ju.  Rows that
     constrain the state alone (Ju = 0) would need a constraint-to-go recursion: not provided, they end with status 2.  NotImplementedError also for
-    (nx, nu, nr) beyond the 160 KB of LDS (n <= 32: never for nr <= 66; 32 < n <= 64: never for nr <= 15).  With J=None the plain entry is called."""
+    (nx, nu, nr) beyond the 160 KB of LDS (n <= 32: never for nr <= 66; 32 < n <= 64: never for nr <= 15).  With J=None the plain entry is called.
+
+    state_rows=True (requires J): the constraint-to-go recursion, for any rows -- r_k > nu, rows on the state alone, dependent rows.  Stage k stacks
+    Cf = [J_k; Hn_{k+1} [A_k B_k]], splits it by elimination with full pivoting on its u columns (a pivot counts while it exceeds
+    rank_tol * max(1, max|Cf|)) into rows of full row rank in u, solved as above, and rows on the state alone, whose independent part is the constraint-to-go
+    Hn_k (c_k orthonormal rows, Hn_k x_k = 0); K_k and Pi_k are returned projected with Pz_k = I - Hn_k' Hn_k (u = -K_k x holds for feasible x_k; off the
+    subspace it says nothing), Phi = (A-BK)_{p-1} ... (A-BK)_0 Pz_0.  Sweeps stop when the change is <= tol and no c_k changed.  The dict then carries
+    Hn [nb,p,nx,nx] (rows beyond c_k zero), cnt [nb,p] int32 (c_k), feas [nb] = info[:, 7] = max_k max(|(Jx - Ju K_k) Pz_k|, |Hn_{k+1} (A_k - B_k K_k) Pz_k|),
+    info [nb,12] (8: sum of c_k, 9: max c_k, 10 / 11: smallest accepted / largest rejected pivot of the rank decisions relative to the stage scale) and no
+    Lam (the multipliers are not unique); info[:, 5:7] read 0 ("not shown") more often than without state_rows, because the rows enter the elimination scaled
+    to S and compete with its diagonal for the pivot.  status 5 (NoFeasibleSubspace): some c_k reached nx; status 4 does not occur.  With every r_k <= nu and full rank the
+    result is that of the call without state_rows up to rounding (the pivot order differs).  NotImplementedError for (nx, nu, nr) beyond the 160 KB of
+    LDS of its wider layout (the bench stage shape with room for 10 rows takes 61 KB)."""
     use_torch, nb, p, nx, mb = _validate(A, B, H, (('Pi0', Pi0, 'A'),))
     if not (float(tol) >= 0.0) or int(max_sweeps) < 1:
         raise ValueError('periodic_lqr_batch: tol >= 0 and max_sweeps >= 1 expected, got {}, {}'.format(tol, max_sweeps))
     if J is None and (ncnt is not None or ng is not None):
         raise ValueError('periodic_lqr_batch: ncnt / ng describe the rows of J, which is None')
+    if state_rows:
+        if J is None:
+            raise ValueError('periodic_lqr_batch: state_rows=True is the recursion for the rows of J, which is None')
+        if isinstance(rank_tol, bool) or not isinstance(rank_tol, (int, float, np.floating)) or not (0.0 < float(rank_tol) < 1.0):
+            raise ValueError('periodic_lqr_batch: 0 < rank_tol < 1 expected, got {!r}'.format(rank_tol))
     if J is not None:
         nr, ng = _validate_rows(J, ncnt, ng, use_torch, A, nb, p, nx + mb)
         A, B, H, Pi0, J, ncnt = (_contig(x, use_torch) if x is not ncnt else (x if x is None else (x.contiguous() if use_torch else np.ascontiguousarray(x)))
                                  for x in (A, B, H, Pi0, J, ncnt))
+        if state_rows:
+            if use_torch:
+                import torch
+                K, Pi, Phi, Hn, cnt, info = _lib.periodic_lqr_ctg_batch_device(A, B, H, J, ncnt, ng, Pi0, tol, rank_tol, max_sweeps)
+                rho = _rho(Phi.cpu().numpy())
+                status = info[:, 0].to(torch.int32); sweeps = info[:, 1].to(torch.int32); feas = info[:, 7].clone()
+            else:
+                K, Pi, Phi, Hn, cnt, info = _lib.periodic_lqr_ctg_batch_host(A, B, H, J, ncnt, ng, Pi0, tol, rank_tol, max_sweeps)
+                rho = _rho(Phi)
+                status = info[:, 0].astype(np.int32); sweeps = info[:, 1].astype(np.int32); feas = info[:, 7].copy()
+            return dict(K=K, Pi=Pi, Phi=Phi, rho=rho, status=status, sweeps=sweeps, info=info, Hn=Hn, cnt=cnt, feas=feas)
         if use_torch:
             import torch
             K, Pi, Phi, Lam, info = _lib.periodic_lqr_rows_batch_device(A, B, H, J, ncnt, ng, Pi0, tol, max_sweeps)
@@ -202,12 +245,17 @@ def _stack_stages(A, B, Q, R, N, G=None, C=None):
     return As[None], Bs[None], Hs[None], rows
 
 
-def periodic_lqr(A, B, Q, R, N, tol=1e-13, max_sweeps=5000, G=None, C=None):
+def periodic_lqr(A, B, Q, R, N, tol=1e-13, max_sweeps=5000, G=None, C=None, state_rows=False, rank_tol=1e-9):
     """The gains of one problem in the reference's calling style: A, B, Q, R, N single matrices (p = 1) or lists of length p, as `convexify`
     takes them -> (K_list, Pi_list, rho): p gains K_k (nu x nx, u = -K_k x), p cost-to-go matrices, the closed-loop spectral radius.
-    G, C (as `convexify` takes them): the rows held as equalities, see periodic_lqr_batch.
+    G, C (as `convexify` takes them): the rows held as equalities, see periodic_lqr_batch.  state_rows=True, rank_tol: the constraint-to-go recursion
+    (any rows; the gains and cost-to-go matrices are the projected ones, valid on the feasible subspace of each stage).
     RuntimeError when the recursion did not converge (status of periodic_lqr_batch != 0)."""
     As, Bs, Hs, rows = _stack_stages(A, B, Q, R, N, G, C)
+    if state_rows:
+        if not rows:
+            raise ValueError('periodic_lqr: state_rows=True is the recursion for the rows G / C, which are None')
+        rows.update(state_rows=True, rank_tol=rank_tol)
     r = periodic_lqr_batch(As, Bs, Hs, tol=tol, max_sweeps=max_sweeps, **rows)
     st = int(r['status'][0])
     if st != 0:
@@ -216,7 +264,7 @@ def periodic_lqr(A, B, Q, R, N, tol=1e-13, max_sweeps=5000, G=None, C=None):
     return [r['K'][0, k].copy() for k in range(p)], [r['Pi'][0, k].copy() for k in range(p)], float(r['rho'][0])
 
 
-def feedback_equivalence_batch(A, B, H, Hc, P=None, tol=1e-13, max_sweeps=5000, J=None, ncnt=None, ng=None):
+def feedback_equivalence_batch(A, B, H, Hc, P=None, tol=1e-13, max_sweeps=5000, J=None, ncnt=None, ng=None, state_rows=False, rank_tol=1e-9):
     """The certificate: gains of the LQ problems on H and on Hc (two recursions), compared.  A, B, H as in periodic_lqr_batch, Hc [nb,p,n,n]
     (the `Hc` of convexify_batch, or H + dHc), numpy or torch GPU tensors.  Returns dict: dK [nb] = max_k max|K_k(H) - K_k(Hc)|,
     dK_rel = dK / max(1, max|K(Hc)|), rho_H, rho_Hc (numpy), status_H, status_Hc, sweeps_H, sweeps_Hc, posdef_H (info[6] of the H side: 1.0 if S was positive definite on its whole path), K, Kc.
@@ -234,9 +282,16 @@ def feedback_equivalence_batch(A, B, H, Hc, P=None, tol=1e-13, max_sweeps=5000, 
     J_k [x_k; u_k] = 0, the term J_k' diag(phi_k) J_k of Hc drops out and dK is at rounding level again (without J the unconstrained gains of H and
     Hc differ by design once a multiplier is non-zero -- a wrong alarm); the dict gains feas_H, feas_Hc (max|Jx - Ju K_k|), convex_Hc (info[6] of the
     Hc side: every stage problem shown convex) and Lam, Lamc.  After Step 3 with rows dK measures T_k as it does without rows.  Not covered: rows
-    that constrain the state alone (Ju without full row rank: status 2) and stages with more rows than inputs (status 4)."""
+    that constrain the state alone (Ju without full row rank: status 2) and stages with more rows than inputs (status 4) -- unless state_rows=True.
+
+    state_rows=True, rank_tol (requires J): both recursions are the constraint-to-go recursion of periodic_lqr_batch, which serves those cases too.  dK is
+    then taken on the projected gains K_k Pz_k (the gains on the feasible subspaces), the dict carries subspace_diff [nb] = max_k max|Pz_k(H side) -
+    Pz_k(Hc side)| (the subspaces depend on A, B and the rows only: it must be at rounding level, and dK means nothing where it is not), cnt, cntc, Hn, Hnc
+    instead of Lam, Lamc; convex_Hc is reported but seldom 1 (see periodic_lqr_batch).  Not covered: an empty feasible subspace (status 5) and shapes beyond the LDS layout."""
     use_torch, nb, p, nx, mb = _validate(A, B, H, (('Hc', Hc, 'H'), ('P', P, 'A')))
     rows = {} if J is None and ncnt is None and ng is None else dict(J=J, ncnt=ncnt, ng=ng)
+    if state_rows:
+        rows.update(state_rows=True, rank_tol=rank_tol)             # (without J: the ValueError of periodic_lqr_batch)
     rH = periodic_lqr_batch(A, B, H, Pi0=P, tol=tol, max_sweeps=max_sweeps, **rows)
     rC = periodic_lqr_batch(A, B, Hc, tol=tol, max_sweeps=max_sweeps, **rows)
     d = (rH['K'] - rC['K']).abs() if use_torch else np.abs(rH['K'] - rC['K'])
@@ -251,20 +306,32 @@ def feedback_equivalence_batch(A, B, H, Hc, P=None, tol=1e-13, max_sweeps=5000, 
                sweeps_H=rH['sweeps'], sweeps_Hc=rC['sweeps'], posdef_H=posdef, K=rH['K'], Kc=rC['K'])
     if rows:
         host = (lambda x: x.cpu().numpy()) if use_torch else (lambda x: x.copy())
-        out.update(feas_H=host(rH['feas']), feas_Hc=host(rC['feas']), convex_Hc=host(rC['info'][:, 6]), Lam=rH['Lam'], Lamc=rC['Lam'])
+        out.update(feas_H=host(rH['feas']), feas_Hc=host(rC['feas']), convex_Hc=host(rC['info'][:, 6]))
+        if state_rows:
+            out.update(subspace_diff=_subspace_diff(rH['Hn'], rC['Hn'], use_torch), cnt=rH['cnt'], cntc=rC['cnt'], Hn=rH['Hn'], Hnc=rC['Hn'])
+        else:
+            out.update(Lam=rH['Lam'], Lamc=rC['Lam'])
     return out
 
 
-def feedback_equivalence(A, B, Q, R, N, dHc, tol=1e-13, max_sweeps=5000, G=None, C=None):
+def feedback_equivalence(A, B, Q, R, N, dHc, tol=1e-13, max_sweeps=5000, G=None, C=None, state_rows=False, rank_tol=1e-9):
     """feedback_equivalence_batch for one problem in the calling style of `convexify`: dHc is its first return value (list of p supplements,
     Hc_k = H_k + dHc_k).  Returns the dict of the batched call with scalars for dK, dK_rel, rho_H, rho_Hc, status_H, status_Hc and lists of
-    p gains for K, Kc.  G, C: the rows `convexify` was called with (then also feas_H, feas_Hc, convex_Hc as scalars)."""
+    p gains for K, Kc.  G, C: the rows `convexify` was called with (then also feas_H, feas_Hc, convex_Hc as scalars).  state_rows=True, rank_tol: the
+    constraint-to-go recursion on both sides (any rows; also subspace_diff as a scalar and cnt, cntc as lists of p counts)."""
     As, Bs, Hs, rows = _stack_stages(A, B, Q, R, N, G, C)
     dH = np.stack([_to_array(d) for d in (dHc if isinstance(dHc, (list, tuple)) else [dHc])])[None]      # (convexify returns a list also at p = 1)
     if dH.shape != Hs.shape:
         raise ValueError('feedback_equivalence: dHc must hold p matrices (nx+nu, nx+nu), got {}'.format(dH.shape[1:]))
+    if state_rows:
+        if not rows:
+            raise ValueError('feedback_equivalence: state_rows=True is the recursion for the rows G / C, which are None')
+        rows.update(state_rows=True, rank_tol=rank_tol)
     r = feedback_equivalence_batch(As, Bs, Hs, Hs + dH, tol=tol, max_sweeps=max_sweeps, **rows)
     p = As.shape[1]
-    out = {k: (float(v[0]) if k.startswith(('dK', 'rho', 'posdef', 'feas', 'convex')) else int(v[0])) for k, v in r.items() if k not in ('K', 'Kc', 'Lam', 'Lamc')}
+    out = {k: (float(v[0]) if k.startswith(('dK', 'rho', 'posdef', 'feas', 'convex', 'subspace')) else int(v[0])) for k, v in r.items()
+           if k not in ('K', 'Kc', 'Lam', 'Lamc', 'Hn', 'Hnc', 'cnt', 'cntc')}
+    if state_rows:
+        out['cnt'] = [int(c) for c in r['cnt'][0]]; out['cntc'] = [int(c) for c in r['cntc'][0]]
     out['K'] = [r['K'][0, k].copy() for k in range(p)]; out['Kc'] = [r['Kc'][0, k].copy() for k in range(p)]
     return out
