@@ -341,6 +341,32 @@ int tmpc_periodic_lqr_ctg_batch_device(int nb, int p, int nx, int mb, int nr, in
                                        const int32_t* ncnt, const double* Pi0, double tol, double rank_tol, int max_sweeps, double* K, double* Pi, double* Phi,
                                        double* Hn, int32_t* cnt, double* info);
 
+/* Finite-horizon gains: the first-order feedback u_0 = -K_0 x_0 of the horizon-N problem that starts at phase k0 of the p-periodic model, for a list of
+ * starting phases (tmpc_lqr_horizon.h; reference pmpc.py:162-281, the LQ content of closed_loop_tools.check_equivalence).  One backward pass j = N-1 ... 0 over
+ * the stages k = (k0 + j) mod p per (problem, phase), no convergence loop; N may be smaller than, equal to or larger than p.  The stage is that of the ctg
+ * entry, so any rows are served; the pass starts from Pi_N = Pf[(k0 + N) mod p] (Pf [nb][p][nx][nx]; NULL: zero) and
+ *     terminal = 0 (cost):        Hn_N empty;
+ *     terminal = 1 (constraint):  Hn_N = I, i.e. x_N = 0 (c_N = nx is legal at this given stage only; a general terminal operator is not provided).
+ * Arguments of the ctg entry (nr = 0 with J = NULL allowed) plus N, nph and phases: int32 [nph], a HOST pointer in both entries (NULL: all p phases in order,
+ * nph must then equal p).  Outputs per (problem, phase): K0 [nb][nph][mb][nx], Pi0 [nb][nph][nx][nx], Hn0 [nb][nph][nx][nx] (rows beyond c_0 zero), all projected
+ * on the feasible subspace of x_0 as in the ctg entry; cnt0 int32 [nb][nph] = c_0; optional Kall [nb][nph][N][mb][nx] and cntall int32 [nb][nph][N], the gains
+ * and counts of every stage j of the pass (large: nb nph N mb nx doubles); info [nb][nph][12]:
+ *   [0] status: 0 done, 2 singular stage system, 3 non-finite, 5 no feasible subspace (a computed c_j reached nx); 1 and 4 are never returned.  With status >= 2
+ *       K0 and Pi0 are NaN, Hn0 is zero, cnt0 is the count at the failing stage (nx for status 5), and the stages of Kall / cntall that were not finished hold
+ *       NaN / -1.  One (problem, phase) never affects another;
+ *   [1] N, [2] stages finished, [3] / [4] smallest / largest |pivot| of the stage systems, [5] = [6] 1.0 if every stage problem was shown convex,
+ *   [7] feas = max_j max(|(Jx - Ju K_j) Pz_j|, |Hn_{j+1} (A - B K_j) Pz_j|), taken inside each stage (0 when status >= 2),
+ *   [8] sum_j c_j, [9] max_j c_j (the given c_N not counted), [10] / [11] smallest accepted / largest rejected pivot of the rank decisions, as in the ctg entry.
+ * TMPC_E_ARG: N < 1, nph < 1, phases NULL with nph != p, a phase outside 0 .. p-1, terminal not 0 / 1, nr < ng, rank_tol <= 0, NULL outputs, (host entry) ncnt
+ * outside 0 .. nr - ng.  TMPC_E_UNSUPPORTED (before the device is touched): nx + mb > TMPC_LQR_NMAX, (nx, mb, nr) beyond the 160 KB LDS layout of the ctg
+ * entry, nph > 65535. */
+int tmpc_horizon_lqr_batch_host(int nb, int p, int nx, int mb, int nr, int ng, int N, int nph, const int32_t* phases, int terminal, const double* A,
+                                const double* B, const double* H, const double* J, const int32_t* ncnt, const double* Pf, double rank_tol, double* K0,
+                                double* Pi0, double* Hn0, int32_t* cnt0, double* Kall, int32_t* cntall, double* info);
+int tmpc_horizon_lqr_batch_device(int nb, int p, int nx, int mb, int nr, int ng, int N, int nph, const int32_t* phases, int terminal, const double* A,
+                                  const double* B, const double* H, const double* J, const int32_t* ncnt, const double* Pf, double rank_tol, double* K0,
+                                  double* Pi0, double* Hn0, int32_t* cnt0, double* Kall, int32_t* cntall, double* info);
+
 /* Accumulated hipEvent timings since the last call (ms) when TMPC_FLAG_PROFILE is set, 16 doubles:
  * out[0] stage_pre+ctrl, [1] schur assembly, [2] block factorisation (all kernels of tmpc_cr.h's factor phase), [3] predictor
  * pass, [4] corrector pass + update, [5] number of factorisation phases (= IPM iterations of the chunks), [6] total ms of the

@@ -9,9 +9,12 @@ The rows leg (csrc/tmpc_lqr_rows.h) times, in the same run on the same inputs (t
 rows per stage and the rows entry with room for 5 rows that no stage uses, and the certificate with rows -> profiles/lqr_rows_timing.json.
 The ctg leg (--ctg; csrc/tmpc_lqr_ctg.h) times, on the Hc side of the same batch with 5 random rows at every stage, the rows entry and the constraint-to-go
 entry next to each other (the rows fit the inputs, so both serve them), and the two certificates -> profiles/lqr_ctg_timing.json; nothing else is run.
+The horizon leg (--horizon; csrc/tmpc_lqr_horizon.h) times, on the same inputs as the ctg leg, the finite-horizon entry from all 64 phases with terminal='cost'
+at N = 16 and N = 64 interleaved with the constraint-to-go entry, and reports the time per workgroup-stage of both -> profiles/lqr_horizon_timing.json.
 
     python scripts/lqr_timing.py [--reps 15] [--batch 512] [--out profiles/lqr_timing.json] [--rows-out profiles/lqr_rows_timing.json] [--rows-only]
     python scripts/lqr_timing.py --ctg [--reps 15] [--batch 512] [--ctg-out profiles/lqr_ctg_timing.json]
+    python scripts/lqr_timing.py --horizon [--reps 15] [--batch 512] [--horizon-out profiles/lqr_horizon_timing.json]
 """
 import argparse
 import json
@@ -116,6 +119,46 @@ def measure_ctg(A, B, H, Hc, P, reps):
     return res
 
 
+def measure_horizon(A, B, H, Hc, P, reps):
+    """Finite-horizon entry (all p phases, terminal cost, N = 16 and N = 64) and constraint-to-go entry on the Hc side of one batch with 5 rows at every stage,
+    interleaved in one run.  Time per workgroup-stage: the elapsed time over the stages all workgroups ran (ctg: its sweeps times p per problem, plus the p
+    lighter stages of its monodromy pass counted as stages; horizon: nb * p * N), i.e. the throughput figure; `stage_chain_us` is the elapsed time over the
+    stages ONE workgroup ran one after the other, the latency figure, which for the horizon entry includes waiting for a place on a compute unit."""
+    nb, p, nx, _ = A.shape
+    n = H.shape[2]
+    J = np.random.default_rng(100002).standard_normal((nb, p, 5, n))
+    dA, dB, dHc, dJ = (torch.from_numpy(np.ascontiguousarray(x)).cuda() for x in (A, B, Hc, J))
+    tol, max_sweeps = 1e-10, 200                             # (the settings of the ctg leg)
+    ctg = lambda: _lib.periodic_lqr_ctg_batch_device(dA, dB, dHc, dJ, None, 5, None, tol, 1e-9, max_sweeps)
+    hor = {N: (lambda N=N: _lib.horizon_lqr_batch_device(dA, dB, dHc, dJ, None, 5, N, None, 0, None, 1e-9, False)) for N in (16, 64)}
+    o_ctg = ctg()
+    sweeps = o_ctg[5][:, 1]
+    print('horizon leg: ctg sweeps', int(sweeps.min()), int(sweeps.max()), flush=True)
+    ctg_stages = float((sweeps.sum() + nb) * p)
+    res = dict(shape=dict(nb=int(nb), p=int(p), nx=int(nx), nu=int(n - nx), rows_per_stage=5, phases=int(p), workgroups_horizon=int(nb * p), workgroups_ctg=int(nb)),
+               terminal='cost', ctg=dict(tol=tol, max_sweeps=max_sweeps, sweeps=[int(sweeps.min()), int(sweeps.max())], converged=int((o_ctg[5][:, 0] == 0).sum())))
+    for N, fn in hor.items():
+        o = fn()
+        print('horizon leg: N', N, 'done', int((o[6][..., 0] == 0).sum()), 'of', nb * p, flush=True)
+        res['N%d' % N] = dict(done=int((o[6][..., 0] == 0).sum()), feas_max=float(o[6][..., 7].max()), counts_sum=int(o[3].sum()))
+        if N == 64:                                          # a long horizon: K_0 against the periodic gain of the same problem
+            res['N64']['K0_minus_periodic_K_max'] = float((o[0] - o_ctg[0]).abs().max())
+        del o
+    for rnd in range(2):                                     # two interleaved rounds: drift of the box shows as a difference between them
+        r = dict(ctg_entry_ms=median_ms(ctg, reps))
+        r['ctg_us_per_workgroup_stage'] = r['ctg_entry_ms']['median'] * 1e3 / ctg_stages
+        r['ctg_stage_chain_us'] = r['ctg_entry_ms']['median'] * 1e3 / ((int(sweeps.max()) + 1) * p)
+        for N, fn in hor.items():
+            ms = median_ms(fn, reps)
+            r['horizon_N%d_entry_ms' % N] = ms
+            r['horizon_N%d_us_per_workgroup_stage' % N] = ms['median'] * 1e3 / (nb * p * N)
+            r['horizon_N%d_stage_chain_us' % N] = ms['median'] * 1e3 / N
+            r['horizon_N%d_over_ctg_per_workgroup_stage' % N] = r['horizon_N%d_us_per_workgroup_stage' % N] / r['ctg_us_per_workgroup_stage']
+        res['round%d' % rnd] = r
+    print('horizon leg', json.dumps(res))
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reps', type=int, default=15)
@@ -125,6 +168,8 @@ def main():
     ap.add_argument('--rows-only', action='store_true', help='only the rows leg (it times the plain entry itself)')
     ap.add_argument('--ctg', action='store_true', help='only the constraint-to-go leg: rows entry against ctg entry with 5 rows per stage')
     ap.add_argument('--ctg-out', default=os.path.join(ROOT, 'profiles', 'lqr_ctg_timing.json'))
+    ap.add_argument('--horizon', action='store_true', help='only the finite-horizon leg: horizon entry (all phases, N = 16 and 64) against the ctg entry')
+    ap.add_argument('--horizon-out', default=os.path.join(ROOT, 'profiles', 'lqr_horizon_timing.json'))
     ap.add_argument('--kernel-only', action='store_true', help='one pass over the three inputs without timing (for a kernel trace)')
     args = ap.parse_args()
     assert args.reps >= 10 or args.kernel_only
@@ -142,6 +187,15 @@ def main():
         with open(args.ctg_out, 'w') as f:
             json.dump(out, f, indent=1)
         print('wrote', args.ctg_out)
+        return
+    if args.horizon:
+        assert not args.kernel_only
+        out = dict(device=torch.cuda.get_device_name(0), reps=args.reps, optimal_members=int((conv['status'] == 0).sum()),
+                   bench=measure_horizon(A, B, H, conv['Hc'], conv['P'], args.reps))
+        os.makedirs(os.path.dirname(os.path.abspath(args.horizon_out)), exist_ok=True)
+        with open(args.horizon_out, 'w') as f:
+            json.dump(out, f, indent=1)
+        print('wrote', args.horizon_out)
         return
     if not args.kernel_only:
         step_ms = json.load(open(os.path.join(ROOT, 'BENCH_r06.json')))['parsed']['ms_per_step']

@@ -24,7 +24,7 @@ EXPORTS = [
     'tmpc_convexify_con_batch_device', 'tmpc_workspace_bytes_step3', 'tmpc_create_step3', 'tmpc_convexify_step3_batch_host', 'tmpc_workspace_bytes_step3_con', 'tmpc_create_step3_con', 'tmpc_convexify_step3_con_batch_host', 'tmpc_convexify_step3_batch_device', 'tmpc_convexify_step3_con_batch_device', 'tmpc_supplement_batch_host', 'tmpc_supplement_terms_batch_host',
     'tmpc_tracking_reference_host', 'tmpc_eig_scan_host', 'tmpc_get_profile', 'tmpc_get_trace', 'tmpc_get_dual_host', 'tmpc_get_dual_con_host', 'tmpc_pack_sensitivities_host', 'tmpc_eig_clip_host',
     'tmpc_periodic_lqr_batch_host', 'tmpc_periodic_lqr_batch_device', 'tmpc_periodic_lqr_rows_batch_host', 'tmpc_periodic_lqr_rows_batch_device',
-    'tmpc_periodic_lqr_ctg_batch_host', 'tmpc_periodic_lqr_ctg_batch_device',
+    'tmpc_periodic_lqr_ctg_batch_host', 'tmpc_periodic_lqr_ctg_batch_device', 'tmpc_horizon_lqr_batch_host', 'tmpc_horizon_lqr_batch_device',
     'tmpc_last_error', 'tmpc_version',
 ]
 # ... and in include/tunempc_hip_debug.h (unit-test / diagnostic entries)
@@ -137,6 +137,10 @@ def load_library():
     lib.tmpc_periodic_lqr_ctg_batch_host.argtypes = [C.c_int] * 6 + [dp] * 4 + [ip, dp, C.c_double, C.c_double, C.c_int] + [dp] * 4 + [ip, dp]
     lib.tmpc_periodic_lqr_ctg_batch_device.restype = C.c_int
     lib.tmpc_periodic_lqr_ctg_batch_device.argtypes = [C.c_int] * 6 + [vp] * 6 + [C.c_double, C.c_double, C.c_int] + [vp] * 6
+    lib.tmpc_horizon_lqr_batch_host.restype = C.c_int
+    lib.tmpc_horizon_lqr_batch_host.argtypes = [C.c_int] * 8 + [ip, C.c_int] + [dp] * 4 + [ip, dp, C.c_double] + [dp] * 3 + [ip, dp, ip, dp]
+    lib.tmpc_horizon_lqr_batch_device.restype = C.c_int
+    lib.tmpc_horizon_lqr_batch_device.argtypes = [C.c_int] * 8 + [ip, C.c_int] + [vp] * 6 + [C.c_double] + [vp] * 7
     lib.tmpc_get_profile.restype = C.c_int
     lib.tmpc_get_profile.argtypes = [vp, dp]
     lib.tmpc_get_trace.restype = C.c_int
@@ -741,6 +745,51 @@ def periodic_lqr_ctg_batch_device(A, B, H, J, ncnt, ng, Pi0, tol, rank_tol, max_
         raise ValueError(lib.tmpc_last_error().decode())
     _check_lqr(lib, rc, 'tmpc_periodic_lqr_ctg_batch_device')
     return K, Pi, Phi, Hn, cnt, info
+
+
+def horizon_lqr_batch_host(A, B, H, J, ncnt, ng, N, phases, terminal, Pf, rank_tol, return_all):
+    """tmpc_horizon_lqr_batch_host on validated, contiguous numpy arrays (fp64; J None or [nb,p,nr,n]; ncnt int32 or None; phases int32 [nph] or None: all p;
+    terminal 0 cost / 1 constraint) -> (K0, Pi0, Hn0, cnt0, Kall or None, cntall or None, info)."""
+    lib = load_library()
+    nb, p, nx, mb = B.shape
+    nr = 0 if J is None else J.shape[2]
+    nph = p if phases is None else len(phases)
+    K0 = np.empty((nb, nph, mb, nx)); Pi0 = np.empty((nb, nph, nx, nx)); Hn0 = np.zeros((nb, nph, nx, nx)); cnt0 = np.zeros((nb, nph), np.int32)
+    info = np.zeros((nb, nph, LQR_CTG_INFO_STRIDE))
+    Kall = np.empty((nb, nph, int(N), mb, nx)) if return_all else None
+    cntall = np.zeros((nb, nph, int(N)), np.int32) if return_all else None
+    rc = lib.tmpc_horizon_lqr_batch_host(nb, p, nx, mb, nr, int(ng), int(N), nph, _iptr(phases), int(terminal), _dptr(A), _dptr(B), _dptr(H),
+                                         _dptr(J) if nr else None, _iptr(ncnt), _dptr(Pf), float(rank_tol), _dptr(K0), _dptr(Pi0), _dptr(Hn0), _iptr(cnt0),
+                                         _dptr(Kall), _iptr(cntall), _dptr(info))
+    if rc == -1:      # TMPC_E_ARG: the library's message names the argument
+        raise ValueError(lib.tmpc_last_error().decode())
+    _check_lqr(lib, rc, 'tmpc_horizon_lqr_batch_host')
+    return K0, Pi0, Hn0, cnt0, Kall, cntall, info
+
+
+def horizon_lqr_batch_device(A, B, H, J, ncnt, ng, N, phases, terminal, Pf, rank_tol, return_all):
+    """tmpc_horizon_lqr_batch_device on validated, contiguous torch tensors of one GPU (fp64; ncnt int32 or None); phases is a numpy int32 array or None (the
+    entry takes the list from the host) -> (K0, Pi0, Hn0, cnt0, Kall or None, cntall or None, info) tensors; A / B / H / J / Pf never leave HBM."""
+    import torch
+    lib = load_library()
+    nb, p, nx, mb = B.shape
+    nr = 0 if J is None else J.shape[2]
+    nph = p if phases is None else len(phases)
+    dev = A.device
+    f64 = lambda *sh: torch.empty(sh, dtype=torch.float64, device=dev)
+    K0, Pi0, info = f64(nb, nph, mb, nx), f64(nb, nph, nx, nx), torch.zeros((nb, nph, LQR_CTG_INFO_STRIDE), dtype=torch.float64, device=dev)
+    Hn0 = torch.zeros((nb, nph, nx, nx), dtype=torch.float64, device=dev); cnt0 = torch.zeros((nb, nph), dtype=torch.int32, device=dev)
+    Kall = f64(nb, nph, int(N), mb, nx) if return_all else None
+    cntall = torch.zeros((nb, nph, int(N)), dtype=torch.int32, device=dev) if return_all else None
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+    with torch.cuda.device(dev):
+        torch.cuda.current_stream(dev).synchronize()      # the entry runs on the null stream: the inputs must be complete
+        rc = lib.tmpc_horizon_lqr_batch_device(nb, p, nx, mb, nr, int(ng), int(N), nph, _iptr(phases), int(terminal), ptr(A), ptr(B), ptr(H), ptr(J), ptr(ncnt),
+                                               ptr(Pf), float(rank_tol), ptr(K0), ptr(Pi0), ptr(Hn0), ptr(cnt0), ptr(Kall), ptr(cntall), ptr(info))
+    if rc == -1:
+        raise ValueError(lib.tmpc_last_error().decode())
+    _check_lqr(lib, rc, 'tmpc_horizon_lqr_batch_device')
+    return K0, Pi0, Hn0, cnt0, Kall, cntall, info
 
 
 def cr_schedule(p):

@@ -32,6 +32,7 @@
 #include "tmpc_lqr.h"
 #include "tmpc_lqr_rows.h"
 #include "tmpc_lqr_ctg.h"
+#include "tmpc_lqr_horizon.h"
 #include "tmpc_dd.h"
 #include "tmpc_big.h"
 
@@ -1940,6 +1941,119 @@ int tmpc_periodic_lqr_ctg_batch_host(int nb, int p, int nx, int mb, int nr, int 
   HIPCHK(hipMemcpy(Hn, dHn, cA * 8, hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(cnt, dC, st * sizeof(int32_t), hipMemcpyDeviceToHost));
   if (Phi) HIPCHK(hipMemcpy(Phi, dPhi, cPhi * 8, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(info, dI, cI * 8, hipMemcpyDeviceToHost));
+  return TMPC_OK;
+}
+
+// Finite-horizon gains (tmpc_lqr_horizon.h): one backward pass of N stages per (problem, starting phase), the stage and the LDS layout of the ctg entry.
+// phases is a host pointer in both entries: the list is checked here and copied.
+static int lqr_horizon_check(const char* who, int nb, int p, int nx, int mb, int nr, int ng, int N, int nph, const int32_t* phases, int terminal, const void* A,
+                             const void* B, const void* H, const void* J, double rank_tol, const void* K0, const void* Pi0, const void* Hn0, const void* cnt0,
+                             const void* info) {
+  if (nb < 1 || p < 1 || nx < 1 || mb < 1 || !A || !B || !H || !K0 || !Pi0 || !Hn0 || !cnt0 || !info) {
+    snprintf(g_err, sizeof(g_err), "%s: bad argument (nb, p, nx, nu >= 1, non-null A, B, H, K0, Pi0, Hn0, cnt0, info)", who);
+    return TMPC_E_ARG;
+  }
+  if (N < 1 || nph < 1 || (!phases && nph != p) || (terminal != LQR_TERMINAL_COST && terminal != LQR_TERMINAL_CONSTRAINT)) {
+    snprintf(g_err, sizeof(g_err), "%s: bad argument (N >= 1, nph >= 1, nph = p without a list of phases, terminal 0 (cost) or 1 (constraint); got N = %d, nph = %d, "
+             "p = %d, terminal = %d)", who, N, nph, p, terminal);
+    return TMPC_E_ARG;
+  }
+  if (phases) for (int i = 0; i < nph; ++i) if (phases[i] < 0 || phases[i] >= p) {
+    snprintf(g_err, sizeof(g_err), "%s: phases[%d] = %d outside 0 .. p - 1 = %d", who, i, (int)phases[i], p - 1);
+    return TMPC_E_ARG;
+  }
+  if (nr < 0 || ng < 0 || nr < ng || (nr > 0 && !J)) {
+    snprintf(g_err, sizeof(g_err), "%s: bad argument (0 <= ng <= nr, the row capacity per stage; non-null J when nr > 0; got ng = %d, nr = %d)", who, ng, nr);
+    return TMPC_E_ARG;
+  }
+  if (!(rank_tol > 0.0) || !(rank_tol < INFINITY)) {
+    snprintf(g_err, sizeof(g_err), "%s: bad argument (finite rank_tol > 0; got rank_tol = %g)", who, rank_tol);
+    return TMPC_E_ARG;
+  }
+  if (nx + mb > LQR_NMAX) {
+    snprintf(g_err, sizeof(g_err), "%s: the LQR recursions handle stage blocks up to nx + nu = %d (got %d)", who, LQR_NMAX, nx + mb);
+    return TMPC_E_UNSUPPORTED;
+  }
+  const long long bytes = (long long)lqr_ctg_lds(nx, mb, nr < 4096 ? nr : 4096).total * (long long)sizeof(double);
+  if (bytes > LQR_LDS_BYTES) {
+    snprintf(g_err, sizeof(g_err), "%s: nx = %d, nu = %d with room for %d rows per stage and a constraint-to-go needs %lld bytes of LDS (limit %d)", who, nx, mb,
+             nr, bytes, LQR_LDS_BYTES);
+    return TMPC_E_UNSUPPORTED;
+  }
+  if (nph > 65535) {
+    snprintf(g_err, sizeof(g_err), "%s: at most 65535 starting phases per call (got %d)", who, nph);
+    return TMPC_E_UNSUPPORTED;
+  }
+  return TMPC_OK;
+}
+
+static int lqr_horizon_launch(int nb, int p, int nx, int mb, int nr, int ng, int N, int nph, const int32_t* dphases, int terminal, const double* A,
+                              const double* B, const double* H, const double* J, const int32_t* ncnt, const double* Pf, double rank_tol, double* K0, double* Pi0,
+                              double* Hn0, int32_t* cnt0, double* Kall, int32_t* cntall, double* info) {
+  const size_t lds_bytes = (size_t)lqr_ctg_lds(nx, mb, nr).total * sizeof(double);
+  HIPCHK(hipFuncSetAttribute((const void*)k_horizon_lqr, hipFuncAttributeMaxDynamicSharedMemorySize, LQR_LDS_BYTES));      // (the same value from every thread and call)
+  int lcw = 0;
+  while ((1 << lcw) < nx + mb) ++lcw;
+  hipLaunchKernelGGL(k_horizon_lqr, dim3(nb, nph), dim3(LQR_NT), lds_bytes, 0, p, nx, mb, nr, ng, lcw, N, (const int*)dphases, terminal, A, B, H,
+                     nr > 0 ? J : nullptr, (const int*)ncnt, Pf, rank_tol, K0, Pi0, Hn0, (int*)cnt0, Kall, (int*)cntall, info);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(0));
+  return TMPC_OK;
+}
+
+static thread_local EigScratch g_lqr_horizon_phases;      // device image of the list of phases
+static thread_local EigScratch g_lqr_horizon_scratch;     // device images of the host entry, kept between calls and grown on demand
+
+int tmpc_horizon_lqr_batch_device(int nb, int p, int nx, int mb, int nr, int ng, int N, int nph, const int32_t* phases, int terminal, const double* A,
+                                  const double* B, const double* H, const double* J, const int32_t* ncnt, const double* Pf, double rank_tol, double* K0,
+                                  double* Pi0, double* Hn0, int32_t* cnt0, double* Kall, int32_t* cntall, double* info) {
+  const int rc = lqr_horizon_check("tmpc_horizon_lqr_batch_device", nb, p, nx, mb, nr, ng, N, nph, phases, terminal, A, B, H, J, rank_tol, K0, Pi0, Hn0, cnt0, info);
+  if (rc != TMPC_OK) return rc;
+  int32_t* dph = nullptr;
+  if (phases) {
+    HIPCHK(g_lqr_horizon_phases.reserve((size_t)nph * sizeof(int32_t)));
+    dph = (int32_t*)g_lqr_horizon_phases.p;
+    HIPCHK(hipMemcpy(dph, phases, (size_t)nph * sizeof(int32_t), hipMemcpyHostToDevice));
+  }
+  return lqr_horizon_launch(nb, p, nx, mb, nr, ng, N, nph, dph, terminal, A, B, H, J, ncnt, Pf, rank_tol, K0, Pi0, Hn0, cnt0, Kall, cntall, info);
+}
+
+int tmpc_horizon_lqr_batch_host(int nb, int p, int nx, int mb, int nr, int ng, int N, int nph, const int32_t* phases, int terminal, const double* A,
+                                const double* B, const double* H, const double* J, const int32_t* ncnt, const double* Pf, double rank_tol, double* K0,
+                                double* Pi0, double* Hn0, int32_t* cnt0, double* Kall, int32_t* cntall, double* info) {
+  const char* who = "tmpc_horizon_lqr_batch_host";
+  const int rc = lqr_horizon_check(who, nb, p, nx, mb, nr, ng, N, nph, phases, terminal, A, B, H, J, rank_tol, K0, Pi0, Hn0, cnt0, info);
+  if (rc != TMPC_OK) return rc;
+  const size_t n = (size_t)nx + mb, st = (size_t)nb * p, sp = (size_t)nb * nph;
+  if (ncnt) for (size_t i = 0; i < st; ++i) if (ncnt[i] < 0 || ncnt[i] > nr - ng) {
+    snprintf(g_err, sizeof(g_err), "%s: ncnt[%zu][%zu] = %d outside 0 .. nr - ng = %d", who, i / p, i % p, (int)ncnt[i], nr - ng);
+    return TMPC_E_ARG;
+  }
+  const size_t cA = st * nx * nx, cB = st * nx * mb, cH = st * n * n, cJ = st * nr * n, cN = (st + 1) / 2;        // int32 arrays are counted in doubles
+  const size_t cK = sp * mb * nx, cP = sp * nx * nx, cI = sp * LQR_CTG_INFO, cC = (sp + 1) / 2, cPh = ((size_t)nph + 1) / 2;
+  const size_t cKa = Kall ? cK * N : 0, cCa = cntall ? (sp * N + 1) / 2 : 0;
+  HIPCHK(g_lqr_horizon_scratch.reserve((2 * cA + cB + cH + cJ + cN + cK + 2 * cP + cI + cC + cPh + cKa + cCa) * 8));
+  double* dA = (double*)g_lqr_horizon_scratch.p; double* dB = dA + cA; double* dH = dB + cB; double* dPf = dH + cH; double* dJ = dPf + cA;      // A | B | H | Pf | J |
+  double* dK = dJ + cJ; double* dPi = dK + cK; double* dHn = dPi + cP; double* dI = dHn + cP; double* dKa = dI + cI;                          // K0 | Pi0 | Hn0 | info | Kall |
+  int32_t* dN = (int32_t*)(dKa + cKa); int32_t* dC = (int32_t*)(dKa + cKa + cN); int32_t* dPh = (int32_t*)(dKa + cKa + cN + cC);           // ncnt | cnt0 | phases | cntall
+  int32_t* dCa = (int32_t*)(dKa + cKa + cN + cC + cPh);
+  HIPCHK(hipMemcpy(dA, A, cA * 8, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dB, B, cB * 8, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dH, H, cH * 8, hipMemcpyHostToDevice));
+  if (cJ) HIPCHK(hipMemcpy(dJ, J, cJ * 8, hipMemcpyHostToDevice));
+  if (ncnt) HIPCHK(hipMemcpy(dN, ncnt, st * sizeof(int32_t), hipMemcpyHostToDevice));
+  if (Pf) HIPCHK(hipMemcpy(dPf, Pf, cA * 8, hipMemcpyHostToDevice));
+  if (phases) HIPCHK(hipMemcpy(dPh, phases, (size_t)nph * sizeof(int32_t), hipMemcpyHostToDevice));
+  const int rl = lqr_horizon_launch(nb, p, nx, mb, nr, ng, N, nph, phases ? dPh : nullptr, terminal, dA, dB, dH, dJ, ncnt ? dN : nullptr, Pf ? dPf : nullptr,
+                                    rank_tol, dK, dPi, dHn, dC, Kall ? dKa : nullptr, cntall ? dCa : nullptr, dI);
+  if (rl != TMPC_OK) return rl;
+  HIPCHK(hipMemcpy(K0, dK, cK * 8, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(Pi0, dPi, cP * 8, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(Hn0, dHn, cP * 8, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(cnt0, dC, sp * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (Kall) HIPCHK(hipMemcpy(Kall, dKa, cKa * 8, hipMemcpyDeviceToHost));
+  if (cntall) HIPCHK(hipMemcpy(cntall, dCa, sp * N * sizeof(int32_t), hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(info, dI, cI * 8, hipMemcpyDeviceToHost));
   return TMPC_OK;
 }

@@ -19,6 +19,17 @@ That recursion serves r_k <= nu rows with an input part of full row rank.  state
 backwards as Hn_k x_k = 0; gains and cost-to-go are returned projected on the feasible subspace, Pz_k = I - Hn_k' Hn_k, where they are unique, and the
 certificate compares the projected gains and the subspaces of the two sides.  An empty feasible subspace ends a problem with status 5.
 
+The controllers a user builds are finite-horizon ones (reference tuner.py:162, pmpc.py:162-281): horizon N, started at whatever phase the plant is in, ended
+by a terminal weight or by x_N = 0.  Their first-order feedback u_0 = -K_0 x_0 is not the periodic gain unless N is long, and the statement to certify is that
+the tracking MPC on Hc and the economic MPC on H give the same K_0 at every phase (the LQ content of closed_loop_tools.check_equivalence):
+
+    horizon_lqr_batch(A, B, H, horizon, terminal='constraint' | 'cost', Pf=None, phases=None, ...)      K_0 of every (problem, starting phase), one backward pass each
+    horizon_lqr(A, B, Q, R, N, horizon, ...)                                                            the reference's calling style
+    horizon_equivalence_batch(A, B, H, Hc, horizon, P=None, ...)                                        max |K_0(H) - K_0(Hc)| per (problem, phase)
+    horizon_equivalence(A, B, Q, R, N, dHc, horizon, ...)                                               the same on what `convexify` takes and returns
+
+(csrc/tmpc_lqr_horizon.h: the stage of the constraint-to-go recursion, so any rows are served; a terminal constraint is that recursion started from Hn_N = I.)
+
 Conventions: stage cost 1/2 [x;u]' H_k [x;u] with H_k = [[Q_k, N_k], [N_k', R_k]] (x block first, the layout of convexify_batch),
 x_{k+1} = A_k x_k + B_k u_k, and u = -K_k x: the sign of scipy.linalg.solve_discrete_are / control.dare.
 There is no CPU path: the recursion runs in the HIP library or the call raises.
@@ -334,4 +345,165 @@ def feedback_equivalence(A, B, Q, R, N, dHc, tol=1e-13, max_sweeps=5000, G=None,
     if state_rows:
         out['cnt'] = [int(c) for c in r['cnt'][0]]; out['cntc'] = [int(c) for c in r['cntc'][0]]
     out['K'] = [r['K'][0, k].copy() for k in range(p)]; out['Kc'] = [r['Kc'][0, k].copy() for k in range(p)]
+    return out
+
+
+# ----------------------------------------------------------------------------- finite horizon
+TERMINAL = {'cost': 0, 'constraint': 1}
+
+
+def _relabel(fn, who, *a):
+    try:
+        return fn(*a)
+    except ValueError as e:
+        raise ValueError(str(e).replace('periodic_lqr_batch', who)) from None
+
+
+def _validate_horizon(who, horizon, terminal, phases, p, rank_tol):
+    """horizon, terminal, phases, rank_tol before any device call -> (N, terminal code, phases as a numpy int32 array or None)."""
+    if isinstance(horizon, bool) or not isinstance(horizon, (int, np.integer)) or int(horizon) < 1:
+        raise ValueError('{}: horizon must be an int >= 1, got {!r}'.format(who, horizon))
+    if not isinstance(terminal, str) or terminal not in TERMINAL:
+        raise ValueError("{}: terminal must be 'constraint' (x_N = 0) or 'cost', got {!r}".format(who, terminal))
+    if isinstance(rank_tol, bool) or not isinstance(rank_tol, (int, float, np.floating)) or not (0.0 < float(rank_tol) < 1.0):
+        raise ValueError('{}: 0 < rank_tol < 1 expected, got {!r}'.format(who, rank_tol))
+    if phases is not None:
+        if _is_torch(phases):
+            phases = phases.cpu().numpy()
+        ph = np.asarray(phases)
+        if ph.ndim != 1 or ph.size < 1 or ph.dtype.kind not in 'iu':
+            raise ValueError('{}: phases must be a non-empty list of ints (None: all p phases), got {!r}'.format(who, phases))
+        if (ph < 0).any() or (ph >= p).any():
+            raise ValueError('{}: phases must lie in 0 .. p - 1 = {}, got {}'.format(who, p - 1, ph.tolist()))
+        phases = np.ascontiguousarray(ph, dtype=np.int32)
+    return int(horizon), TERMINAL[terminal], phases
+
+
+def horizon_lqr_batch(A, B, H, horizon, terminal='constraint', Pf=None, phases=None, J=None, ncnt=None, ng=None, rank_tol=1e-9, return_all=False):
+    """First-order feedback of the horizon-N LQ problems on nb p-periodic models, from every starting phase: for problem b and phase k0 one backward pass
+    j = horizon-1 ... 0 over the stages k = (k0 + j) mod p (horizon may be smaller than, equal to or larger than p), started from the terminal weight
+    Pi_N = Pf[b, (k0 + N) mod p] (Pf [nb,p,nx,nx]; None: zero) and
+
+        terminal='cost':        nothing else;
+        terminal='constraint':  x_N = 0, i.e. the constraint-to-go Hn_N = I (a general terminal operator, the reference's p_operator, is not provided).
+
+    A, B, H, J, ncnt, ng, rank_tol as in periodic_lqr_batch(..., state_rows=True): every stage is the constraint-to-go stage, so any rows are served and J=None
+    is allowed (under a terminal constraint the constraint-to-go is there without rows).  phases: list of starting phases (None: all p, in order).
+    numpy arrays run through the host entry; torch tensors on a GPU through the device entry (torch tensors out, the inputs are not copied).
+
+    Returns dict: K0 [nb,nph,nu,nx] (u_0 = -K0 x_0 for feasible x_0: projected with Pz_0 = I - Hn0' Hn0), Pi0 [nb,nph,nx,nx] (cost-to-go of x_0, projected),
+    Hn0 [nb,nph,nx,nx] (c_0 orthonormal rows, Hn0 x_0 = 0: the x_0 from which the horizon problem is feasible; rows beyond c_0 zero), cnt0 [nb,nph] int32,
+    status [nb,nph] (0 done, 2 singular stage system, 3 non-finite, 5 no feasible subspace: a computed c_j reached nx; 1 and 4 do not occur), feas [nb,nph] =
+    info[..., 7] = max_j max(|(Jx - Ju K_j) Pz_j|, |Hn_{j+1} (A - B K_j) Pz_j|), info [nb,nph,12] (1: N, 2: stages finished, else the slots of the ctg entry),
+    phases (numpy int32).  Where status >= 2: K0, Pi0 NaN, Hn0 zero, cnt0 the count at the failing stage.  One (problem, phase) never affects another.
+    return_all=True adds Kall [nb,nph,N,nu,nx] and cntall [nb,nph,N], the gains and counts of every stage of every pass (large: nb nph N nu nx doubles;
+    NaN / -1 at the stages a failed pass did not finish).  ValueError: shapes, dtypes, horizon < 1, a phase outside 0 .. p-1, terminal;
+    NotImplementedError: (nx, nu, nr) beyond the 160 KB LDS layout of the ctg entry, more than 65535 phases."""
+    who = 'horizon_lqr_batch'
+    use_torch, nb, p, nx, mb = _relabel(_validate, who, A, B, H, (('Pf', Pf, 'A'),))
+    N, term, phases = _validate_horizon(who, horizon, terminal, phases, p, rank_tol)
+    if J is None and (ncnt is not None or ng is not None):
+        raise ValueError('{}: ncnt / ng describe the rows of J, which is None'.format(who))
+    ng_ = 0
+    if J is not None:
+        _, ng_ = _relabel(_validate_rows, who, J, ncnt, ng, use_torch, A, nb, p, nx + mb)
+    A, B, H, Pf, J = (_contig(x, use_torch) for x in (A, B, H, Pf, J))
+    if ncnt is not None:
+        ncnt = ncnt.contiguous() if use_torch else np.ascontiguousarray(ncnt)
+    entry = _lib.horizon_lqr_batch_device if use_torch else _lib.horizon_lqr_batch_host
+    K0, Pi0, Hn0, cnt0, Kall, cntall, info = entry(A, B, H, J, ncnt, ng_, N, phases, term, Pf, rank_tol, bool(return_all))
+    if use_torch:
+        import torch
+        status = info[..., 0].to(torch.int32); feas = info[..., 7].clone()
+    else:
+        status = info[..., 0].astype(np.int32); feas = info[..., 7].copy()
+    out = dict(K0=K0, Pi0=Pi0, Hn0=Hn0, cnt0=cnt0, status=status, feas=feas, info=info, phases=np.arange(p, dtype=np.int32) if phases is None else phases)
+    if return_all:
+        out.update(Kall=Kall, cntall=cntall)
+    return out
+
+
+def horizon_equivalence_batch(A, B, H, Hc, horizon, P=None, terminal='constraint', Pf=None, phases=None, J=None, ncnt=None, ng=None, rank_tol=1e-9):
+    """The finite-horizon certificate: K_0 of the horizon-N problems on H and on Hc (two passes per phase), compared.  Arguments as in horizon_lqr_batch, Hc
+    [nb,p,n,n] and P [nb,p,nx,nx], the `P` of the convexification: Hc_k = H_k + [A_k B_k]' P_{k+1} [A_k B_k] - diag(P_k, 0) (+ J_k' diag(phi_k) J_k, which
+    vanishes on the rows).  The cost of the H problem is that of the Hc problem plus x_0' P_k0 x_0 - x_N' P_{k0+N} x_N, so the two are the same problem when
+    the H side carries the terminal weight Pf + P[(k0 + N) mod p] and the Hc side Pf: that is what is run.  terminal='cost' therefore needs P (ValueError
+    without it: dK0 would measure the mismatch of the terminal weights, O(1) at N = 1 and fading with N).  With terminal='constraint' x_N = 0 makes the
+    terminal weight irrelevant in exact arithmetic and P is optional; when given it is used, because it keeps S of the H side convex on the way.
+
+    Returns dict of numpy arrays [nb,nph]: dK0 = max|K0(H) - K0(Hc)| on the projected gains, dK0_rel = dK0 / max(1, max|K0(Hc)|), subspace_diff =
+    max|Pz_0(H side) - Pz_0(Hc side)| (the subspaces depend on A, B and the rows only: rounding level, and dK0 means nothing where it is not), cnt0_H,
+    cnt0_Hc, status_H, status_Hc, feas_H, feas_Hc; and K0, K0c as the entries returned them.  dK0 is NaN where a side ended with status >= 2.  Not covered: an
+    empty feasible subspace (status 5), a general terminal operator, shapes beyond the LDS layout."""
+    who = 'horizon_equivalence_batch'
+    use_torch, nb, p, nx, mb = _relabel(_validate, who, A, B, H, (('Hc', Hc, 'H'), ('P', P, 'A'), ('Pf', Pf, 'A')))
+    _validate_horizon(who, horizon, terminal, phases, p, rank_tol)
+    if terminal == 'cost' and P is None:
+        raise ValueError("{}: terminal='cost' needs P: the H side must carry the terminal weight Pf + P[(k0 + N) mod p] for the two problems to be "
+                         'the same'.format(who))
+    PfH = Pf if P is None else (P if Pf is None else Pf + P)
+    kw = dict(terminal=terminal, phases=phases, J=J, ncnt=ncnt, ng=ng, rank_tol=rank_tol)
+    rH = horizon_lqr_batch(A, B, H, horizon, Pf=PfH, **kw)
+    rC = horizon_lqr_batch(A, B, Hc, horizon, Pf=Pf, **kw)
+    nph = rH['K0'].shape[1]
+    host = (lambda x: x.cpu().numpy()) if use_torch else (lambda x: np.array(x))
+    if use_torch:
+        import torch
+        d = (rH['K0'] - rC['K0']).abs().reshape(nb, nph, -1).max(dim=2).values; kmax = rC['K0'].abs().reshape(nb, nph, -1).max(dim=2).values
+        sd = (torch.einsum('bkji,bkjl->bkil', rH['Hn0'], rH['Hn0']) - torch.einsum('bkji,bkjl->bkil', rC['Hn0'], rC['Hn0'])).abs().reshape(nb, nph, -1).max(dim=2).values
+    else:
+        d = np.abs(rH['K0'] - rC['K0']).reshape(nb, nph, -1).max(axis=2); kmax = np.abs(rC['K0']).reshape(nb, nph, -1).max(axis=2)
+        sd = np.abs(np.einsum('bkji,bkjl->bkil', rH['Hn0'], rH['Hn0']) - np.einsum('bkji,bkjl->bkil', rC['Hn0'], rC['Hn0'])).reshape(nb, nph, -1).max(axis=2)
+    dK0, kmax = host(d), host(kmax)
+    with np.errstate(invalid='ignore'):
+        rel = dK0 / np.maximum(1.0, kmax)
+    return dict(dK0=dK0, dK0_rel=rel, subspace_diff=host(sd), cnt0_H=host(rH['cnt0']), cnt0_Hc=host(rC['cnt0']), status_H=host(rH['status']),
+                status_Hc=host(rC['status']), feas_H=host(rH['feas']), feas_Hc=host(rC['feas']), K0=rH['K0'], K0c=rC['K0'], phases=rH['phases'])
+
+
+def _stack_weights(X, p, nx, name):
+    """A single (nx, nx) matrix or a list of p of them (None passes through) -> [1,p,nx,nx]."""
+    if X is None:
+        return None
+    Xs = [_to_array(x) for x in X] if isinstance(X, (list, tuple)) else [_to_array(X)] * p
+    if len(Xs) != p or any(x.shape != (nx, nx) for x in Xs):
+        raise ValueError('horizon_lqr: {} must be one (nx, nx) matrix or a list of p = {} of them'.format(name, p))
+    return np.ascontiguousarray(np.stack(Xs)[None], dtype=np.float64)
+
+
+def horizon_lqr(A, B, Q, R, N, horizon, terminal='constraint', Pf=None, phases=None, G=None, C=None, rank_tol=1e-9):
+    """K_0 of one model in the reference's calling style (N is the cross term, as in periodic_lqr; the horizon is `horizon`): A, B, Q, R, N single matrices
+    (p = 1) or lists of length p, G, C the rows as `convexify` takes them, Pf one (nx, nx) matrix or a list of p -> (K0_list, Pi0_list, cnt0_list), one entry
+    per starting phase (phases=None: all p): the projected gain (nu x nx, u_0 = -K_0 x_0 on the feasible x_0), the projected cost-to-go, the count c_0.
+    RuntimeError when a pass did not finish (status of horizon_lqr_batch != 0)."""
+    As, Bs, Hs, rows = _stack_stages(A, B, Q, R, N, G, C)
+    r = horizon_lqr_batch(As, Bs, Hs, horizon, terminal=terminal, Pf=_stack_weights(Pf, As.shape[1], As.shape[2], 'Pf'), phases=phases, rank_tol=rank_tol, **rows)
+    bad = np.nonzero(r['status'][0])[0]
+    if bad.size:
+        st = int(r['status'][0, bad[0]])
+        raise RuntimeError('horizon_lqr: the pass from phase {} ended with status {} ({}) after {} of {} stages'.format(
+            int(r['phases'][bad[0]]), st, STATUS_NAMES.get(st), int(r['info'][0, bad[0], 2]), int(horizon)))
+    nph = r['K0'].shape[1]
+    return [r['K0'][0, i].copy() for i in range(nph)], [r['Pi0'][0, i].copy() for i in range(nph)], [int(c) for c in r['cnt0'][0]]
+
+
+def horizon_equivalence(A, B, Q, R, N, dHc, horizon, P=None, terminal='constraint', Pf=None, phases=None, G=None, C=None, rank_tol=1e-9):
+    """horizon_equivalence_batch for one model in the calling style of `convexify`: dHc is its first return value (list of p supplements, Hc_k = H_k + dHc_k),
+    P its second (list of p matrices, or None), G, C the rows it was called with.  Returns the dict of the batched call with lists over the starting phases
+    (floats for dK0, dK0_rel, subspace_diff, feas_H, feas_Hc; ints for cnt0_H, cnt0_Hc, status_H, status_Hc; matrices for K0, K0c)."""
+    As, Bs, Hs, rows = _stack_stages(A, B, Q, R, N, G, C)
+    dH = np.stack([_to_array(d) for d in (dHc if isinstance(dHc, (list, tuple)) else [dHc])])[None]
+    if dH.shape != Hs.shape:
+        raise ValueError('horizon_equivalence: dHc must hold p matrices (nx+nu, nx+nu), got {}'.format(dH.shape[1:]))
+    p, nx = As.shape[1], As.shape[2]
+    r = horizon_equivalence_batch(As, Bs, Hs, Hs + dH, horizon, P=_stack_weights(P, p, nx, 'P'), terminal=terminal, Pf=_stack_weights(Pf, p, nx, 'Pf'),
+                                  phases=phases, rank_tol=rank_tol, **rows)
+    out = {}
+    for k, v in r.items():
+        if k in ('K0', 'K0c'):
+            out[k] = [v[0, i].copy() for i in range(v.shape[1])]
+        elif k == 'phases':
+            out[k] = [int(x) for x in v]
+        else:
+            out[k] = [(int(x) if k.startswith(('cnt', 'status')) else float(x)) for x in v[0]]
     return out
