@@ -367,6 +367,32 @@ int tmpc_horizon_lqr_batch_device(int nb, int p, int nx, int mb, int nr, int ng,
                                   const double* B, const double* H, const double* J, const int32_t* ncnt, const double* Pf, double rank_tol, double* K0,
                                   double* Pi0, double* Hn0, int32_t* cnt0, double* Kall, int32_t* cntall, double* info);
 
+/* Closed-loop rollouts of a phase-indexed feedback law u = -K_k x on the p-periodic model (tmpc_closed_loop.h; the LQ content of the reference's
+ * closed_loop_tools.closed_loop_sim: the first-order loop -- changes of the active set and the nonlinear plant are not simulated).  ns initial states per
+ * problem walk t = 0 .. T-1 over the stages k = (k0 + t) mod p, one launch for the whole batch:
+ *     u_t = -K_k x_t,  z_t = [x_t; u_t],  l_t = 1/2 z_t' H_k z_t,  lc_t = 1/2 z_t' Hc_k z_t,  rowres_t = max|J_k z_t| over the first r_k = ng + ncnt_k rows,
+ *     subres_t = max|Hn_k x_t| over all nx rows (rows beyond c_k are zero),  x_{t+1} = A_k x_t + B_k u_t.
+ * Inputs: A, B as above, K [nb][p][mb][nx] (any phase-indexed law: the K of the periodic entries, the K0 of the horizon entries over all phases),
+ * X0 [nb][ns][nx]; optional (NULL: absent) H, Hc [nb][p][n][n], J [nb][p][nr][n] with ncnt int32 [nb][p] (NULL: ng rows at every stage; J NULL exactly when
+ * nr = 0), Hn [nb][p][nx][nx].  Outputs, TIME-MAJOR (the stores of a step are contiguous; the Python layer returns permuted views): optional X [nb][T+1][ns][nx],
+ * U [nb][T][ns][mb], l, lc, rowres, subres [nb][T][ns] (each needs its input), sums [nb][ns][2] = (sum_t l_t, sum_t lc_t) added in the order of t (NaN for an
+ * absent cost); required XT [nb][ns][nx] = x_T and info [nb][ns][4]:
+ *   [0] status: 0 done, 3 non-finite (a non-finite value met in A, B, K, X0, H, Hc, J or Hn, or overflow during the rollout); there are no other statuses.
+ *       Such a state stops at the first step t that produced a non-finite u_t, l_t, lc_t, rowres_t, subres_t or x_{t+1} (step 0 for a non-finite x_0): its
+ *       entries of U, l, lc, rowres, subres from t on, of X from t + 1 on, XT and sums are NaN.  One state never affects another;
+ *   [1] steps finished (T when status = 0), [2] max |x_t| over t = 0 .. steps finished (NaN for a non-finite x_0), [3] reserved (0).
+ * The numbers of a state do not depend on ns or on the other states of the call (fixed order of accumulation), and the host entry stages through device
+ * buffers and runs the same kernel.  TMPC_E_ARG: nb, p, nx, mb, ns, T < 1, k0 outside 0 .. p-1, nr < ng, J / nr mismatch, ncnt without J, an output without
+ * its input, NULL A, B, K, X0, XT, info, (host entry) ncnt outside 0 .. nr - ng.  TMPC_E_UNSUPPORTED (before the device is touched): nx + mb > TMPC_LQR_NMAX,
+ * (nx, mb, nr) beyond 160 KB of LDS for a tile of one state (every n <= 64 fits with the nr the ctg entry serves), more than 65535 tiles of states. */
+#define TMPC_CLOSED_LOOP_INFO 4
+int tmpc_closed_loop_batch_host(int nb, int p, int nx, int mb, int nr, int ng, int ns, int T, int k0, const double* A, const double* B, const double* K,
+                                const double* X0, const double* H, const double* Hc, const double* J, const int32_t* ncnt, const double* Hn, double* X,
+                                double* U, double* l, double* lc, double* rowres, double* subres, double* sums, double* XT, double* info);
+int tmpc_closed_loop_batch_device(int nb, int p, int nx, int mb, int nr, int ng, int ns, int T, int k0, const double* A, const double* B, const double* K,
+                                  const double* X0, const double* H, const double* Hc, const double* J, const int32_t* ncnt, const double* Hn, double* X,
+                                  double* U, double* l, double* lc, double* rowres, double* subres, double* sums, double* XT, double* info);
+
 /* Accumulated hipEvent timings since the last call (ms) when TMPC_FLAG_PROFILE is set, 16 doubles:
  * out[0] stage_pre+ctrl, [1] schur assembly, [2] block factorisation (all kernels of tmpc_cr.h's factor phase), [3] predictor
  * pass, [4] corrector pass + update, [5] number of factorisation phases (= IPM iterations of the chunks), [6] total ms of the

@@ -25,6 +25,7 @@ EXPORTS = [
     'tmpc_tracking_reference_host', 'tmpc_eig_scan_host', 'tmpc_get_profile', 'tmpc_get_trace', 'tmpc_get_dual_host', 'tmpc_get_dual_con_host', 'tmpc_pack_sensitivities_host', 'tmpc_eig_clip_host',
     'tmpc_periodic_lqr_batch_host', 'tmpc_periodic_lqr_batch_device', 'tmpc_periodic_lqr_rows_batch_host', 'tmpc_periodic_lqr_rows_batch_device',
     'tmpc_periodic_lqr_ctg_batch_host', 'tmpc_periodic_lqr_ctg_batch_device', 'tmpc_horizon_lqr_batch_host', 'tmpc_horizon_lqr_batch_device',
+    'tmpc_closed_loop_batch_host', 'tmpc_closed_loop_batch_device',
     'tmpc_last_error', 'tmpc_version',
 ]
 # ... and in include/tunempc_hip_debug.h (unit-test / diagnostic entries)
@@ -141,6 +142,10 @@ def load_library():
     lib.tmpc_horizon_lqr_batch_host.argtypes = [C.c_int] * 8 + [ip, C.c_int] + [dp] * 4 + [ip, dp, C.c_double] + [dp] * 3 + [ip, dp, ip, dp]
     lib.tmpc_horizon_lqr_batch_device.restype = C.c_int
     lib.tmpc_horizon_lqr_batch_device.argtypes = [C.c_int] * 8 + [ip, C.c_int] + [vp] * 6 + [C.c_double] + [vp] * 7
+    lib.tmpc_closed_loop_batch_host.restype = C.c_int
+    lib.tmpc_closed_loop_batch_host.argtypes = [C.c_int] * 9 + [dp] * 7 + [ip] + [dp] * 10
+    lib.tmpc_closed_loop_batch_device.restype = C.c_int
+    lib.tmpc_closed_loop_batch_device.argtypes = [C.c_int] * 9 + [vp] * 18
     lib.tmpc_get_profile.restype = C.c_int
     lib.tmpc_get_profile.argtypes = [vp, dp]
     lib.tmpc_get_trace.restype = C.c_int
@@ -189,6 +194,7 @@ E_NOCONV = -6
 E_UNSUPPORTED = -2
 LQR_INFO_STRIDE = 8
 LQR_CTG_INFO_STRIDE = 12
+CLOSED_LOOP_INFO_STRIDE = 4
 
 
 def _check(lib, rc, what):
@@ -790,6 +796,63 @@ def horizon_lqr_batch_device(A, B, H, J, ncnt, ng, N, phases, terminal, Pf, rank
         raise ValueError(lib.tmpc_last_error().decode())
     _check_lqr(lib, rc, 'tmpc_horizon_lqr_batch_device')
     return K0, Pi0, Hn0, cnt0, Kall, cntall, info
+
+
+def _closed_loop_views(X, U, l, lc, rowres, subres, sums, XT, info, tr4, tr3):
+    """The outputs of the closed-loop entries (time-major in memory) in the layout of closed_loop_batch: permuted views, nothing is copied."""
+    return dict(X=None if X is None else tr4(X), U=None if U is None else tr4(U), l=None if l is None else tr3(l), lc=None if lc is None else tr3(lc),
+                rowres=None if rowres is None else tr3(rowres), subres=None if subres is None else tr3(subres), sums=sums, XT=XT, info=info)
+
+
+def closed_loop_batch_host(A, B, K, X0, H, Hc, J, ncnt, ng, Hn, T, k0, return_traj):
+    """tmpc_closed_loop_batch_host on validated, contiguous numpy arrays (fp64; H, Hc, J, Hn None or arrays; ncnt int32 or None) -> dict X [nb,ns,T+1,nx],
+    U [nb,ns,T,nu] (None without return_traj), l, lc, rowres, subres [nb,ns,T] (None without their input), sums [nb,ns,2] (None without a cost), XT [nb,ns,nx],
+    info [nb,ns,4].  The library stores the trajectories time-major: X, U and the per-step scalars are permuted views of those arrays."""
+    lib = load_library()
+    nb, p, nx, mb = B.shape
+    ns, T = X0.shape[1], int(T)
+    nr = 0 if J is None else J.shape[2]
+    X = np.empty((nb, T + 1, ns, nx)) if return_traj else None
+    U = np.empty((nb, T, ns, mb)) if return_traj else None
+    step = lambda have: np.empty((nb, T, ns)) if have is not None else None
+    l, lc, rowres, subres = step(H), step(Hc), step(J if nr else None), step(Hn)
+    sums = np.empty((nb, ns, 2)) if (H is not None or Hc is not None) else None
+    XT = np.empty((nb, ns, nx)); info = np.zeros((nb, ns, CLOSED_LOOP_INFO_STRIDE))
+    rc = lib.tmpc_closed_loop_batch_host(nb, p, nx, mb, nr, int(ng), ns, T, int(k0), _dptr(A), _dptr(B), _dptr(K), _dptr(X0), _dptr(H), _dptr(Hc),
+                                         _dptr(J) if nr else None, _iptr(ncnt) if nr else None, _dptr(Hn), _dptr(X), _dptr(U), _dptr(l), _dptr(lc), _dptr(rowres),
+                                         _dptr(subres), _dptr(sums), _dptr(XT), _dptr(info))
+    if rc == -1:      # TMPC_E_ARG: the library's message names the argument
+        raise ValueError(lib.tmpc_last_error().decode())
+    _check_lqr(lib, rc, 'tmpc_closed_loop_batch_host')
+    return _closed_loop_views(X, U, l, lc, rowres, subres, sums, XT, info, lambda a: a.transpose(0, 2, 1, 3), lambda a: a.transpose(0, 2, 1))
+
+
+def closed_loop_batch_device(A, B, K, X0, H, Hc, J, ncnt, ng, Hn, T, k0, return_traj):
+    """tmpc_closed_loop_batch_device on validated, contiguous torch tensors of one GPU (fp64; ncnt int32 or None) -> the dict of closed_loop_batch_host with
+    torch tensors; the inputs never leave HBM."""
+    import torch
+    lib = load_library()
+    nb, p, nx, mb = B.shape
+    ns, T = X0.shape[1], int(T)
+    nr = 0 if J is None else J.shape[2]
+    dev = A.device
+    f64 = lambda *sh: torch.empty(sh, dtype=torch.float64, device=dev)
+    X = f64(nb, T + 1, ns, nx) if return_traj else None
+    U = f64(nb, T, ns, mb) if return_traj else None
+    step = lambda have: f64(nb, T, ns) if have is not None else None
+    l, lc, rowres, subres = step(H), step(Hc), step(J if nr else None), step(Hn)
+    sums = f64(nb, ns, 2) if (H is not None or Hc is not None) else None
+    XT = f64(nb, ns, nx); info = torch.zeros((nb, ns, CLOSED_LOOP_INFO_STRIDE), dtype=torch.float64, device=dev)
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+    with torch.cuda.device(dev):
+        torch.cuda.current_stream(dev).synchronize()      # the entry runs on the null stream: the inputs must be complete
+        rc = lib.tmpc_closed_loop_batch_device(nb, p, nx, mb, nr, int(ng), ns, T, int(k0), ptr(A), ptr(B), ptr(K), ptr(X0), ptr(H), ptr(Hc), ptr(J) if nr else None,
+                                               ptr(ncnt) if nr else None, ptr(Hn), ptr(X), ptr(U), ptr(l), ptr(lc), ptr(rowres), ptr(subres), ptr(sums), ptr(XT),
+                                               ptr(info))
+    if rc == -1:
+        raise ValueError(lib.tmpc_last_error().decode())
+    _check_lqr(lib, rc, 'tmpc_closed_loop_batch_device')
+    return _closed_loop_views(X, U, l, lc, rowres, subres, sums, XT, info, lambda a: a.permute(0, 2, 1, 3), lambda a: a.permute(0, 2, 1))
 
 
 def cr_schedule(p):

@@ -33,6 +33,7 @@
 #include "tmpc_lqr_rows.h"
 #include "tmpc_lqr_ctg.h"
 #include "tmpc_lqr_horizon.h"
+#include "tmpc_closed_loop.h"
 #include "tmpc_dd.h"
 #include "tmpc_big.h"
 
@@ -2054,6 +2055,116 @@ int tmpc_horizon_lqr_batch_host(int nb, int p, int nx, int mb, int nr, int ng, i
   HIPCHK(hipMemcpy(cnt0, dC, sp * sizeof(int32_t), hipMemcpyDeviceToHost));
   if (Kall) HIPCHK(hipMemcpy(Kall, dKa, cKa * 8, hipMemcpyDeviceToHost));
   if (cntall) HIPCHK(hipMemcpy(cntall, dCa, sp * N * sizeof(int32_t), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(info, dI, cI * 8, hipMemcpyDeviceToHost));
+  return TMPC_OK;
+}
+
+// Closed-loop rollouts (tmpc_closed_loop.h): one workgroup per (problem, tile of TS initial states) walks the T steps with the tile in LDS.
+static_assert(CL_INFO == TMPC_CLOSED_LOOP_INFO, "tunempc_hip.h: info stride of the closed-loop entries");
+
+static int closed_loop_check(const char* who, int nb, int p, int nx, int mb, int nr, int ng, int ns, int T, int k0, const void* A, const void* B, const void* K,
+                             const void* X0, const void* H, const void* Hc, const void* J, const void* ncnt, const void* Hn, const void* l, const void* lc,
+                             const void* rowres, const void* subres, const void* sums, const void* XT, const void* info) {
+  if (nb < 1 || p < 1 || nx < 1 || mb < 1 || ns < 1 || !A || !B || !K || !X0 || !XT || !info) {
+    snprintf(g_err, sizeof(g_err), "%s: bad argument (nb, p, nx, nu, ns >= 1, non-null A, B, K, X0, XT, info; got ns = %d)", who, ns);
+    return TMPC_E_ARG;
+  }
+  if (T < 1 || k0 < 0 || k0 >= p) {
+    snprintf(g_err, sizeof(g_err), "%s: bad argument (T >= 1 steps, starting phase k0 in 0 .. p - 1 = %d; got T = %d, k0 = %d)", who, p - 1, T, k0);
+    return TMPC_E_ARG;
+  }
+  if (nr < 0 || ng < 0 || nr < ng || ((nr > 0) != (J != nullptr)) || (ncnt && !J)) {
+    snprintf(g_err, sizeof(g_err), "%s: bad argument (0 <= ng <= nr, the row capacity per stage; J non-null exactly when nr > 0; ncnt only with J; got ng = %d, "
+             "nr = %d)", who, ng, nr);
+    return TMPC_E_ARG;
+  }
+  if ((l && !H) || (lc && !Hc) || (rowres && !J) || (subres && !Hn) || (sums && !H && !Hc)) {
+    snprintf(g_err, sizeof(g_err), "%s: bad argument (an output without its input: l needs H, lc Hc, rowres J, subres Hn, sums H or Hc)", who);
+    return TMPC_E_ARG;
+  }
+  if (nx + mb > LQR_NMAX) {
+    snprintf(g_err, sizeof(g_err), "%s: the closed-loop rollout handles stage blocks up to nx + nu = %d (got %d)", who, LQR_NMAX, nx + mb);
+    return TMPC_E_UNSUPPORTED;
+  }
+  const ClosedLoopLds L = closed_loop_lds(nx, mb, nr < 4096 ? nr : 4096);
+  const long long bytes = (long long)L.total * (long long)sizeof(double);
+  if (L.ts < 1 || bytes > LQR_LDS_BYTES) {
+    snprintf(g_err, sizeof(g_err), "%s: nx = %d, nu = %d with room for %d rows per stage needs %lld bytes of LDS for a single state (limit %d)", who, nx, mb, nr,
+             bytes, LQR_LDS_BYTES);
+    return TMPC_E_UNSUPPORTED;
+  }
+  if ((ns + L.ts - 1) / L.ts > 65535) {
+    snprintf(g_err, sizeof(g_err), "%s: at most %d initial states per call at this shape (got %d)", who, 65535 * L.ts, ns);
+    return TMPC_E_UNSUPPORTED;
+  }
+  return TMPC_OK;
+}
+
+static int closed_loop_launch(int nb, int p, int nx, int mb, int nr, int ng, int ns, int T, int k0, const double* A, const double* B, const double* K,
+                              const double* X0, const double* H, const double* Hc, const double* J, const int32_t* ncnt, const double* Hn, double* X, double* U,
+                              double* l, double* lc, double* rowres, double* subres, double* sums, double* XT, double* info) {
+  const ClosedLoopLds L = closed_loop_lds(nx, mb, nr);
+  const size_t lds_bytes = (size_t)L.total * sizeof(double);
+  HIPCHK(hipFuncSetAttribute((const void*)k_closed_loop, hipFuncAttributeMaxDynamicSharedMemorySize, LQR_LDS_BYTES));      // (the same value from every thread and call)
+  hipLaunchKernelGGL(k_closed_loop, dim3(nb, (ns + L.ts - 1) / L.ts), dim3(LQR_NT), lds_bytes, 0, p, nx, mb, nr, ng, ns, T, k0, A, B, K, X0, H, Hc, J,
+                     (const int*)ncnt, Hn, X, U, l, lc, rowres, subres, sums, XT, info);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(0));
+  return TMPC_OK;
+}
+
+int tmpc_closed_loop_batch_device(int nb, int p, int nx, int mb, int nr, int ng, int ns, int T, int k0, const double* A, const double* B, const double* K,
+                                  const double* X0, const double* H, const double* Hc, const double* J, const int32_t* ncnt, const double* Hn, double* X,
+                                  double* U, double* l, double* lc, double* rowres, double* subres, double* sums, double* XT, double* info) {
+  const int rc = closed_loop_check("tmpc_closed_loop_batch_device", nb, p, nx, mb, nr, ng, ns, T, k0, A, B, K, X0, H, Hc, J, ncnt, Hn, l, lc, rowres, subres,
+                                   sums, XT, info);
+  if (rc != TMPC_OK) return rc;
+  return closed_loop_launch(nb, p, nx, mb, nr, ng, ns, T, k0, A, B, K, X0, H, Hc, J, ncnt, Hn, X, U, l, lc, rowres, subres, sums, XT, info);
+}
+
+static thread_local EigScratch g_closed_loop_scratch;      // device images of the host entry, kept between calls and grown on demand
+
+int tmpc_closed_loop_batch_host(int nb, int p, int nx, int mb, int nr, int ng, int ns, int T, int k0, const double* A, const double* B, const double* K,
+                                const double* X0, const double* H, const double* Hc, const double* J, const int32_t* ncnt, const double* Hn, double* X,
+                                double* U, double* l, double* lc, double* rowres, double* subres, double* sums, double* XT, double* info) {
+  const char* who = "tmpc_closed_loop_batch_host";
+  const int rc = closed_loop_check(who, nb, p, nx, mb, nr, ng, ns, T, k0, A, B, K, X0, H, Hc, J, ncnt, Hn, l, lc, rowres, subres, sums, XT, info);
+  if (rc != TMPC_OK) return rc;
+  const size_t n = (size_t)nx + mb, st = (size_t)nb * p, sn = (size_t)nb * ns;
+  if (ncnt) for (size_t i = 0; i < st; ++i) if (ncnt[i] < 0 || ncnt[i] > nr - ng) {
+    snprintf(g_err, sizeof(g_err), "%s: ncnt[%zu][%zu] = %d outside 0 .. nr - ng = %d", who, i / p, i % p, (int)ncnt[i], nr - ng);
+    return TMPC_E_ARG;
+  }
+  const size_t cA = st * nx * nx, cB = st * nx * mb, cH = H ? st * n * n : 0, cHc = Hc ? st * n * n : 0, cJ = J ? st * nr * n : 0, cHn = Hn ? cA : 0;
+  const size_t cN = ncnt ? (st + 1) / 2 : 0;                      // int32, counted in doubles
+  const size_t c0 = sn * nx, cI = sn * CL_INFO, cS = sn * T, cX = X ? sn * (T + 1) * nx : 0, cU = U ? sn * T * mb : 0;
+  const size_t cl = l ? cS : 0, clc = lc ? cS : 0, cr = rowres ? cS : 0, cs = subres ? cS : 0, cSum = sums ? sn * 2 : 0;
+  HIPCHK(g_closed_loop_scratch.reserve((cA + 2 * cB + 2 * c0 + cH + cHc + cJ + cHn + cN + cI + cX + cU + cl + clc + cr + cs + cSum) * 8));
+  double* dA = (double*)g_closed_loop_scratch.p; double* dB = dA + cA; double* dK = dB + cB; double* d0 = dK + cB; double* dH = d0 + c0;      // A | B | K | X0 | H |
+  double* dHc = dH + cH; double* dJ = dHc + cHc; double* dHn = dJ + cJ; double* dXT = dHn + cHn; double* dI = dXT + c0; double* dX = dI + cI;      // Hc | J | Hn | XT | info | X |
+  double* dU = dX + cX; double* dl = dU + cU; double* dlc = dl + cl; double* dr = dlc + clc; double* ds = dr + cr; double* dSum = ds + cs;        // U | l | lc | rowres | subres | sums |
+  int32_t* dN = (int32_t*)(dSum + cSum);                                                                                                          // ncnt
+  HIPCHK(hipMemcpy(dA, A, cA * 8, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dB, B, cB * 8, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dK, K, cB * 8, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(d0, X0, c0 * 8, hipMemcpyHostToDevice));
+  if (H) HIPCHK(hipMemcpy(dH, H, cH * 8, hipMemcpyHostToDevice));
+  if (Hc) HIPCHK(hipMemcpy(dHc, Hc, cHc * 8, hipMemcpyHostToDevice));
+  if (J) HIPCHK(hipMemcpy(dJ, J, cJ * 8, hipMemcpyHostToDevice));
+  if (Hn) HIPCHK(hipMemcpy(dHn, Hn, cHn * 8, hipMemcpyHostToDevice));
+  if (ncnt) HIPCHK(hipMemcpy(dN, ncnt, st * sizeof(int32_t), hipMemcpyHostToDevice));
+  const int rl = closed_loop_launch(nb, p, nx, mb, nr, ng, ns, T, k0, dA, dB, dK, d0, H ? dH : nullptr, Hc ? dHc : nullptr, J ? dJ : nullptr,
+                                    ncnt ? dN : nullptr, Hn ? dHn : nullptr, X ? dX : nullptr, U ? dU : nullptr, l ? dl : nullptr, lc ? dlc : nullptr,
+                                    rowres ? dr : nullptr, subres ? ds : nullptr, sums ? dSum : nullptr, dXT, dI);
+  if (rl != TMPC_OK) return rl;
+  if (X) HIPCHK(hipMemcpy(X, dX, cX * 8, hipMemcpyDeviceToHost));
+  if (U) HIPCHK(hipMemcpy(U, dU, cU * 8, hipMemcpyDeviceToHost));
+  if (l) HIPCHK(hipMemcpy(l, dl, cS * 8, hipMemcpyDeviceToHost));
+  if (lc) HIPCHK(hipMemcpy(lc, dlc, cS * 8, hipMemcpyDeviceToHost));
+  if (rowres) HIPCHK(hipMemcpy(rowres, dr, cS * 8, hipMemcpyDeviceToHost));
+  if (subres) HIPCHK(hipMemcpy(subres, ds, cS * 8, hipMemcpyDeviceToHost));
+  if (sums) HIPCHK(hipMemcpy(sums, dSum, cSum * 8, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(XT, dXT, c0 * 8, hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(info, dI, cI * 8, hipMemcpyDeviceToHost));
   return TMPC_OK;
 }
