@@ -368,7 +368,7 @@ int tmpc_horizon_lqr_batch_device(int nb, int p, int nx, int mb, int nr, int ng,
                                   double* Pi0, double* Hn0, int32_t* cnt0, double* Kall, int32_t* cntall, double* info);
 
 /* Closed-loop rollouts of a phase-indexed feedback law u = -K_k x on the p-periodic model (tmpc_closed_loop.h; the LQ content of the reference's
- * closed_loop_tools.closed_loop_sim: the first-order loop -- changes of the active set and the nonlinear plant are not simulated).  ns initial states per
+ * closed_loop_tools.closed_loop_sim: the first-order loop -- the active set is fixed (its changes: tmpc_mpc_qp_batch_*), the nonlinear plant is not simulated).  ns initial states per
  * problem walk t = 0 .. T-1 over the stages k = (k0 + t) mod p, one launch for the whole batch:
  *     u_t = -K_k x_t,  z_t = [x_t; u_t],  l_t = 1/2 z_t' H_k z_t,  lc_t = 1/2 z_t' Hc_k z_t,  rowres_t = max|J_k z_t| over the first r_k = ng + ncnt_k rows,
  *     subres_t = max|Hn_k x_t| over all nx rows (rows beyond c_k are zero),  x_{t+1} = A_k x_t + B_k u_t.
@@ -392,6 +392,41 @@ int tmpc_closed_loop_batch_host(int nb, int p, int nx, int mb, int nr, int ng, i
 int tmpc_closed_loop_batch_device(int nb, int p, int nx, int mb, int nr, int ng, int ns, int T, int k0, const double* A, const double* B, const double* K,
                                   const double* X0, const double* H, const double* Hc, const double* J, const int32_t* ncnt, const double* Hn, double* X,
                                   double* U, double* l, double* lc, double* rowres, double* subres, double* sums, double* XT, double* info);
+
+/* The inequality-constrained tracking-MPC step and its receding-horizon loop on the p-periodic linear model (tmpc_mpc_qp.h; the reference's pmpc.py with
+ * h(x, u) >= 0 at every stage, as closed_loop_tools.check_equivalence and closed_loop_sim exercise it): ns initial deviations per problem, for each the QP
+ *     min  sum_{j<N} (1/2 z_j' H_k z_j + q_k' z_j) + 1/2 x_N' Pf_{k_N} x_N,   z_j = [x_j; u_j],   k = k_j = (k0 + j) mod p,
+ *     s.t. x_{j+1} = A_k x_j + B_k u_j,  x_0 given,   D_k z_j <= d_k (first ndcnt_k rows of the stage),   j = 0 .. N-1,
+ * solved at the steps t = 0 .. T-1 from the phase (k0 + t) mod p; u_0 is applied and x <- A_k x + B_k u_0 (the linear plant), one launch for the whole batch.
+ * Not served (there are no arguments for them): equality rows J, the terminal constraint x_N = 0, slack penalties, warm starts between steps, the nonlinear plant.
+ * Method: primal-dual interior point with Mehrotra's predictor-corrector, started infeasible, the Newton system solved by a Riccati pass with a Cholesky
+ * factorisation per stage; the stop rule is r_p <= tol, r_d <= tol, mu <= 1e-3 tol max(1, max lam), residuals relative to the scale of the problem (stated
+ * in tmpc_mpc_qp.h and in tests/mpc_qp_reference.py).  H is used as (H + H') / 2, likewise Pf.
+ * Inputs: A, B, H as above; optional (NULL: zero) q [nb][p][n], Pf [nb][p][nx][nx]; D [nb][p][nd][n], d [nb][p][nd] (both NULL exactly when nd = 0: the plain
+ * horizon-N LQ problem), ndcnt int32 [nb][p] (NULL: all nd rows); X0 [nb][ns][nx]; tol > 0, max_iter >= 1 (the reference's defaults: 1e-10, 60).
+ * Outputs: required U0 [nb][ns][mb] (the first input of step 0), XT [nb][ns][nx] = x_T, info [nb][ns][8]; optional (NULL: not written), the logs TIME-MAJOR as
+ * in the closed-loop entry: X [nb][T+1][ns][nx], U [nb][T][ns][mb], iters, nact int32 [nb][T][ns] (iterations of the step; rows of stage 0 with lam > s),
+ * hres [nb][T][ns] = max(D z - d) of the applied step (-inf at a stage without rows); and the open-loop solution of the QP of step 0: Xol [nb][ns][N+1][nx],
+ * Uol [nb][ns][N][mb], Lam [nb][ns][N][nd] (rows beyond ndcnt zero).  info:
+ *   [0] status: 0 converged at every step; 1 max_iter reached at some step (an infeasible instance ends here); 2 a stage matrix S = R + B' Pi B + ... not positive
+ *       definite (the problem is not convex along the path, e.g. an indefinite H); 3 non-finite.  Such an instance stops at the step t that met it: U, hres from
+ *       t on, X from t + 1 on, XT (and U0, Xol, Uol, Lam when t = 0) are NaN, nact from t on and iters beyond t are -1.  One instance never affects another;
+ *   [1] steps finished (T when status = 0), [2] / [3] total / largest iteration count of the steps, [4] mu, [5] primal and [6] dual residual at the last stop
+ *   test, [7] smallest pivot (R_cc^2) of the Cholesky factorisations.
+ * The numbers of an instance do not depend on ns, on the other instances or on the workspace slot it ran in (fixed order of accumulation); the host entry stages
+ * through device buffers and runs the same kernel.  Workspace: the library keeps min(nb ns, 512) slots of
+ * 8 (2 (N+1) n + 6 N nd + N nx + N mb (n+1)) bytes per thread, fewer slots where that would exceed 1 GiB.
+ * TMPC_E_ARG: nb, p, nx, mb, N, ns, T < 1, nd < 0, k0 outside 0 .. p-1, D / d / nd mismatch, ndcnt without D, tol <= 0, max_iter < 1, NULL A, B, H, X0, U0, XT,
+ * info, (host entry) ndcnt outside 0 .. nd.  TMPC_E_UNSUPPORTED (before the device is touched): nx + mb > TMPC_LQR_NMAX, (nx, mb, nd) beyond 160 KB of LDS. */
+#define TMPC_MPC_QP_INFO 8
+int tmpc_mpc_qp_batch_host(int nb, int p, int nx, int mb, int nd, int N, int ns, int T, int k0, const double* A, const double* B, const double* H,
+                           const double* q, const double* Pf, const double* D, const int32_t* ndcnt, const double* d, const double* X0, double tol, int max_iter,
+                           double* U0, double* XT, double* info, double* X, double* U, int32_t* iters, int32_t* nact, double* hres, double* Xol, double* Uol,
+                           double* Lam);
+int tmpc_mpc_qp_batch_device(int nb, int p, int nx, int mb, int nd, int N, int ns, int T, int k0, const double* A, const double* B, const double* H,
+                             const double* q, const double* Pf, const double* D, const int32_t* ndcnt, const double* d, const double* X0, double tol,
+                             int max_iter, double* U0, double* XT, double* info, double* X, double* U, int32_t* iters, int32_t* nact, double* hres, double* Xol,
+                             double* Uol, double* Lam);
 
 /* Accumulated hipEvent timings since the last call (ms) when TMPC_FLAG_PROFILE is set, 16 doubles:
  * out[0] stage_pre+ctrl, [1] schur assembly, [2] block factorisation (all kernels of tmpc_cr.h's factor phase), [3] predictor

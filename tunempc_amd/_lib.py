@@ -25,7 +25,7 @@ EXPORTS = [
     'tmpc_tracking_reference_host', 'tmpc_eig_scan_host', 'tmpc_get_profile', 'tmpc_get_trace', 'tmpc_get_dual_host', 'tmpc_get_dual_con_host', 'tmpc_pack_sensitivities_host', 'tmpc_eig_clip_host',
     'tmpc_periodic_lqr_batch_host', 'tmpc_periodic_lqr_batch_device', 'tmpc_periodic_lqr_rows_batch_host', 'tmpc_periodic_lqr_rows_batch_device',
     'tmpc_periodic_lqr_ctg_batch_host', 'tmpc_periodic_lqr_ctg_batch_device', 'tmpc_horizon_lqr_batch_host', 'tmpc_horizon_lqr_batch_device',
-    'tmpc_closed_loop_batch_host', 'tmpc_closed_loop_batch_device',
+    'tmpc_closed_loop_batch_host', 'tmpc_closed_loop_batch_device', 'tmpc_mpc_qp_batch_host', 'tmpc_mpc_qp_batch_device',
     'tmpc_last_error', 'tmpc_version',
 ]
 # ... and in include/tunempc_hip_debug.h (unit-test / diagnostic entries)
@@ -146,6 +146,10 @@ def load_library():
     lib.tmpc_closed_loop_batch_host.argtypes = [C.c_int] * 9 + [dp] * 7 + [ip] + [dp] * 10
     lib.tmpc_closed_loop_batch_device.restype = C.c_int
     lib.tmpc_closed_loop_batch_device.argtypes = [C.c_int] * 9 + [vp] * 18
+    lib.tmpc_mpc_qp_batch_host.restype = C.c_int
+    lib.tmpc_mpc_qp_batch_host.argtypes = [C.c_int] * 9 + [dp] * 6 + [ip, dp, dp, C.c_double, C.c_int] + [dp] * 5 + [ip, ip] + [dp] * 4
+    lib.tmpc_mpc_qp_batch_device.restype = C.c_int
+    lib.tmpc_mpc_qp_batch_device.argtypes = [C.c_int] * 9 + [vp] * 9 + [C.c_double, C.c_int] + [vp] * 11
     lib.tmpc_get_profile.restype = C.c_int
     lib.tmpc_get_profile.argtypes = [vp, dp]
     lib.tmpc_get_trace.restype = C.c_int
@@ -195,6 +199,7 @@ E_UNSUPPORTED = -2
 LQR_INFO_STRIDE = 8
 LQR_CTG_INFO_STRIDE = 12
 CLOSED_LOOP_INFO_STRIDE = 4
+MPC_QP_INFO_STRIDE = 8
 
 
 def _check(lib, rc, what):
@@ -853,6 +858,66 @@ def closed_loop_batch_device(A, B, K, X0, H, Hc, J, ncnt, ng, Hn, T, k0, return_
         raise ValueError(lib.tmpc_last_error().decode())
     _check_lqr(lib, rc, 'tmpc_closed_loop_batch_device')
     return _closed_loop_views(X, U, l, lc, rowres, subres, sums, XT, info, lambda a: a.permute(0, 2, 1, 3), lambda a: a.permute(0, 2, 1))
+
+
+def _mpc_qp_views(U0, XT, info, X, U, iters, nact, hres, Xol, Uol, Lam, tr4, tr3):
+    """The outputs of the MPC QP entries (logs time-major in memory) in the layout of mpc_closed_loop_batch: permuted views, nothing is copied."""
+    return dict(U0=U0, XT=XT, info=info, X=None if X is None else tr4(X), U=None if U is None else tr4(U), iters=tr3(iters), nact=tr3(nact), hres=tr3(hres),
+                Xol=Xol, Uol=Uol, Lam=Lam)
+
+
+def mpc_qp_batch_host(A, B, H, q, Pf, D, ndcnt, d, X0, N, T, k0, tol, max_iter, return_traj, return_ol):
+    """tmpc_mpc_qp_batch_host on validated, contiguous numpy arrays (fp64; q, Pf, D, d None or arrays; ndcnt int32 or None) -> dict U0 [nb,ns,nu], XT [nb,ns,nx],
+    info [nb,ns,8], X [nb,ns,T+1,nx], U [nb,ns,T,nu] (None without return_traj), iters, nact int32 [nb,ns,T], hres [nb,ns,T], Xol [nb,ns,N+1,nx], Uol [nb,ns,N,nu],
+    Lam [nb,ns,N,nd] (None without return_ol).  The library stores the logs time-major: they are permuted views."""
+    lib = load_library()
+    nb, p, nx, mb = B.shape
+    ns, T, N = X0.shape[1], int(T), int(N)
+    nd = 0 if D is None else D.shape[2]
+    X = np.empty((nb, T + 1, ns, nx)) if return_traj else None
+    U = np.empty((nb, T, ns, mb)) if return_traj else None
+    iters = np.empty((nb, T, ns), np.int32); nact = np.empty((nb, T, ns), np.int32); hres = np.empty((nb, T, ns))
+    Xol = np.empty((nb, ns, N + 1, nx)) if return_ol else None
+    Uol = np.empty((nb, ns, N, mb)) if return_ol else None
+    Lam = np.empty((nb, ns, N, nd)) if return_ol else None
+    U0 = np.empty((nb, ns, mb)); XT = np.empty((nb, ns, nx)); info = np.zeros((nb, ns, MPC_QP_INFO_STRIDE))
+    rc = lib.tmpc_mpc_qp_batch_host(nb, p, nx, mb, nd, N, ns, T, int(k0), _dptr(A), _dptr(B), _dptr(H), _dptr(q), _dptr(Pf), _dptr(D) if nd else None,
+                                    _iptr(ndcnt) if nd else None, _dptr(d) if nd else None, _dptr(X0), float(tol), int(max_iter), _dptr(U0), _dptr(XT), _dptr(info),
+                                    _dptr(X), _dptr(U), _iptr(iters), _iptr(nact), _dptr(hres), _dptr(Xol), _dptr(Uol), _dptr(Lam))
+    if rc == -1:      # TMPC_E_ARG: the library's message names the argument
+        raise ValueError(lib.tmpc_last_error().decode())
+    _check_lqr(lib, rc, 'tmpc_mpc_qp_batch_host')
+    return _mpc_qp_views(U0, XT, info, X, U, iters, nact, hres, Xol, Uol, Lam, lambda a: a.transpose(0, 2, 1, 3), lambda a: a.transpose(0, 2, 1))
+
+
+def mpc_qp_batch_device(A, B, H, q, Pf, D, ndcnt, d, X0, N, T, k0, tol, max_iter, return_traj, return_ol):
+    """tmpc_mpc_qp_batch_device on validated, contiguous torch tensors of one GPU (fp64; ndcnt int32 or None) -> the dict of mpc_qp_batch_host with torch
+    tensors; the inputs never leave HBM."""
+    import torch
+    lib = load_library()
+    nb, p, nx, mb = B.shape
+    ns, T, N = X0.shape[1], int(T), int(N)
+    nd = 0 if D is None else D.shape[2]
+    dev = A.device
+    f64 = lambda *sh: torch.empty(sh, dtype=torch.float64, device=dev)
+    i32 = lambda *sh: torch.empty(sh, dtype=torch.int32, device=dev)
+    X = f64(nb, T + 1, ns, nx) if return_traj else None
+    U = f64(nb, T, ns, mb) if return_traj else None
+    iters = i32(nb, T, ns); nact = i32(nb, T, ns); hres = f64(nb, T, ns)
+    Xol = f64(nb, ns, N + 1, nx) if return_ol else None
+    Uol = f64(nb, ns, N, mb) if return_ol else None
+    Lam = f64(nb, ns, N, nd) if return_ol else None
+    U0 = f64(nb, ns, mb); XT = f64(nb, ns, nx); info = torch.zeros((nb, ns, MPC_QP_INFO_STRIDE), dtype=torch.float64, device=dev)
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+    with torch.cuda.device(dev):
+        torch.cuda.current_stream(dev).synchronize()      # the entry runs on the null stream: the inputs must be complete
+        rc = lib.tmpc_mpc_qp_batch_device(nb, p, nx, mb, nd, N, ns, T, int(k0), ptr(A), ptr(B), ptr(H), ptr(q), ptr(Pf), ptr(D) if nd else None,
+                                          ptr(ndcnt) if nd else None, ptr(d) if nd else None, ptr(X0), float(tol), int(max_iter), ptr(U0), ptr(XT), ptr(info),
+                                          ptr(X), ptr(U), ptr(iters), ptr(nact), ptr(hres), ptr(Xol), ptr(Uol), ptr(Lam))
+    if rc == -1:
+        raise ValueError(lib.tmpc_last_error().decode())
+    _check_lqr(lib, rc, 'tmpc_mpc_qp_batch_device')
+    return _mpc_qp_views(U0, XT, info, X, U, iters, nact, hres, Xol, Uol, Lam, lambda a: a.permute(0, 2, 1, 3), lambda a: a.permute(0, 2, 1))
 
 
 def cr_schedule(p):

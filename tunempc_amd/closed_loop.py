@@ -16,7 +16,7 @@ a constraint-to-go max|Hn_k x_t| -- one launch for the whole batch (csrc/tmpc_cl
     cost_equivalence(A, B, Q, R, N, dHc, P, K, x0, steps, ...)                          the certificate on what `convexify` takes and returns
 
 This is the first-order (LQ) loop: the rows J_k are the ones active at the optimal cycle and stay fixed, the plant is its linearisation.  Changes of the
-active set and the nonlinear plant are not simulated.
+active set are served by mpc_qp.py (the inequality-constrained MPC in the loop); the nonlinear plant is not simulated.
 
 The certificate: Hc_k = H_k + [A_k B_k]' P_{k+1} [A_k B_k] - diag(P_k, 0) (+ J_k' diag(phi_k) J_k, zero on trajectories that keep the rows), so along ANY
 trajectory of the dynamics, whatever the feedback,

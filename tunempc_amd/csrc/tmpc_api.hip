@@ -34,6 +34,7 @@
 #include "tmpc_lqr_ctg.h"
 #include "tmpc_lqr_horizon.h"
 #include "tmpc_closed_loop.h"
+#include "tmpc_mpc_qp.h"
 #include "tmpc_dd.h"
 #include "tmpc_big.h"
 
@@ -2166,6 +2167,130 @@ int tmpc_closed_loop_batch_host(int nb, int p, int nx, int mb, int nr, int ng, i
   if (sums) HIPCHK(hipMemcpy(sums, dSum, cSum * 8, hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(XT, dXT, c0 * 8, hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(info, dI, cI * 8, hipMemcpyDeviceToHost));
+  return TMPC_OK;
+}
+
+// The inequality-constrained MPC step and closed loop (tmpc_mpc_qp.h): one workgroup per instance (problem, initial state), min(instances, MQ_SLOTS) workgroups
+// loop over the instances, each with its slot of the workspace.
+static_assert(MQ_INFO == TMPC_MPC_QP_INFO, "tunempc_hip.h: info stride of the MPC QP entries");
+constexpr long long MQ_WS_CAP_BYTES = 1LL << 30;      // the workspace of a launch: fewer slots beyond this (one slot at the least)
+
+static int mpc_qp_check(const char* who, int nb, int p, int nx, int mb, int nd, int N, int ns, int T, int k0, const void* A, const void* B, const void* H,
+                        const void* D, const void* ndcnt, const void* d, const void* X0, double tol, int max_iter, const void* U0, const void* XT,
+                        const void* info) {
+  if (nb < 1 || p < 1 || nx < 1 || mb < 1 || N < 1 || ns < 1 || T < 1 || nd < 0 || !A || !B || !H || !X0 || !U0 || !XT || !info) {
+    snprintf(g_err, sizeof(g_err), "%s: bad argument (nb, p, nx, nu, N, ns, T >= 1, nd >= 0, non-null A, B, H, X0, U0, XT, info; got N = %d, ns = %d, T = %d, "
+             "nd = %d)", who, N, ns, T, nd);
+    return TMPC_E_ARG;
+  }
+  if (k0 < 0 || k0 >= p) {
+    snprintf(g_err, sizeof(g_err), "%s: bad argument (starting phase k0 in 0 .. p - 1 = %d; got %d)", who, p - 1, k0);
+    return TMPC_E_ARG;
+  }
+  if (((nd > 0) != (D != nullptr)) || ((nd > 0) != (d != nullptr)) || (ndcnt && !D)) {
+    snprintf(g_err, sizeof(g_err), "%s: bad argument (D and d non-null exactly when nd > 0, the row capacity per stage; ndcnt only with D; got nd = %d)", who, nd);
+    return TMPC_E_ARG;
+  }
+  if (!(tol > 0.0) || max_iter < 1) {
+    snprintf(g_err, sizeof(g_err), "%s: bad argument (tol > 0, max_iter >= 1; got tol = %g, max_iter = %d)", who, tol, max_iter);
+    return TMPC_E_ARG;
+  }
+  if (nx + mb > LQR_NMAX) {
+    snprintf(g_err, sizeof(g_err), "%s: the MPC step handles stage blocks up to nx + nu = %d (got %d)", who, LQR_NMAX, nx + mb);
+    return TMPC_E_UNSUPPORTED;
+  }
+  const MpcQpLds L = mpc_qp_lds(nx, mb, nd < 65536 ? nd : 65536);
+  const long long bytes = (long long)L.total * (long long)sizeof(double);
+  if (bytes > LQR_LDS_BYTES) {
+    snprintf(g_err, sizeof(g_err), "%s: nx = %d, nu = %d with room for %d rows per stage needs %lld bytes of LDS (limit %d)", who, nx, mb, nd, bytes, LQR_LDS_BYTES);
+    return TMPC_E_UNSUPPORTED;
+  }
+  if ((long long)(N + 1) * (nx + mb) > 0x7fffffffLL / 4 || (long long)N * (nd > mb * (nx + mb + 1) ? nd : mb * (nx + mb + 1)) > 0x7fffffffLL / 4) {
+    snprintf(g_err, sizeof(g_err), "%s: horizon N = %d too long for this stage shape (32-bit indices inside a slot)", who, N);
+    return TMPC_E_UNSUPPORTED;
+  }
+  return TMPC_OK;
+}
+
+static thread_local EigScratch g_mpc_qp_ws;           // workspace slots of both entries, kept between calls and grown on demand
+
+static int mpc_qp_launch(int nb, int p, int nx, int mb, int nd, int N, int ns, int T, int k0, const double* A, const double* B, const double* H, const double* q,
+                         const double* Pf, const double* D, const int32_t* ndcnt, const double* d, const double* X0, double tol, int max_iter, double* U0,
+                         double* XT, double* info, double* X, double* U, int32_t* iters, int32_t* nact, double* hres, double* Xol, double* Uol, double* Lam) {
+  const MpcQpLds L = mpc_qp_lds(nx, mb, nd);
+  const size_t lds_bytes = (size_t)L.total * sizeof(double);
+  const long long ninst = (long long)nb * ns, per = mpc_qp_ws_doubles(nx, mb, nd, N) * 8;
+  long long slots = ninst < MQ_SLOTS ? ninst : MQ_SLOTS;
+  if (slots * per > MQ_WS_CAP_BYTES) slots = MQ_WS_CAP_BYTES / per;
+  if (slots < 1) slots = 1;
+  HIPCHK(g_mpc_qp_ws.reserve((size_t)(slots * per)));
+  HIPCHK(hipFuncSetAttribute((const void*)k_mpc_qp, hipFuncAttributeMaxDynamicSharedMemorySize, LQR_LDS_BYTES));
+  int lcw = 0;
+  while ((1 << lcw) < nx + mb) ++lcw;
+  hipLaunchKernelGGL(k_mpc_qp, dim3((unsigned)slots), dim3(LQR_NT), lds_bytes, 0, p, nx, mb, nd, lcw, N, ns, T, k0, ninst, A, B, H, q, Pf, D, (const int*)ndcnt, d,
+                     X0, tol, max_iter, (double*)g_mpc_qp_ws.p, U0, XT, info, X, U, (int*)iters, (int*)nact, hres, Xol, Uol, Lam);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(0));
+  return TMPC_OK;
+}
+
+int tmpc_mpc_qp_batch_device(int nb, int p, int nx, int mb, int nd, int N, int ns, int T, int k0, const double* A, const double* B, const double* H,
+                             const double* q, const double* Pf, const double* D, const int32_t* ndcnt, const double* d, const double* X0, double tol,
+                             int max_iter, double* U0, double* XT, double* info, double* X, double* U, int32_t* iters, int32_t* nact, double* hres, double* Xol,
+                             double* Uol, double* Lam) {
+  const int rc = mpc_qp_check("tmpc_mpc_qp_batch_device", nb, p, nx, mb, nd, N, ns, T, k0, A, B, H, D, ndcnt, d, X0, tol, max_iter, U0, XT, info);
+  if (rc != TMPC_OK) return rc;
+  return mpc_qp_launch(nb, p, nx, mb, nd, N, ns, T, k0, A, B, H, q, Pf, D, ndcnt, d, X0, tol, max_iter, U0, XT, info, X, U, iters, nact, hres, Xol, Uol, Lam);
+}
+
+static thread_local EigScratch g_mpc_qp_scratch;      // device images of the host entry
+
+int tmpc_mpc_qp_batch_host(int nb, int p, int nx, int mb, int nd, int N, int ns, int T, int k0, const double* A, const double* B, const double* H,
+                           const double* q, const double* Pf, const double* D, const int32_t* ndcnt, const double* d, const double* X0, double tol, int max_iter,
+                           double* U0, double* XT, double* info, double* X, double* U, int32_t* iters, int32_t* nact, double* hres, double* Xol, double* Uol,
+                           double* Lam) {
+  const char* who = "tmpc_mpc_qp_batch_host";
+  const int rc = mpc_qp_check(who, nb, p, nx, mb, nd, N, ns, T, k0, A, B, H, D, ndcnt, d, X0, tol, max_iter, U0, XT, info);
+  if (rc != TMPC_OK) return rc;
+  const size_t n = (size_t)nx + mb, st = (size_t)nb * p, sn = (size_t)nb * ns;
+  if (ndcnt) for (size_t i = 0; i < st; ++i) if (ndcnt[i] < 0 || ndcnt[i] > nd) {
+    snprintf(g_err, sizeof(g_err), "%s: ndcnt[%zu][%zu] = %d outside 0 .. nd = %d", who, i / p, i % p, (int)ndcnt[i], nd);
+    return TMPC_E_ARG;
+  }
+  // inputs A | B | H | q | Pf | D | d | X0, outputs U0 | XT | info | X | U | hres | Xol | Uol | Lam, then the int32 arrays ndcnt | iters | nact
+  const size_t cA = st * nx * nx, cB = st * nx * mb, cH = st * n * n, cq = q ? st * n : 0, cPf = Pf ? cA : 0, cD = st * nd * n, cd = st * nd, c0 = sn * nx;
+  const size_t cU0 = sn * mb, cI = sn * MQ_INFO, cS = sn * T, cX = X ? sn * (T + 1) * nx : 0, cU = U ? sn * T * mb : 0, ch = hres ? cS : 0;
+  const size_t cXo = Xol ? sn * (N + 1) * nx : 0, cUo = Uol ? sn * N * mb : 0, cL = Lam ? sn * N * nd : 0;
+  const size_t cN = ndcnt ? (st + 1) / 2 : 0, cit = iters ? (cS + 1) / 2 : 0, cna = nact ? (cS + 1) / 2 : 0;       // int32, counted in doubles
+  HIPCHK(g_mpc_qp_scratch.reserve((cA + cB + cH + cq + cPf + cD + cd + 2 * c0 + cU0 + cI + cX + cU + ch + cXo + cUo + cL + cN + cit + cna + 1) * 8));
+  double* dA = (double*)g_mpc_qp_scratch.p; double* dB = dA + cA; double* dH = dB + cB; double* dq = dH + cH; double* dPf = dq + cq; double* dD = dPf + cPf;
+  double* dd = dD + cD; double* d0 = dd + cd; double* dU0 = d0 + c0; double* dXT = dU0 + cU0; double* dI = dXT + c0; double* dX = dI + cI; double* dU = dX + cX;
+  double* dh = dU + cU; double* dXo = dh + ch; double* dUo = dXo + cXo; double* dL = dUo + cUo;
+  int32_t* dN = (int32_t*)(dL + cL); int32_t* dit = (int32_t*)((double*)dN + cN); int32_t* dna = (int32_t*)((double*)dit + cit);
+  HIPCHK(hipMemcpy(dA, A, cA * 8, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dB, B, cB * 8, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dH, H, cH * 8, hipMemcpyHostToDevice));
+  if (q) HIPCHK(hipMemcpy(dq, q, cq * 8, hipMemcpyHostToDevice));
+  if (Pf) HIPCHK(hipMemcpy(dPf, Pf, cPf * 8, hipMemcpyHostToDevice));
+  if (D) HIPCHK(hipMemcpy(dD, D, cD * 8, hipMemcpyHostToDevice));
+  if (d) HIPCHK(hipMemcpy(dd, d, cd * 8, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(d0, X0, c0 * 8, hipMemcpyHostToDevice));
+  if (ndcnt) HIPCHK(hipMemcpy(dN, ndcnt, st * sizeof(int32_t), hipMemcpyHostToDevice));
+  const int rl = mpc_qp_launch(nb, p, nx, mb, nd, N, ns, T, k0, dA, dB, dH, q ? dq : nullptr, Pf ? dPf : nullptr, D ? dD : nullptr, ndcnt ? dN : nullptr,
+                               d ? dd : nullptr, d0, tol, max_iter, dU0, dXT, dI, X ? dX : nullptr, U ? dU : nullptr, iters ? dit : nullptr,
+                               nact ? dna : nullptr, hres ? dh : nullptr, Xol ? dXo : nullptr, Uol ? dUo : nullptr, Lam ? dL : nullptr);
+  if (rl != TMPC_OK) return rl;
+  HIPCHK(hipMemcpy(U0, dU0, cU0 * 8, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(XT, dXT, c0 * 8, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(info, dI, cI * 8, hipMemcpyDeviceToHost));
+  if (X) HIPCHK(hipMemcpy(X, dX, cX * 8, hipMemcpyDeviceToHost));
+  if (U) HIPCHK(hipMemcpy(U, dU, cU * 8, hipMemcpyDeviceToHost));
+  if (hres) HIPCHK(hipMemcpy(hres, dh, cS * 8, hipMemcpyDeviceToHost));
+  if (Xol) HIPCHK(hipMemcpy(Xol, dXo, cXo * 8, hipMemcpyDeviceToHost));
+  if (Uol) HIPCHK(hipMemcpy(Uol, dUo, cUo * 8, hipMemcpyDeviceToHost));
+  if (Lam && cL) HIPCHK(hipMemcpy(Lam, dL, cL * 8, hipMemcpyDeviceToHost));
+  if (iters) HIPCHK(hipMemcpy(iters, dit, cS * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (nact) HIPCHK(hipMemcpy(nact, dna, cS * sizeof(int32_t), hipMemcpyDeviceToHost));
   return TMPC_OK;
 }
 

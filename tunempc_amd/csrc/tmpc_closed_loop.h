@@ -2,7 +2,7 @@
 // reference's closed_loop_tools.closed_loop_sim).  A tile of TS initial states of one problem walks t = 0 ... T-1 over the stages k = (k0 + t) mod p:
 //   U = -K_k X,  Z = [X; U],  l = 1/2 colsum(Z o (H_k Z)),  lc = 1/2 colsum(Z o (Hc_k Z)),  rowres = colmax|J_k Z| (first r_k = ng + ncnt_k rows),
 //   subres = colmax|Hn_k X| (all nx rows; rows beyond c_k are zero),  X <- A_k X + B_k U.
-// This is the first-order (LQ) loop: the active set is fixed and the plant is the linearisation.
+// This is the first-order (LQ) loop: the active set is fixed (tmpc_mpc_qp.h serves its changes) and the plant is the linearisation.
 //
 // Residency: grid nb x ceil(ns / TS), one 256-thread workgroup per (problem, tile); the tile [n x TS] (twice: a step reads one image and writes the next X into
 // the other) stays in LDS for the whole rollout, [A_k B_k], K_k, one cost matrix (H_k, then Hc_k through the same buffer), J_k and Hn_k come from global memory

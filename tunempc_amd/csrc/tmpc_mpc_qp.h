@@ -1,0 +1,468 @@
+// The inequality-constrained tracking-MPC step and its receding-horizon loop (the reference's pmpc.py with h(x, u) >= 0 at every stage, seen through
+// closed_loop_tools.check_equivalence and closed_loop_sim): one small structured QP per (problem, initial state),
+//   min  sum_{j<N} (1/2 z_j' H_k z_j + q_k' z_j) + 1/2 x_N' Pf_{k_N} x_N,   z_j = [x_j; u_j],   k = k_j = (k0 + j) mod p,
+//   s.t. x_{j+1} = A_k x_j + B_k u_j,  x_0 given,   D_k z_j <= d_k (first ndcnt_k rows),   j = 0 .. N-1,
+// solved T times in a row: step t starts at phase (k0 + t) mod p, applies u_0 and moves x <- A_k x + B_k u_0 on the linear plant.
+// Not served: equality rows J, the terminal constraint x_N = 0, slack penalties, warm starts between the steps, the nonlinear plant.
+//
+// Method: a primal-dual interior-point method with Mehrotra's predictor-corrector, started infeasible (z = 0 but x_0, s_i = max(d_i, 1), lam_i = 1).  The
+// multipliers of the dynamics are not variables: they are the adjoint of the iterate, pi_N = Pf x_N, [pi_j; r_u] = H z_j + q + D' lam_j + [A B]' pi_{j+1}, so
+// the dual residual is r_u.  One iteration:
+//   pass 1 (backward)   residuals (rows r_in = D z + s - d, dynamics r_dyn = [A B] z_j - x_{j+1}, r_u), then the Newton system, which is the LQ problem with
+//                       Hb = H + E' Pi_{j+1} E + D' diag(w) D,  w = lam / (s + rho lam)  (rho = 1e-12, a dual regularisation that bounds w by 1 / rho: its
+//                       error in the row equation is rho dlam and vanishes with the step),  h = H z + q + D' (w (r_in + rho lam)) + E' (Pi_{j+1} r_dyn + p_{j+1}):
+//                       S = Hb_uu = R' R (Cholesky, in place and together with the right-hand sides: [R | Y | y] = R^-T [S | Hb_ux | h_u]),
+//                       Pi_j = Hb_xx - Y' Y,  p_j = h_x - Y' y;
+//   sweep (forward)     du = -R^-1 (Y dx + y),  dlam = c - w s + w (r_in + D dz),  ds = -r_in - D dz + rho dlam,  dx+ = E dz + r_dyn, and the step length;
+//   corrector           c = (sigma mu - ds_aff dlam_aff) / (s + rho lam), sigma = (mu_aff / mu)^3; by linearity only the change of y is swept backward with
+//                       the factors of pass 1 (dh = D' c + E' dp_{j+1}, dy = R^-T dh_u, dp_j = dh_x - Y' dy), then the forward sweep again;
+//   step                alpha = min(1, 0.995 alpha_max), one length for primal and dual.
+// Stop (tests/mpc_qp_reference.py states the same rule): r_p <= tol, r_d <= tol, mu <= 1e-3 tol max(1, max lam) with
+//   r_p = max(max_i |r_in,i| / max(1, |d_i|), max|r_dyn| / max(1, max|x|)),   r_d = max|r_u| / max(1, max_j |H z_j + q + D' lam_j|).
+// The factorisation of the pass that meets the stop test is not used: a failed pivot counts only when the test was not met.
+//
+// Residency: one 256-thread workgroup per instance, fp64 on the vector ALU, the interior-point loop and all T steps in one launch.  The operands of a stage
+// ([A B], Pi, Pi E, Hb with the factors, D_k and the vectors of the stage) live in LDS (mpc_qp_lds); A, B, H, D are read again per stage and pass (the ns
+// instances of a problem share them in L2).  What an instance keeps per stage for its sweeps -- [Y | R | y], the iterate, the direction, r_in, r_dyn, c --
+// lies in a slot of a global workspace (mpc_qp_ws_doubles per slot); the grid is min(instances, MQ_SLOTS) workgroups that loop over the instances.
+//
+// Order of accumulation: every sum is one thread's sum in ascending order, or a butterfly over the lanes of a wave followed by the four waves in order; nothing
+// depends on the slot, on ns or on the other instances.  Control flow is uniform in the workgroup: every decision is taken on block-reduced values or on LDS
+// entries that all threads read, there is no exit around a barrier.
+//
+// Statuses: 0 converged at every step, 1 max_iter reached (an infeasible instance ends here), 2 a stage matrix S not positive definite, 3 non-finite.  An
+// instance that fails at step t keeps what it logged before; U, hres from t on, X from t + 1 on and XT are NaN, iters beyond t and nact from t on are -1.
+#pragma once
+#include "tmpc_closed_loop.h"
+
+namespace tmpc {
+
+constexpr int MQ_INFO = 8;                   // doubles of info per instance (TMPC_MPC_QP_INFO)
+constexpr int MQ_SLOTS = 512;                // workgroups (and workspace slots) per launch at the most
+constexpr int MQ_NVEC = 24;                  // vector slots of the LDS layout
+constexpr double MQ_RHO = 1e-12, MQ_STEP_BACK = 0.995, MQ_MU_FACTOR = 1e-3;
+enum { MQ_OK = 0, MQ_MAXITER = 1, MQ_NOT_CONVEX = 2, MQ_NONFINITE = 3 };
+
+struct MpcQpLds { int ld, ldp, lv, oE, oP, oW, oH, oD, oV, oR, total; };      // offsets in doubles
+__host__ __device__ inline MpcQpLds mpc_qp_lds(int nx, int mb, int nd) {
+  MpcQpLds l;
+  const int n = nx + mb;
+  l.ld = (n + 1) | 1; l.ldp = nx | 1;
+  l.lv = n + 1 > nd ? n + 1 : nd;
+  l.oE = 0;                                  // E_k = [A_k B_k] [nx x n]
+  l.oP = l.oE + nx * l.ld;                   // Pi_{j+1}, then Pi_j [nx x nx]
+  l.oW = l.oP + nx * l.ldp;                  // Pi E [nx x n]
+  l.oH = l.oW + nx * l.ld;                   // H_k, then Hb, then [Y | R | y] in its rows nx .. n-1 (column n: h_u) [n x (n + 1)]
+  l.oD = l.oH + n * l.ld;                    // D_k [nd x n]
+  l.oV = l.oD + nd * l.ld;                   // MQ_NVEC vectors of lv doubles
+  l.oR = l.oV + MQ_NVEC * l.lv;              // block reductions [8]
+  const long long total = (long long)l.oR + 8;
+  l.total = total > 0x7fffffffLL / 8 ? 0x7fffffff / 8 : (int)total;
+  return l;
+}
+
+// doubles of workspace per slot: Z, dZ [(N+1)][n]; S, L, dS, dL, RIN, COR [N][nd]; RDYN [N][nx]; FAC [N][mb][n + 1]
+__host__ __device__ inline long long mpc_qp_ws_doubles(int nx, int mb, int nd, int N) {
+  const long long n = nx + mb;
+  return 2LL * (N + 1) * n + 6LL * N * nd + (long long)N * nx + (long long)N * mb * (n + 1);
+}
+
+__device__ __forceinline__ double mq_dot(const double* __restrict__ a, const double* __restrict__ b, int len) {
+  double acc = 0.0;
+  for (int c = 0; c < len; ++c) acc = fma(a[c], b[c], acc);
+  return acc;
+}
+
+// op 0: sum, 1: max, 2: min over the workgroup; every thread returns the same value.  Butterfly over the lanes, then the four waves in order.
+template <int OP> __device__ __forceinline__ double mq_block(double v, double* red, int tid) {
+  for (int o = 32; o > 0; o >>= 1) {
+    const double u = __shfl_xor(v, o, 64);
+    v = OP == 0 ? v + u : (OP == 1 ? fmax(v, u) : fmin(v, u));
+  }
+  if ((tid & 63) == 0) red[tid >> 6] = v;
+  __syncthreads();
+  const double a = red[0], b = red[1], c = red[2], d = red[3];
+  const double r = OP == 0 ? ((a + b) + c) + d : (OP == 1 ? fmax(fmax(a, b), fmax(c, d)) : fmin(fmin(a, b), fmin(c, d)));
+  __syncthreads();
+  return r;
+}
+
+// E_k, D_k (m rows) and optionally H_k (symmetrised) of stage k into LDS; tx < cw columns, ty first row, rs row stride.
+__device__ __forceinline__ void mq_fetch(double* El, double* Hl, double* Dl, int ld, const double* __restrict__ Ak, const double* __restrict__ Bk,
+                                         const double* __restrict__ Hk, const double* __restrict__ Dk, int nx, int mb, int m, int tx, int ty, int rs) {
+  const int n = nx + mb;
+  if (tx < n) {
+    for (int r = ty; r < nx; r += rs) El[r * ld + tx] = tx < nx ? Ak[r * nx + tx] : Bk[r * mb + tx - nx];
+    if (Hk) for (int r = ty; r < n; r += rs) Hl[r * ld + tx] = 0.5 * (Hk[r * n + tx] + Hk[tx * n + r]);
+    for (int i = ty; i < m; i += rs) Dl[i * ld + tx] = Dk[i * n + tx];
+  }
+}
+
+// grid: min(nb * ns, MQ_SLOTS) workgroups; instance = b * ns + s.  cw = 1 << lcw: power of two >= n (<= 64).  A [nb][p][nx][nx], B [nb][p][nx][mb],
+// H [nb][p][n][n], q [nb][p][n] or null, Pf [nb][p][nx][nx] or null, D [nb][p][nd][n] and d [nb][p][nd] (null when nd = 0), ndcnt [nb][p] or null (all nd rows;
+// counts are clamped to 0 .. nd), X0 [nb][ns][nx]; ws: gridDim.x slots of mpc_qp_ws_doubles.  Outputs: U0 [nb][ns][mb], XT [nb][ns][nx], info [nb][ns][8];
+// each or null: X [nb][T+1][ns][nx], U [nb][T][ns][mb], iters, nact int [nb][T][ns], hres [nb][T][ns], Xol [nb][ns][N+1][nx], Uol [nb][ns][N][mb],
+// Lam [nb][ns][N][nd] (the open-loop solution of step 0).
+__global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd, int lcw, int N, int ns, int T, int k0, long long ninst,
+                                                   const double* __restrict__ Ag, const double* __restrict__ Bg, const double* __restrict__ Hg,
+                                                   const double* __restrict__ qg, const double* __restrict__ Pfg, const double* __restrict__ Dg,
+                                                   const int* __restrict__ ndcntg, const double* __restrict__ dg, const double* __restrict__ X0g, double tol,
+                                                   int max_iter, double* wsg, double* __restrict__ U0g, double* __restrict__ XTg, double* __restrict__ infog,
+                                                   double* __restrict__ Xg, double* __restrict__ Ug, int* __restrict__ itersg, int* __restrict__ nactg,
+                                                   double* __restrict__ hresg, double* __restrict__ Xolg, double* __restrict__ Uolg,
+                                                   double* __restrict__ Lamg) {
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  const int n = nx + mb;
+  const MpcQpLds Ly = mpc_qp_lds(nx, mb, nd);
+  const int ld = Ly.ld, ldp = Ly.ldp, lv = Ly.lv;
+  double* El = lds + Ly.oE; double* Pl = lds + Ly.oP; double* Wl = lds + Ly.oW; double* Hl = lds + Ly.oH; double* Dl = lds + Ly.oD; double* red = lds + Ly.oR;
+  double* V = lds + Ly.oV;
+  double* zv = V; double* xn = V + lv; double* lamv = V + 2 * lv; double* sv = V + 3 * lv; double* ddv = V + 4 * lv; double* wv_ = V + 5 * lv;
+  double* rinv = V + 6 * lv; double* bsv = V + 7 * lv; double* gq = V + 8 * lv; double* fullv = V + 9 * lv; double* hp = V + 10 * lv; double* rdynv = V + 11 * lv;
+  double* vv = V + 12 * lv; double* pin = V + 13 * lv; double* pv = V + 14 * lv; double* dxa = V + 15 * lv; double* dxb = V + 16 * lv; double* dzv = V + 17 * lv;
+  double* corv = V + 18 * lv; double* xcur = V + 19 * lv; double* dgv = V + 20 * lv; double* dyv = V + 21 * lv; double* qv = V + 22 * lv;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int cw = 1 << lcw, tx = tid & (cw - 1), ty = tid >> lcw, rs = LQR_NT >> lcw;
+  const double qnan = __longlong_as_double(0x7ff8000000000000LL);
+  const long long wsn = mpc_qp_ws_doubles(nx, mb, nd, N);
+  double* ws = wsg + (size_t)blockIdx.x * wsn;
+  double* Z = ws; double* dZ = Z + (size_t)(N + 1) * n; double* Sg = dZ + (size_t)(N + 1) * n; double* Lg = Sg + (size_t)N * nd; double* dSg = Lg + (size_t)N * nd;
+  double* dLg = dSg + (size_t)N * nd; double* RIN = dLg + (size_t)N * nd; double* COR = RIN + (size_t)N * nd; double* RDYN = COR + (size_t)N * nd;
+  double* FAC = RDYN + (size_t)N * nx;
+  const int fs = mb * (n + 1);                                               // doubles of [Y | R | y] per stage
+
+  for (long long inst = blockIdx.x; inst < ninst; inst += gridDim.x) {
+    const size_t b = (size_t)(inst / ns), si = (size_t)(inst % ns);
+    const double* A = Ag + b * p * nx * nx; const double* B = Bg + b * p * nx * mb; const double* H = Hg + b * p * n * n;
+    const double* q = qg ? qg + b * p * n : nullptr; const double* Pf = Pfg ? Pfg + b * p * nx * nx : nullptr;
+    const double* D = nd > 0 ? Dg + b * p * nd * n : nullptr; const double* dd = nd > 0 ? dg + b * p * nd : nullptr;
+    const int* ndcnt = ndcntg ? ndcntg + b * p : nullptr;
+    auto rows_of = [&](int k) { return nd > 0 ? (ndcnt ? max(0, min(nd, ndcnt[k])) : nd) : 0; };
+
+    if (tid < nx) {
+      const double v = X0g[(b * ns + si) * nx + tid];
+      xcur[tid] = v;
+      if (Xg) Xg[((b * (T + 1)) * ns + si) * nx + tid] = v;
+    }
+    __syncthreads();
+    int status = MQ_OK, done = 0, it_total = 0, it_max = 0;
+    double mu = 0.0, rp = 0.0, rd = 0.0, pivmin = INFINITY;
+
+    for (int t = 0; t < T; ++t) {
+      const int k0s = (k0 + t % p) % p;
+      int its = 0, nact = -1;
+      double hres = qnan;
+      if (status == MQ_OK) {                                                 // (uniform: status is the same in every thread)
+        // ---- start of the step: z = 0 but x_0, s = max(d, 1), lam = 1, no direction
+        int mt = 0;
+        for (int j = 0; j < N; ++j) mt += rows_of((k0s + j % p) % p);
+        for (int e = tid; e < (N + 1) * n; e += LQR_NT) { Z[e] = e < nx ? xcur[e] : 0.0; dZ[e] = 0.0; }
+        for (int e = tid; e < N * nd; e += LQR_NT) {
+          const int j = e / nd, i = e - j * nd, k = (k0s + j % p) % p;
+          const bool on = i < rows_of(k);
+          Sg[e] = on ? fmax(dd[k * nd + i], 1.0) : 1.0; Lg[e] = on ? 1.0 : 0.0;
+          dSg[e] = 0.0; dLg[e] = 0.0; RIN[e] = 0.0; COR[e] = 0.0;
+        }
+        __syncthreads();
+        const int kN = (k0s + N % p) % p;
+
+        for (int it = 0;; ++it) {
+          its = it;
+          // ================================================================ pass 1: residuals and factorisation, j = N-1 .. 0
+          if (tx < nx) for (int r = ty; r < nx; r += rs) Pl[r * ldp + tx] = Pf ? 0.5 * (Pf[((size_t)kN * nx + r) * nx + tx] + Pf[((size_t)kN * nx + tx) * nx + r]) : 0.0;
+          if (tid < nx) xn[tid] = Z[(size_t)N * n + tid];
+          __syncthreads();
+          double a_rp = 0.0, a_dyn = 0.0, a_x = 0.0, a_rd = 0.0, a_g = 0.0, a_lam = 0.0;
+          if (tid < nx) {
+            const double v = mq_dot(Pl + tid * ldp, xn, nx);
+            pin[tid] = v; pv[tid] = v;
+            a_x = cl_absmax(a_x, xn[tid]);
+          }
+          int facfail = 0;
+          __syncthreads();
+          for (int j = N - 1; j >= 0; --j) {
+            const int k = (k0s + j % p) % p, m = rows_of(k);
+            mq_fetch(El, Hl, Dl, ld, A + (size_t)k * nx * nx, B + (size_t)k * nx * mb, H + (size_t)k * n * n, D ? D + (size_t)k * nd * n : nullptr, nx, mb, m, tx, ty, rs);
+            if (tid < n) { zv[tid] = Z[(size_t)j * n + tid]; qv[tid] = q ? q[k * n + tid] : 0.0; }
+            if (tid >= 64 && tid < 64 + nx) xn[tid - 64] = Z[(size_t)(j + 1) * n + tid - 64];
+            for (int i = tid; i < m; i += LQR_NT) { lamv[i] = Lg[(size_t)j * nd + i]; sv[i] = Sg[(size_t)j * nd + i]; ddv[i] = dd[k * nd + i]; }
+            __syncthreads();
+            // ---- A: the residuals of the rows and of the dynamics, H z + q, Pi E
+            for (int e = tid; e < m + nx + n; e += LQR_NT) {
+              if (e < m) {
+                const double lam = lamv[e], s = sv[e];
+                const double r = mq_dot(Dl + e * ld, zv, n) + s - ddv[e];
+                const double w = lam / (s + MQ_RHO * lam);
+                rinv[e] = r; wv_[e] = w; bsv[e] = w * (r + MQ_RHO * lam);
+                RIN[(size_t)j * nd + e] = r;
+                a_rp = cl_absmax(a_rp, r / fmax(1.0, fabs(ddv[e]))); a_lam = cl_absmax(a_lam, lam);
+              } else if (e < m + nx) {
+                const int r = e - m;
+                const double v = mq_dot(El + r * ld, zv, n) - xn[r];
+                rdynv[r] = v; RDYN[(size_t)j * nx + r] = v;
+                a_dyn = cl_absmax(a_dyn, v); a_x = cl_absmax(a_x, zv[r]);
+              } else {
+                const int i = e - m - nx;
+                gq[i] = mq_dot(Hl + i * ld, zv, n) + qv[i];
+              }
+            }
+            if (tx < n) for (int r = ty; r < nx; r += rs) {
+              double acc = 0.0;
+              for (int c = 0; c < nx; ++c) acc = fma(Pl[r * ldp + c], El[c * ld + tx], acc);
+              Wl[r * ld + tx] = acc;
+            }
+            __syncthreads();
+            // ---- B: g = H z + q + D' lam, [pi_j; r_u] = g + E' pi_{j+1}, v = Pi r_dyn + p, Hb = H + E' Pi E + D' w D
+            for (int e = tid; e < n + nx; e += LQR_NT) {
+              if (e < n) {
+                double dl = 0.0, db = 0.0, ep = 0.0;
+                for (int r = 0; r < m; ++r) { const double x = Dl[r * ld + e]; dl = fma(x, lamv[r], dl); db = fma(x, bsv[r], db); }
+                for (int r = 0; r < nx; ++r) ep = fma(El[r * ld + e], pin[r], ep);
+                const double g = gq[e] + dl;
+                a_g = cl_absmax(a_g, g);
+                fullv[e] = g + ep;
+                if (e >= nx) a_rd = cl_absmax(a_rd, g + ep);
+                hp[e] = gq[e] + db;
+              } else {
+                const int r = e - n;
+                vv[r] = mq_dot(Pl + r * ldp, rdynv, nx) + pv[r];
+              }
+            }
+            if (!facfail && tx < n) for (int i = ty; i < n; i += rs) {
+              double acc = Hl[i * ld + tx];
+              for (int r = 0; r < nx; ++r) acc = fma(El[r * ld + i], Wl[r * ld + tx], acc);
+              for (int r = 0; r < m; ++r) acc = fma(Dl[r * ld + i] * wv_[r], Dl[r * ld + tx], acc);
+              Hl[i * ld + tx] = acc;
+            }
+            __syncthreads();
+            // ---- C: h = H z + q + D' (w (r_in + rho lam)) + E' v; its u part becomes column n of Hb; pi_j
+            if (tid < n) {
+              double acc = hp[tid];
+              for (int r = 0; r < nx; ++r) acc = fma(El[r * ld + tid], vv[r], acc);
+              hp[tid] = acc;
+              if (tid >= nx) Hl[tid * ld + n] = acc;
+              else pin[tid] = fullv[tid];
+            }
+            __syncthreads();
+            if (!facfail) {
+              // ---- S = R' R in the rows nx .. n-1 of Hb, the right-hand sides [Hb_ux | h_u] along: one pivot per barrier, rows scaled at the end
+              for (int c = 0; c < mb; ++c) {
+                const double piv = Hl[(nx + c) * ld + nx + c];
+                if (!(piv > 0.0 && piv < INFINITY)) { facfail = 1; break; }
+                pivmin = fmin(pivmin, piv);
+                const double inv = 1.0 / piv;
+                const double* prow = Hl + (nx + c) * ld;
+                for (int i = c + 1 + ty; i < mb; i += rs) {
+                  const double f = prow[nx + i] * inv;
+                  double* row = Hl + (nx + i) * ld;
+                  for (int col = tx; col <= n; col += cw) if (col < nx || col > nx + c) row[col] = fma(-f, prow[col], row[col]);
+                }
+                __syncthreads();
+              }
+            }
+            if (!facfail) {
+              if (tid < mb) dgv[tid] = 1.0 / sqrt(Hl[(nx + tid) * ld + nx + tid]);
+              __syncthreads();
+              for (int i = ty; i < mb; i += rs) {
+                const double sc = dgv[i];
+                for (int col = tx; col <= n; col += cw) {
+                  const double v = Hl[(nx + i) * ld + col] * sc;
+                  Hl[(nx + i) * ld + col] = v;
+                  FAC[(size_t)j * fs + i * (n + 1) + col] = v;
+                }
+              }
+              __syncthreads();
+              // ---- Pi_j = sym(Hb_xx) - Y' Y,  p_j = h_x - Y' y
+              if (tx < nx) for (int i = ty; i < nx; i += rs) {
+                double acc = 0.5 * (Hl[i * ld + tx] + Hl[tx * ld + i]);
+                for (int c = 0; c < mb; ++c) acc = fma(-Hl[(nx + c) * ld + i], Hl[(nx + c) * ld + tx], acc);
+                Pl[i * ldp + tx] = acc;
+              }
+              if (tid >= 64 && tid < 64 + nx) {
+                const int r = tid - 64;
+                double acc = hp[r];
+                for (int c = 0; c < mb; ++c) acc = fma(-Hl[(nx + c) * ld + r], Hl[(nx + c) * ld + n], acc);
+                pv[r] = acc;
+              }
+            }
+            __syncthreads();
+          }
+          // ---- the figures of the iterate and the stop test
+          double part = 0.0;
+          for (int e = tid; e < N * nd; e += LQR_NT) part = fma(Lg[e], Sg[e], part);
+          const double sumc = mq_block<0>(part, red, tid);
+          const double xmax = mq_block<1>(a_x, red, tid), lmax = mq_block<1>(a_lam, red, tid), gmax = mq_block<1>(a_g, red, tid);
+          rp = fmax(mq_block<1>(a_rp, red, tid), mq_block<1>(a_dyn, red, tid) / fmax(1.0, xmax));
+          rd = mq_block<1>(a_rd, red, tid) / fmax(1.0, gmax);
+          mu = mt > 0 ? sumc / mt : 0.0;
+          if (!(rp < INFINITY && rd < INFINITY && fabs(mu) < INFINITY && lmax < INFINITY && xmax < INFINITY)) { status = MQ_NONFINITE; break; }
+          if (rp <= tol && rd <= tol && mu <= MQ_MU_FACTOR * tol * fmax(1.0, lmax)) break;
+          if (facfail) { status = MQ_NOT_CONVEX; break; }
+          if (it == max_iter) { status = MQ_MAXITER; break; }
+
+          double alpha = 1.0;
+          for (int sweep = 0; sweep < 2; ++sweep) {
+            if (sweep == 1) {
+              if (mt == 0) break;
+              // ============================================================== the corrector: sigma, c, and the change of y swept backward
+              const double aa = fmin(1.0, alpha);
+              part = 0.0;
+              for (int e = tid; e < N * nd; e += LQR_NT) part = fma(Lg[e] + aa * dLg[e], Sg[e] + aa * dSg[e], part);
+              const double r3 = mq_block<0>(part, red, tid) / mt / mu;
+              const double sigmu = r3 * r3 * r3 * mu;
+              for (int e = tid; e < N * nd; e += LQR_NT) {
+                const int j = e / nd, i = e - j * nd;
+                COR[e] = i < rows_of((k0s + j % p) % p) ? (sigmu - dSg[e] * dLg[e]) / (Sg[e] + MQ_RHO * Lg[e]) : 0.0;
+              }
+              if (tid < nx) dxa[tid] = 0.0;                                  // dp_N
+              __syncthreads();
+              double* dp = dxa; double* dpn = dxb;
+              for (int j = N - 1; j >= 0; --j) {
+                const int k = (k0s + j % p) % p, m = rows_of(k);
+                mq_fetch(El, nullptr, Dl, ld, A + (size_t)k * nx * nx, B + (size_t)k * nx * mb, nullptr, D ? D + (size_t)k * nd * n : nullptr, nx, mb, m, tx, ty, rs);
+                for (int i = ty; i < mb; i += rs) for (int col = tx; col <= n; col += cw) Hl[(nx + i) * ld + col] = FAC[(size_t)j * fs + i * (n + 1) + col];
+                for (int i = tid; i < m; i += LQR_NT) corv[i] = COR[(size_t)j * nd + i];
+                __syncthreads();
+                if (tid < n) {
+                  double acc = 0.0;
+                  for (int r = 0; r < m; ++r) acc = fma(Dl[r * ld + tid], corv[r], acc);
+                  for (int r = 0; r < nx; ++r) acc = fma(El[r * ld + tid], dp[r], acc);
+                  hp[tid] = acc;
+                }
+                __syncthreads();
+                if (wave == 0) {                                             // R' dy = dh_u, column by column inside one wave
+                  double tt = lane < mb ? hp[nx + lane] : 0.0;
+                  for (int c = 0; c < mb; ++c) {
+                    const double yc = __shfl(tt, c, 64) / Hl[(nx + c) * ld + nx + c];
+                    if (lane > c && lane < mb) tt = fma(-Hl[(nx + c) * ld + nx + lane], yc, tt);
+                    if (lane == c) tt = yc;
+                  }
+                  if (lane < mb) { dyv[lane] = tt; FAC[(size_t)j * fs + lane * (n + 1) + n] = Hl[(nx + lane) * ld + n] + tt; }
+                }
+                __syncthreads();
+                if (tid < nx) {
+                  double acc = hp[tid];
+                  for (int c = 0; c < mb; ++c) acc = fma(-Hl[(nx + c) * ld + tid], dyv[c], acc);
+                  dpn[tid] = acc;
+                }
+                __syncthreads();
+                { double* t_ = dp; dp = dpn; dpn = t_; }
+              }
+            }
+            // ================================================================ the forward sweep: the direction and its largest step
+            if (tid < nx) dxa[tid] = 0.0;
+            __syncthreads();
+            double* dx = dxa; double* dxn = dxb;
+            double amin = 1e300;
+            for (int j = 0; j < N; ++j) {
+              const int k = (k0s + j % p) % p, m = rows_of(k);
+              mq_fetch(El, nullptr, Dl, ld, A + (size_t)k * nx * nx, B + (size_t)k * nx * mb, nullptr, D ? D + (size_t)k * nd * n : nullptr, nx, mb, m, tx, ty, rs);
+              for (int i = ty; i < mb; i += rs) for (int col = tx; col <= n; col += cw) Hl[(nx + i) * ld + col] = FAC[(size_t)j * fs + i * (n + 1) + col];
+              for (int i = tid; i < m; i += LQR_NT) {
+                lamv[i] = Lg[(size_t)j * nd + i]; sv[i] = Sg[(size_t)j * nd + i]; rinv[i] = RIN[(size_t)j * nd + i]; corv[i] = sweep ? COR[(size_t)j * nd + i] : 0.0;
+              }
+              if (tid >= 64 && tid < 64 + nx) rdynv[tid - 64] = RDYN[(size_t)j * nx + tid - 64];
+              __syncthreads();
+              if (wave == 0) {                                               // du = -R^-1 (Y dx + y), column by column inside one wave
+                double tt = lane < mb ? mq_dot(Hl + (nx + lane) * ld, dx, nx) + Hl[(nx + lane) * ld + n] : 0.0;
+                for (int c = mb - 1; c >= 0; --c) {
+                  const double uc = __shfl(tt, c, 64) / Hl[(nx + c) * ld + nx + c];
+                  if (lane < c) tt = fma(-Hl[(nx + lane) * ld + nx + c], uc, tt);
+                  if (lane == c) tt = uc;
+                }
+                if (lane < mb) { dzv[nx + lane] = -tt; dZ[(size_t)j * n + nx + lane] = -tt; }
+              } else if (tid - 64 < nx) {
+                const double v = dx[tid - 64];
+                dzv[tid - 64] = v; dZ[(size_t)j * n + tid - 64] = v;
+              }
+              __syncthreads();
+              for (int e = tid; e < m + nx; e += LQR_NT) {
+                if (e < m) {
+                  const double lam = lamv[e], s = sv[e], Dz = mq_dot(Dl + e * ld, dzv, n);
+                  const double w = lam / (s + MQ_RHO * lam);
+                  const double dl = corv[e] - w * s + w * (rinv[e] + Dz);
+                  const double ds = -rinv[e] - Dz + MQ_RHO * dl;
+                  dLg[(size_t)j * nd + e] = dl; dSg[(size_t)j * nd + e] = ds;
+                  if (ds < 0.0) amin = fmin(amin, -s / ds);
+                  if (dl < 0.0) amin = fmin(amin, -lam / dl);
+                } else {
+                  const int r = e - m;
+                  dxn[r] = mq_dot(El + r * ld, dzv, n) + rdynv[r];
+                }
+              }
+              __syncthreads();
+              { double* t_ = dx; dx = dxn; dxn = t_; }
+            }
+            if (tid < nx) dZ[(size_t)N * n + tid] = dx[tid];
+            alpha = mq_block<2>(amin, red, tid);
+          }
+          // ================================================================ the step
+          const double al = fmin(1.0, MQ_STEP_BACK * alpha);
+          for (int e = tid; e < (N + 1) * n; e += LQR_NT) Z[e] = fma(al, dZ[e], Z[e]);
+          for (int e = tid; e < N * nd; e += LQR_NT) { Sg[e] = fma(al, dSg[e], Sg[e]); Lg[e] = fma(al, dLg[e], Lg[e]); }
+          __syncthreads();
+        }
+        it_total += its; it_max = max(it_max, its);
+      }
+      // ---- the step's results: u_0, the open-loop solution of step 0, nact, hres, x <- E [x; u_0]
+      const bool ok = status == MQ_OK && done == t;
+      if (ok) {
+        const int m = rows_of(k0s);
+        mq_fetch(El, nullptr, Dl, ld, A + (size_t)k0s * nx * nx, B + (size_t)k0s * nx * mb, nullptr, D ? D + (size_t)k0s * nd * n : nullptr, nx, mb, m, tx, ty, rs);
+        if (tid < n) zv[tid] = Z[tid];
+        __syncthreads();
+        double hmax = -INFINITY, cnt = 0.0;
+        for (int i = tid; i < m; i += LQR_NT) {
+          hmax = fmax(hmax, mq_dot(Dl + i * ld, zv, n) - dd[k0s * nd + i]);
+          if (Lg[i] > Sg[i]) cnt += 1.0;
+        }
+        hres = mq_block<1>(hmax, red, tid);
+        nact = (int)mq_block<0>(cnt, red, tid);
+        if (t == 0) {
+          if (Xolg) for (int e = tid; e < (N + 1) * nx; e += LQR_NT) { const int j = e / nx; Xolg[((b * ns + si) * (N + 1)) * nx + e] = Z[(size_t)j * n + e - j * nx]; }
+          if (Uolg) for (int e = tid; e < N * mb; e += LQR_NT) { const int j = e / mb; Uolg[((b * ns + si) * N) * mb + e] = Z[(size_t)j * n + nx + e - j * mb]; }
+          if (Lamg) for (int e = tid; e < N * nd; e += LQR_NT) Lamg[((b * ns + si) * N) * nd + e] = Lg[e];
+        }
+        double xnew = 0.0;
+        if (tid < nx) xnew = mq_dot(El + tid * ld, zv, n);
+        if (tid >= 64 && tid < 64 + mb) {
+          const double u = zv[nx + tid - 64];
+          if (t == 0) U0g[(b * ns + si) * mb + tid - 64] = u;
+          if (Ug) Ug[((b * T + t) * ns + si) * mb + tid - 64] = u;
+        }
+        __syncthreads();
+        if (tid < nx) {
+          xcur[tid] = xnew;
+          if (Xg) Xg[((b * (T + 1) + t + 1) * ns + si) * nx + tid] = xnew;
+        }
+        __syncthreads();
+        done = t + 1;
+      } else {
+        if (tid < mb) {
+          if (t == 0) U0g[(b * ns + si) * mb + tid] = qnan;
+          if (Ug) Ug[((b * T + t) * ns + si) * mb + tid] = qnan;
+        }
+        if (tid < nx && Xg) Xg[((b * (T + 1) + t + 1) * ns + si) * nx + tid] = qnan;
+        if (t == 0) {
+          if (Xolg) for (int e = tid; e < (N + 1) * nx; e += LQR_NT) Xolg[((b * ns + si) * (N + 1)) * nx + e] = qnan;
+          if (Uolg) for (int e = tid; e < N * mb; e += LQR_NT) Uolg[((b * ns + si) * N) * mb + e] = qnan;
+          if (Lamg) for (int e = tid; e < N * nd; e += LQR_NT) Lamg[((b * ns + si) * N) * nd + e] = qnan;
+        }
+      }
+      if (tid == 0) {
+        const size_t o = (b * T + t) * ns + si;
+        if (itersg) itersg[o] = done >= t ? its : -1;
+        if (nactg) nactg[o] = nact;
+        if (hresg) hresg[o] = hres;
+      }
+    }
+    if (tid < nx) XTg[(b * ns + si) * nx + tid] = status == MQ_OK ? xcur[tid] : qnan;
+    if (tid == 0) {
+      double* o = infog + (b * ns + si) * MQ_INFO;
+      o[0] = status; o[1] = done; o[2] = it_total; o[3] = it_max; o[4] = mu; o[5] = rp; o[6] = rd; o[7] = pivmin;
+    }
+    __syncthreads();
+  }
+}
+
+}  // namespace tmpc

@@ -1,0 +1,231 @@
+"""The inequality-constrained tracking-MPC step and its receding-horizon loop on the GPU: what the tracking MPC does when a deviation is large enough to hit
+a bound (the reference's pmpc.py with h(x, u) >= 0 at every stage, as closed_loop_tools.check_equivalence and closed_loop_sim exercise it).
+
+lqr.py and closed_loop.py serve the laws of a FIXED active set.  This module solves, per (problem, initial deviation x_0) and k_j = (phase0 + j) mod p,
+
+    min  sum_{j<N} (1/2 z_j' H_k z_j + q_k' z_j) + 1/2 x_N' Pf_{k_N} x_N,   z_j = [x_j; u_j],
+    s.t. x_{j+1} = A_k x_j + B_k u_j,   D_k z_j <= d_k (first ndcnt_k rows of the stage),   j = 0 .. N-1,
+
+with a primal-dual interior-point method (Mehrotra's predictor-corrector, Riccati recursion with a Cholesky factorisation per stage), one 256-thread workgroup
+per instance, the whole interior-point loop and all steps of the closed loop in one launch (csrc/tmpc_mpc_qp.h).
+
+    mpc_qp_batch(A, B, H, X0, horizon, phase0=0, D=None, d=None, ...)              one step: u0, the open-loop X, U, lam
+    mpc_closed_loop_batch(A, B, H, X0, horizon, steps, phase0=0, ...)              the receding-horizon loop on the linear plant
+    mpc_step(A, B, Q, R, N, x0, horizon, ...)                                      one model in the reference's calling style
+    mpc_closed_loop_sim(A, B, Q, R, N, x0, horizon, steps, ...)                    -> the reference's log {'x', 'u', 'l', 'h'}
+
+Not served: equality rows J, the terminal constraint x_N = 0, slack penalties (usc), warm starts between the steps, the nonlinear plant; there are no arguments
+for them.  Conventions as in lqr.py / closed_loop.py.  There is no CPU path: the solve runs in the HIP library or the call raises."""
+import numpy as np
+
+from . import _lib
+from . import lqr
+from . import closed_loop as _cl
+from .convexifier import _to_array
+
+STATUS_NAMES = {0: 'Converged', 1: 'MaxIter', 2: 'NotConvex', 3: 'NonFinite'}
+LDS_BYTES = 160 * 1024
+TOL = 1e-10            # the defaults of tests/mpc_qp_reference.py
+MAX_ITER = 60
+SLOTS = 512            # workgroups (workspace slots) of a launch at the most
+INFO_FIELDS = ('status', 'steps', 'iters_total', 'iters_max', 'mu', 'rp', 'rd', 'pivmin')
+
+
+def lds_layout(nx, nu, nd=0):
+    """mpc_qp_lds of csrc/tmpc_mpc_qp.h restated: dict bytes (LDS of a workgroup), ws_doubles (function of the horizon: doubles of workspace per slot)."""
+    nx, nu, nd = int(nx), int(nu), int(nd)
+    n = nx + nu
+    ld, ldp, lv = (n + 1) | 1, nx | 1, max(n + 1, nd)
+    total = nx * ld + nx * ldp + nx * ld + n * ld + nd * ld + 24 * lv + 8
+    return dict(bytes=8 * total, ws_doubles=lambda N: 2 * (N + 1) * n + 6 * N * nd + N * nx + N * nu * (n + 1))
+
+
+def _validate(who, A, B, H, X0, horizon, phase0, D, d, ndcnt, q, Pf, tol, max_iter, steps=1):
+    named = [('A', A), ('B', B), ('H', H), ('X0', X0)] + [(nm, x) for nm, x in (('D', D), ('d', d), ('q', q), ('Pf', Pf)) if x is not None]
+    use_torch = _cl._check_kind(who, named)
+    if len(A.shape) != 4 or A.shape[2] != A.shape[3]:
+        raise ValueError('{}: A [nb, p, nx, nx] expected, got {}'.format(who, tuple(A.shape)))
+    nb, p, nx, _ = (int(v) for v in A.shape)
+    if len(B.shape) != 4 or tuple(B.shape[:3]) != (nb, p, nx):
+        raise ValueError('{}: B [nb, p, nx, nu] = [{}, {}, {}, nu] expected, got {}'.format(who, nb, p, nx, tuple(B.shape)))
+    nu = int(B.shape[3])
+    if nb < 1 or p < 1 or nx < 1 or nu < 1:
+        raise ValueError('{}: nb, p, nx, nu >= 1 expected, got nb = {}, p = {}, nx = {}, nu = {}'.format(who, nb, p, nx, nu))
+    n = nx + nu
+    if tuple(H.shape) != (nb, p, n, n):
+        raise ValueError('{}: H {} expected, got {}'.format(who, (nb, p, n, n), tuple(H.shape)))
+    if len(X0.shape) != 3 or int(X0.shape[0]) != nb or int(X0.shape[2]) != nx:
+        raise ValueError('{}: X0 [nb, ns, nx] = [{}, ns, {}] expected, got {}'.format(who, nb, nx, tuple(X0.shape)))
+    ns = int(X0.shape[1])
+    if ns < 1:
+        raise ValueError('{}: ns >= 1 initial states expected, got X0 {}'.format(who, tuple(X0.shape)))
+    if isinstance(horizon, bool) or not isinstance(horizon, (int, np.integer)) or int(horizon) < 1:
+        raise ValueError('{}: horizon must be an int >= 1, got {!r}'.format(who, horizon))
+    T, k0 = _cl._validate_steps(who, steps, phase0, p)
+    if (D is None) != (d is None):
+        raise ValueError('{}: D and d come together (the rows D z <= d), got {} without {}'.format(who, *(('d', 'D') if D is None else ('D', 'd'))))
+    if D is None and ndcnt is not None:
+        raise ValueError('{}: ndcnt describes the rows of D, which is None'.format(who))
+    nd = 0
+    if D is not None:
+        if len(D.shape) != 4 or tuple(D.shape[:2]) != (nb, p) or int(D.shape[3]) != n or int(D.shape[2]) < 1:
+            raise ValueError('{}: D [nb, p, nd, nx + nu] = [{}, {}, nd >= 1, {}] expected, got {}'.format(who, nb, p, n, tuple(D.shape)))
+        nd = int(D.shape[2])
+        if tuple(d.shape) != (nb, p, nd):
+            raise ValueError('{}: d {} expected, got {}'.format(who, (nb, p, nd), tuple(d.shape)))
+        if ndcnt is not None:
+            if not hasattr(ndcnt, 'shape') or lqr._is_torch(ndcnt) != use_torch:
+                raise ValueError('{}: ndcnt must be {} like A, B, H'.format(who, 'a torch tensor' if use_torch else 'a numpy array'))
+            if tuple(ndcnt.shape) != (nb, p) or 'int32' not in str(ndcnt.dtype):
+                raise ValueError('{}: ndcnt int32 {} expected, got {} {}'.format(who, (nb, p), ndcnt.dtype, tuple(ndcnt.shape)))
+            if use_torch and (not ndcnt.is_cuda or ndcnt.device != A.device):
+                raise ValueError('{}: torch tensors must be tensors of one GPU (ndcnt: {})'.format(who, ndcnt.device))
+            lo, hi = (int(ndcnt.min()), int(ndcnt.max()))
+            if lo < 0 or hi > nd:
+                raise ValueError('{}: ndcnt in 0 .. nd = {} expected, got {} .. {}'.format(who, nd, lo, hi))
+    if q is not None and tuple(q.shape) != (nb, p, n):
+        raise ValueError('{}: q {} expected, got {}'.format(who, (nb, p, n), tuple(q.shape)))
+    if Pf is not None and tuple(Pf.shape) != (nb, p, nx, nx):
+        raise ValueError('{}: Pf {} expected, got {}'.format(who, (nb, p, nx, nx), tuple(Pf.shape)))
+    if isinstance(tol, bool) or not isinstance(tol, (int, float, np.floating)) or not float(tol) > 0.0:
+        raise ValueError('{}: tol must be a float > 0, got {!r}'.format(who, tol))
+    if isinstance(max_iter, bool) or not isinstance(max_iter, (int, np.integer)) or int(max_iter) < 1:
+        raise ValueError('{}: max_iter must be an int >= 1, got {!r}'.format(who, max_iter))
+    if n > 64:
+        raise NotImplementedError('{}: the MPC step handles stage blocks up to nx + nu = 64 (got {})'.format(who, n))
+    lay = lds_layout(nx, nu, nd)
+    if lay['bytes'] > LDS_BYTES:
+        raise NotImplementedError('{}: nx = {}, nu = {} with room for {} rows per stage needs {} bytes of LDS (limit {})'.format(who, nx, nu, nd, lay['bytes'], LDS_BYTES))
+    return use_torch, nd, int(horizon), T, k0
+
+
+def _run(who, A, B, H, X0, horizon, steps, phase0, D, d, ndcnt, q, Pf, tol, max_iter, return_traj, return_ol):
+    use_torch, nd, N, T, k0 = _validate(who, A, B, H, X0, horizon, phase0, D, d, ndcnt, q, Pf, tol, max_iter, steps)
+    A, B, H, X0, D, d, q, Pf = (lqr._contig(x, use_torch) for x in (A, B, H, X0, D, d, q, Pf))
+    if ndcnt is not None:
+        ndcnt = ndcnt.contiguous() if use_torch else np.ascontiguousarray(ndcnt)
+    entry = _lib.mpc_qp_batch_device if use_torch else _lib.mpc_qp_batch_host
+    out = entry(A, B, H, q, Pf, D, ndcnt, d, X0, N, T, k0, float(tol), int(max_iter), bool(return_traj), bool(return_ol))
+    info = out['info']
+    for i, name in enumerate(INFO_FIELDS):
+        col = info[..., i]
+        if i < 4:
+            col = col.to(__import__('torch').int32) if use_torch else col.astype(np.int32)
+        else:
+            col = col.clone() if use_torch else col.copy()
+        out[name] = col
+    return out
+
+
+def mpc_qp_batch(A, B, H, X0, horizon, phase0=0, D=None, d=None, ndcnt=None, q=None, Pf=None, tol=TOL, max_iter=MAX_ITER, return_traj=True):
+    """One MPC step per (problem, initial deviation): A [nb,p,nx,nx], B [nb,p,nx,nu], H [nb,p,n,n] (used as (H + H') / 2), X0 [nb,ns,nx], fp64, n = nx + nu <= 64;
+    the horizon-`horizon` QP from phase `phase0`.  Optional: the rows D [nb,p,nd,n], d [nb,p,nd] (D z <= d; ndcnt int32 [nb,p]: only the first ndcnt rows of a
+    stage, None: all nd), q [nb,p,n] (linear cost), Pf [nb,p,nx,nx] (terminal weight 1/2 x_N' Pf[(phase0 + N) mod p] x_N); None: absent / zero.  Without rows
+    this is the plain horizon-N LQ problem.  tol, max_iter: the stop rule of csrc/tmpc_mpc_qp.h (residuals and mu relative to the scale of the problem).
+
+    numpy arrays run through the host entry; torch tensors on a GPU through the device entry (torch tensors out, the inputs are not copied).  Both run the same
+    kernel and agree bit for bit; the numbers of an instance do not depend on ns or on the other instances of the call.
+
+    Returns dict: u0 [nb,ns,nu], X [nb,ns,N+1,nx], U [nb,ns,N,nu], lam [nb,ns,N,nd] (the open-loop solution; None with return_traj=False), nact [nb,ns] int32
+    (rows of stage 0 with lam > s), hres [nb,ns] = max(D z_0 - d) (-inf at a stage without rows), x1 [nb,ns,nx] = A x_0 + B u_0, and the info fields status
+    (0 converged, 1 max_iter reached -- an infeasible instance ends here --, 2 a stage matrix not positive definite: not convex along the path, 3 non-finite), steps,
+    iters_total, iters_max [nb,ns] int32, mu, rp, rd, pivmin [nb,ns], info [nb,ns,8].  An instance with status != 0 returns NaN (nact -1); the others are not
+    affected.  ValueError: shapes, dtypes, mixed numpy / torch, horizon < 1, phase0 outside 0 .. p-1, D without d, ndcnt outside 0 .. nd, tol <= 0,
+    max_iter < 1; NotImplementedError: n > 64, (nx, nu, nd) beyond the 160 KB LDS layout (lds_layout)."""
+    o = _run('mpc_qp_batch', A, B, H, X0, horizon, 1, phase0, D, d, ndcnt, q, Pf, tol, max_iter, False, return_traj)
+    out = dict(u0=o['U0'], X=o['Xol'], U=o['Uol'], lam=o['Lam'], nact=o['nact'][..., 0], hres=o['hres'][..., 0], x1=o['XT'], info=o['info'])
+    out.update({k: o[k] for k in INFO_FIELDS})
+    return out
+
+
+def mpc_closed_loop_batch(A, B, H, X0, horizon, steps, phase0=0, D=None, d=None, ndcnt=None, q=None, Pf=None, tol=TOL, max_iter=MAX_ITER, return_traj=True):
+    """The receding-horizon loop: at t = 0 .. steps-1 the QP of mpc_qp_batch from phase (phase0 + t) mod p, cold-started, u_0 applied, x <- A_k x + B_k u_0 (the
+    linear plant, as closed_loop_batch does), all steps in one launch.  Arguments as mpc_qp_batch.
+
+    Returns dict: X [nb,ns,steps+1,nx], U [nb,ns,steps,nu] (None with return_traj=False), iters, nact [nb,ns,steps] int32, hres [nb,ns,steps], XT [nb,ns,nx],
+    u0 [nb,ns,nu] (the first input of step 0) and the info fields of mpc_qp_batch (steps: steps finished).  An instance that fails at step t (status 1, 2, 3)
+    keeps what it logged before: U, hres from t on, X from t + 1 on and XT are NaN, nact from t on and iters beyond t are -1.  X, U and the per-step logs are
+    permuted views of time-major arrays."""
+    o = _run('mpc_closed_loop_batch', A, B, H, X0, horizon, steps, phase0, D, d, ndcnt, q, Pf, tol, max_iter, return_traj, False)
+    out = dict(X=o['X'], U=o['U'], iters=o['iters'], nact=o['nact'], hres=o['hres'], XT=o['XT'], u0=o['U0'], info=o['info'])
+    out.update({k: o[k] for k in INFO_FIELDS})
+    return out
+
+
+def _stack_one(who, A, B, Q, R, N, x0, D, d, q, Pf):
+    """The reference's calling style -> batched arrays of one problem and one state."""
+    try:
+        As, Bs, Hs, _ = lqr._stack_stages(A, B, Q, R, N)
+    except ValueError as e:
+        raise ValueError(str(e).replace('periodic_lqr', who)) from None
+    p, nx, nu = As.shape[1], As.shape[2], Bs.shape[3]
+    n = nx + nu
+    x = _to_array(x0).astype(np.float64).reshape(-1)
+    if x.shape != (nx,):
+        raise ValueError('{}: x0 must hold nx = {} entries, got {}'.format(who, nx, _to_array(x0).shape))
+    Ds = ds = cnt = None
+    if (D is None) != (d is None):
+        raise ValueError('{}: D and d come together (the rows D z <= d)'.format(who))
+    if D is not None:
+        Dl = [None if m is None else np.atleast_2d(_to_array(m)).astype(np.float64) for m in (D if isinstance(D, (list, tuple)) else [D] * p)]
+        dl = [None if v is None else _to_array(v).astype(np.float64).reshape(-1) for v in (d if isinstance(d, (list, tuple)) else [d] * p)]
+        if len(Dl) != p or len(dl) != p:
+            raise ValueError('{}: D, d must be single arrays or lists of p = {} (None: no rows at that stage)'.format(who, p))
+        cnts = [0 if m is None else m.shape[0] for m in Dl]
+        for k in range(p):
+            if (Dl[k] is None) != (dl[k] is None) or (Dl[k] is not None and (Dl[k].shape[1] != n or dl[k].shape != (cnts[k],))):
+                raise ValueError('{}: D[{}] (rows, nx + nu = {}) with d[{}] (rows) expected'.format(who, k, n, k))
+        nd = max(cnts)
+        if nd:
+            Ds = np.zeros((1, p, nd, n)); ds = np.zeros((1, p, nd)); cnt = np.asarray([cnts], np.int32)
+            for k in range(p):
+                if cnts[k]:
+                    Ds[0, k, :cnts[k]] = Dl[k]; ds[0, k, :cnts[k]] = dl[k]
+    qs = None
+    if q is not None:
+        ql = [_to_array(v).astype(np.float64).reshape(-1) for v in (q if isinstance(q, (list, tuple)) else [q] * p)]
+        if len(ql) != p or any(v.shape != (n,) for v in ql):
+            raise ValueError('{}: q must be one vector of nx + nu = {} entries or a list of p = {} of them'.format(who, n, p))
+        qs = np.ascontiguousarray(np.stack(ql)[None])
+    try:
+        Pfs = lqr._stack_weights(Pf, p, nx, 'Pf')
+    except ValueError as e:
+        raise ValueError(str(e).replace('horizon_lqr', who)) from None
+    return As, Bs, Hs, np.ascontiguousarray(x[None, None]), dict(D=Ds, d=ds, ndcnt=cnt, q=qs, Pf=Pfs)
+
+
+def mpc_step(A, B, Q, R, N, x0, horizon, phase0=0, D=None, d=None, q=None, Pf=None, tol=TOL, max_iter=MAX_ITER):
+    """One MPC step of one model in the reference's calling style: A, B, Q, R, N (the cross term) single matrices (p = 1) or lists of length p as in horizon_lqr,
+    D, d the rows D_k [x; u] <= d_k (single arrays or lists of p; None entries: no rows at that stage), q, Pf likewise.  Returns (u0, X [horizon+1,nx],
+    U [horizon,nu], lam [horizon,nd], info dict).  RuntimeError when the solve did not converge."""
+    who = 'mpc_step'
+    As, Bs, Hs, X0, kw = _stack_one(who, A, B, Q, R, N, x0, D, d, q, Pf)
+    r = mpc_qp_batch(As, Bs, Hs, X0, horizon, phase0, tol=tol, max_iter=max_iter, **kw)
+    st = int(r['status'][0, 0])
+    if st != 0:
+        raise RuntimeError('{}: the solve ended with status {} ({}) after {} iterations'.format(who, st, STATUS_NAMES.get(st), int(r['iters_total'][0, 0])))
+    return r['u0'][0, 0], r['X'][0, 0], r['U'][0, 0], r['lam'][0, 0], {k: r[k][0, 0] for k in INFO_FIELDS + ('nact', 'hres')}
+
+
+def mpc_closed_loop_sim(A, B, Q, R, N, x0, horizon, steps, phase0=0, D=None, d=None, q=None, Pf=None, tol=TOL, max_iter=MAX_ITER):
+    """The reference's closed_loop_sim with the inequality-constrained tracking MPC in the loop and the linear plant, one model in the calling style of mpc_step.
+    Returns the reference's log: {'x': steps + 1 states, 'u': steps inputs, 'l': steps stage costs 1/2 z' H_k z + q_k' z, 'h': steps arrays d_k - D_k [x_t; u_t]
+    (>= 0 when the rows hold; empty at a stage without rows)} and 'iters', 'nact'.  RuntimeError when a step did not converge."""
+    who = 'mpc_closed_loop_sim'
+    As, Bs, Hs, X0, kw = _stack_one(who, A, B, Q, R, N, x0, D, d, q, Pf)
+    r = mpc_closed_loop_batch(As, Bs, Hs, X0, horizon, steps, phase0, tol=tol, max_iter=max_iter, **kw)
+    st = int(r['status'][0, 0])
+    if st != 0:
+        raise RuntimeError('{}: step {} of {} ended with status {} ({})'.format(who, int(r['steps'][0, 0]), int(steps), st, STATUS_NAMES.get(st)))
+    T, p = int(steps), As.shape[1]
+    X, U = r['X'][0, 0], r['U'][0, 0]
+    log = {'x': [X[t].copy() for t in range(T + 1)], 'u': [U[t].copy() for t in range(T)], 'l': [], 'h': [], 'iters': [int(v) for v in r['iters'][0, 0]],
+           'nact': [int(v) for v in r['nact'][0, 0]]}
+    for t in range(T):
+        k = (int(phase0) + t) % p
+        z = np.concatenate([X[t], U[t]])
+        Hk = (Hs[0, k] + Hs[0, k].T) / 2
+        log['l'].append(float(0.5 * z @ Hk @ z + (kw['q'][0, k] @ z if kw['q'] is not None else 0.0)))
+        m = int(kw['ndcnt'][0, k]) if kw['D'] is not None else 0
+        log['h'].append(kw['d'][0, k, :m] - kw['D'][0, k, :m] @ z if m else np.zeros(0))
+    return log
