@@ -398,7 +398,8 @@ int tmpc_closed_loop_batch_device(int nb, int p, int nx, int mb, int nr, int ng,
  *     min  sum_{j<N} (1/2 z_j' H_k z_j + q_k' z_j) + 1/2 x_N' Pf_{k_N} x_N,   z_j = [x_j; u_j],   k = k_j = (k0 + j) mod p,
  *     s.t. x_{j+1} = A_k x_j + B_k u_j,  x_0 given,   D_k z_j <= d_k (first ndcnt_k rows of the stage),   j = 0 .. N-1,
  * solved at the steps t = 0 .. T-1 from the phase (k0 + t) mod p; u_0 is applied and x <- A_k x + B_k u_0 (the linear plant), one launch for the whole batch.
- * Not served (there are no arguments for them): equality rows J, the terminal constraint x_N = 0, slack penalties, warm starts between steps, the nonlinear plant.
+ * Not served (there are no arguments for them): equality rows J, the terminal constraint x_N = 0, quadratic slack penalties, warm starts between steps, the
+ * nonlinear plant.  Soft rows (exact L1 slack penalties, the reference's `usc`): the tmpc_mpc_qp_soft_batch_* entries below.
  * Method: primal-dual interior point with Mehrotra's predictor-corrector, started infeasible, the Newton system solved by a Riccati pass with a Cholesky
  * factorisation per stage; the stop rule is r_p <= tol, r_d <= tol, mu <= 1e-3 tol max(1, max lam), residuals relative to the scale of the problem (stated
  * in tmpc_mpc_qp.h and in tests/mpc_qp_reference.py).  H is used as (H + H') / 2, likewise Pf.
@@ -427,6 +428,26 @@ int tmpc_mpc_qp_batch_device(int nb, int p, int nx, int mb, int nd, int N, int n
                              const double* q, const double* Pf, const double* D, const int32_t* ndcnt, const double* d, const double* X0, double tol,
                              int max_iter, double* U0, double* XT, double* info, double* X, double* U, int32_t* iters, int32_t* nact, double* hres, double* Xol,
                              double* Uol, double* Lam);
+
+/* The same step and loop with SOFT rows (the reference's preprocessing.add_mpc_slacks: h + usc >= 0, usc >= 0, cost scost' usc): the 31 arguments of the entries
+ * above, then
+ *   penalty [nb][p][nd]: +inf a hard row D_i z <= d_i, a finite c > 0 the soft row D_i z - e_i <= d_i, e_i >= 0 with the cost c e_i at every stage of the horizon
+ *                        (hard and soft rows mix freely; ndcnt keeps its meaning).  NULL: every row hard -- the hard kernel runs, Eol and nviol are zero;
+ *   Eol [nb][ns][N][nd], optional: the open-loop slacks e of step 0 (0 on hard rows and beyond ndcnt; NaN when step 0 failed);
+ *   nviol int32 [nb][T][ns], optional, time-major: rows of stage 0 with e > nu at the applied step (nu = c - lam the multiplier of e >= 0); -1 from a failed step on.
+ * The slack and its multiplier are eliminated per row inside the interior-point iteration (tmpc_mpc_qp.h), the stage matrices keep their size; the rules of the
+ * start, mu and the stop test are stated there and in tests/mpc_qp_soft_reference.py.  info, statuses and failure isolation as above; hres = max(D z - d) is
+ * positive when a soft row of the applied step is violated, nact stays lam > s.  Workspace per slot: 32 N nd bytes more than above.
+ * TMPC_E_ARG, besides the above: penalty with nd = 0; (host entry) a penalty <= 0 or NaN, named in the message.  On the device entry such a penalty makes the
+ * instances of that problem status 3 before their first step.  TMPC_E_UNSUPPORTED: the soft layout (24 nd bytes of LDS more) beyond 160 KB, with the byte count. */
+int tmpc_mpc_qp_soft_batch_host(int nb, int p, int nx, int mb, int nd, int N, int ns, int T, int k0, const double* A, const double* B, const double* H,
+                                const double* q, const double* Pf, const double* D, const int32_t* ndcnt, const double* d, const double* X0, double tol,
+                                int max_iter, double* U0, double* XT, double* info, double* X, double* U, int32_t* iters, int32_t* nact, double* hres, double* Xol,
+                                double* Uol, double* Lam, const double* penalty, double* Eol, int32_t* nviol);
+int tmpc_mpc_qp_soft_batch_device(int nb, int p, int nx, int mb, int nd, int N, int ns, int T, int k0, const double* A, const double* B, const double* H,
+                                  const double* q, const double* Pf, const double* D, const int32_t* ndcnt, const double* d, const double* X0, double tol,
+                                  int max_iter, double* U0, double* XT, double* info, double* X, double* U, int32_t* iters, int32_t* nact, double* hres,
+                                  double* Xol, double* Uol, double* Lam, const double* penalty, double* Eol, int32_t* nviol);
 
 /* Accumulated hipEvent timings since the last call (ms) when TMPC_FLAG_PROFILE is set, 16 doubles:
  * out[0] stage_pre+ctrl, [1] schur assembly, [2] block factorisation (all kernels of tmpc_cr.h's factor phase), [3] predictor

@@ -26,6 +26,7 @@ EXPORTS = [
     'tmpc_periodic_lqr_batch_host', 'tmpc_periodic_lqr_batch_device', 'tmpc_periodic_lqr_rows_batch_host', 'tmpc_periodic_lqr_rows_batch_device',
     'tmpc_periodic_lqr_ctg_batch_host', 'tmpc_periodic_lqr_ctg_batch_device', 'tmpc_horizon_lqr_batch_host', 'tmpc_horizon_lqr_batch_device',
     'tmpc_closed_loop_batch_host', 'tmpc_closed_loop_batch_device', 'tmpc_mpc_qp_batch_host', 'tmpc_mpc_qp_batch_device',
+    'tmpc_mpc_qp_soft_batch_host', 'tmpc_mpc_qp_soft_batch_device',
     'tmpc_last_error', 'tmpc_version',
 ]
 # ... and in include/tunempc_hip_debug.h (unit-test / diagnostic entries)
@@ -150,6 +151,10 @@ def load_library():
     lib.tmpc_mpc_qp_batch_host.argtypes = [C.c_int] * 9 + [dp] * 6 + [ip, dp, dp, C.c_double, C.c_int] + [dp] * 5 + [ip, ip] + [dp] * 4
     lib.tmpc_mpc_qp_batch_device.restype = C.c_int
     lib.tmpc_mpc_qp_batch_device.argtypes = [C.c_int] * 9 + [vp] * 9 + [C.c_double, C.c_int] + [vp] * 11
+    lib.tmpc_mpc_qp_soft_batch_host.restype = C.c_int
+    lib.tmpc_mpc_qp_soft_batch_host.argtypes = lib.tmpc_mpc_qp_batch_host.argtypes + [dp, dp, ip]
+    lib.tmpc_mpc_qp_soft_batch_device.restype = C.c_int
+    lib.tmpc_mpc_qp_soft_batch_device.argtypes = lib.tmpc_mpc_qp_batch_device.argtypes + [vp] * 3
     lib.tmpc_get_profile.restype = C.c_int
     lib.tmpc_get_profile.argtypes = [vp, dp]
     lib.tmpc_get_trace.restype = C.c_int
@@ -918,6 +923,64 @@ def mpc_qp_batch_device(A, B, H, q, Pf, D, ndcnt, d, X0, N, T, k0, tol, max_iter
         raise ValueError(lib.tmpc_last_error().decode())
     _check_lqr(lib, rc, 'tmpc_mpc_qp_batch_device')
     return _mpc_qp_views(U0, XT, info, X, U, iters, nact, hres, Xol, Uol, Lam, lambda a: a.permute(0, 2, 1, 3), lambda a: a.permute(0, 2, 1))
+
+
+def mpc_qp_soft_batch_host(A, B, H, q, Pf, D, ndcnt, d, penalty, X0, N, T, k0, tol, max_iter, return_traj, return_ol):
+    """tmpc_mpc_qp_soft_batch_host on validated, contiguous numpy arrays (penalty fp64 [nb,p,nd]) -> the dict of mpc_qp_batch_host with Eol [nb,ns,N,nd] (None
+    without return_ol) and nviol int32 [nb,ns,T]."""
+    lib = load_library()
+    nb, p, nx, mb = B.shape
+    ns, T, N = X0.shape[1], int(T), int(N)
+    nd = D.shape[2]
+    X = np.empty((nb, T + 1, ns, nx)) if return_traj else None
+    U = np.empty((nb, T, ns, mb)) if return_traj else None
+    iters = np.empty((nb, T, ns), np.int32); nact = np.empty((nb, T, ns), np.int32); nviol = np.empty((nb, T, ns), np.int32); hres = np.empty((nb, T, ns))
+    Xol = np.empty((nb, ns, N + 1, nx)) if return_ol else None
+    Uol = np.empty((nb, ns, N, mb)) if return_ol else None
+    Lam = np.empty((nb, ns, N, nd)) if return_ol else None
+    Eol = np.empty((nb, ns, N, nd)) if return_ol else None
+    U0 = np.empty((nb, ns, mb)); XT = np.empty((nb, ns, nx)); info = np.zeros((nb, ns, MPC_QP_INFO_STRIDE))
+    rc = lib.tmpc_mpc_qp_soft_batch_host(nb, p, nx, mb, nd, N, ns, T, int(k0), _dptr(A), _dptr(B), _dptr(H), _dptr(q), _dptr(Pf), _dptr(D), _iptr(ndcnt), _dptr(d),
+                                         _dptr(X0), float(tol), int(max_iter), _dptr(U0), _dptr(XT), _dptr(info), _dptr(X), _dptr(U), _iptr(iters), _iptr(nact),
+                                         _dptr(hres), _dptr(Xol), _dptr(Uol), _dptr(Lam), _dptr(penalty), _dptr(Eol), _iptr(nviol))
+    if rc == -1:
+        raise ValueError(lib.tmpc_last_error().decode())
+    _check_lqr(lib, rc, 'tmpc_mpc_qp_soft_batch_host')
+    out = _mpc_qp_views(U0, XT, info, X, U, iters, nact, hres, Xol, Uol, Lam, lambda a: a.transpose(0, 2, 1, 3), lambda a: a.transpose(0, 2, 1))
+    out.update(Eol=Eol, nviol=nviol.transpose(0, 2, 1))
+    return out
+
+
+def mpc_qp_soft_batch_device(A, B, H, q, Pf, D, ndcnt, d, penalty, X0, N, T, k0, tol, max_iter, return_traj, return_ol):
+    """tmpc_mpc_qp_soft_batch_device on validated, contiguous torch tensors of one GPU -> the dict of mpc_qp_soft_batch_host with torch tensors."""
+    import torch
+    lib = load_library()
+    nb, p, nx, mb = B.shape
+    ns, T, N = X0.shape[1], int(T), int(N)
+    nd = D.shape[2]
+    dev = A.device
+    f64 = lambda *sh: torch.empty(sh, dtype=torch.float64, device=dev)
+    i32 = lambda *sh: torch.empty(sh, dtype=torch.int32, device=dev)
+    X = f64(nb, T + 1, ns, nx) if return_traj else None
+    U = f64(nb, T, ns, mb) if return_traj else None
+    iters = i32(nb, T, ns); nact = i32(nb, T, ns); nviol = i32(nb, T, ns); hres = f64(nb, T, ns)
+    Xol = f64(nb, ns, N + 1, nx) if return_ol else None
+    Uol = f64(nb, ns, N, mb) if return_ol else None
+    Lam = f64(nb, ns, N, nd) if return_ol else None
+    Eol = f64(nb, ns, N, nd) if return_ol else None
+    U0 = f64(nb, ns, mb); XT = f64(nb, ns, nx); info = torch.zeros((nb, ns, MPC_QP_INFO_STRIDE), dtype=torch.float64, device=dev)
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+    with torch.cuda.device(dev):
+        torch.cuda.current_stream(dev).synchronize()      # the entry runs on the null stream: the inputs must be complete
+        rc = lib.tmpc_mpc_qp_soft_batch_device(nb, p, nx, mb, nd, N, ns, T, int(k0), ptr(A), ptr(B), ptr(H), ptr(q), ptr(Pf), ptr(D), ptr(ndcnt), ptr(d), ptr(X0),
+                                               float(tol), int(max_iter), ptr(U0), ptr(XT), ptr(info), ptr(X), ptr(U), ptr(iters), ptr(nact), ptr(hres), ptr(Xol),
+                                               ptr(Uol), ptr(Lam), ptr(penalty), ptr(Eol), ptr(nviol))
+    if rc == -1:
+        raise ValueError(lib.tmpc_last_error().decode())
+    _check_lqr(lib, rc, 'tmpc_mpc_qp_soft_batch_device')
+    out = _mpc_qp_views(U0, XT, info, X, U, iters, nact, hres, Xol, Uol, Lam, lambda a: a.permute(0, 2, 1, 3), lambda a: a.permute(0, 2, 1))
+    out.update(Eol=Eol, nviol=nviol.permute(0, 2, 1))
+    return out
 
 
 def cr_schedule(p):

@@ -2216,19 +2216,21 @@ static thread_local EigScratch g_mpc_qp_ws;           // workspace slots of both
 
 static int mpc_qp_launch(int nb, int p, int nx, int mb, int nd, int N, int ns, int T, int k0, const double* A, const double* B, const double* H, const double* q,
                          const double* Pf, const double* D, const int32_t* ndcnt, const double* d, const double* X0, double tol, int max_iter, double* U0,
-                         double* XT, double* info, double* X, double* U, int32_t* iters, int32_t* nact, double* hres, double* Xol, double* Uol, double* Lam) {
-  const MpcQpLds L = mpc_qp_lds(nx, mb, nd);
-  const size_t lds_bytes = (size_t)L.total * sizeof(double);
-  const long long ninst = (long long)nb * ns, per = mpc_qp_ws_doubles(nx, mb, nd, N) * 8;
+                         double* XT, double* info, double* X, double* U, int32_t* iters, int32_t* nact, double* hres, double* Xol, double* Uol, double* Lam,
+                         const double* penalty = nullptr, double* Eol = nullptr, int32_t* nviol = nullptr) {
+  // penalty: the SOFT instantiation with its longer LDS layout and workspace slots; without it the hard kernel (Eol, nviol are not passed then)
+  const size_t lds_bytes = (size_t)(penalty ? mpc_qp_soft_lds(nx, mb, nd).total : mpc_qp_lds(nx, mb, nd).total) * sizeof(double);
+  const long long ninst = (long long)nb * ns, per = (penalty ? mpc_qp_soft_ws_doubles(nx, mb, nd, N) : mpc_qp_ws_doubles(nx, mb, nd, N)) * 8;
   long long slots = ninst < MQ_SLOTS ? ninst : MQ_SLOTS;
   if (slots * per > MQ_WS_CAP_BYTES) slots = MQ_WS_CAP_BYTES / per;
   if (slots < 1) slots = 1;
   HIPCHK(g_mpc_qp_ws.reserve((size_t)(slots * per)));
-  HIPCHK(hipFuncSetAttribute((const void*)k_mpc_qp, hipFuncAttributeMaxDynamicSharedMemorySize, LQR_LDS_BYTES));
+  auto kern = penalty ? k_mpc_qp<true> : k_mpc_qp<false>;
+  HIPCHK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LQR_LDS_BYTES));
   int lcw = 0;
   while ((1 << lcw) < nx + mb) ++lcw;
-  hipLaunchKernelGGL(k_mpc_qp, dim3((unsigned)slots), dim3(LQR_NT), lds_bytes, 0, p, nx, mb, nd, lcw, N, ns, T, k0, ninst, A, B, H, q, Pf, D, (const int*)ndcnt, d,
-                     X0, tol, max_iter, (double*)g_mpc_qp_ws.p, U0, XT, info, X, U, (int*)iters, (int*)nact, hres, Xol, Uol, Lam);
+  hipLaunchKernelGGL(kern, dim3((unsigned)slots), dim3(LQR_NT), lds_bytes, 0, p, nx, mb, nd, lcw, N, ns, T, k0, ninst, A, B, H, q, Pf, D, (const int*)ndcnt, d,
+                     X0, tol, max_iter, (double*)g_mpc_qp_ws.p, U0, XT, info, X, U, (int*)iters, (int*)nact, hres, Xol, Uol, Lam, penalty, Eol, (int*)nviol);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(0));
   return TMPC_OK;
@@ -2291,6 +2293,106 @@ int tmpc_mpc_qp_batch_host(int nb, int p, int nx, int mb, int nd, int N, int ns,
   if (Lam && cL) HIPCHK(hipMemcpy(Lam, dL, cL * 8, hipMemcpyDeviceToHost));
   if (iters) HIPCHK(hipMemcpy(iters, dit, cS * sizeof(int32_t), hipMemcpyDeviceToHost));
   if (nact) HIPCHK(hipMemcpy(nact, dna, cS * sizeof(int32_t), hipMemcpyDeviceToHost));
+  return TMPC_OK;
+}
+
+// The same entries with soft rows (tmpc_mpc_qp.h, the SOFT instantiation).  penalty NULL: the hard kernel, Eol and nviol zero.
+static int mpc_qp_soft_check(const char* who, int nx, int mb, int nd, int N, const void* penalty) {
+  if (!penalty) return TMPC_OK;
+  if (nd < 1) {
+    snprintf(g_err, sizeof(g_err), "%s: bad argument (penalty describes the rows of D; got nd = %d)", who, nd);
+    return TMPC_E_ARG;
+  }
+  const long long bytes = (long long)mpc_qp_soft_lds(nx, mb, nd).total * (long long)sizeof(double);
+  if (bytes > LQR_LDS_BYTES) {
+    snprintf(g_err, sizeof(g_err), "%s: nx = %d, nu = %d with room for %d soft rows per stage needs %lld bytes of LDS (limit %d)", who, nx, mb, nd, bytes, LQR_LDS_BYTES);
+    return TMPC_E_UNSUPPORTED;
+  }
+  return TMPC_OK;
+}
+
+int tmpc_mpc_qp_soft_batch_device(int nb, int p, int nx, int mb, int nd, int N, int ns, int T, int k0, const double* A, const double* B, const double* H,
+                                  const double* q, const double* Pf, const double* D, const int32_t* ndcnt, const double* d, const double* X0, double tol,
+                                  int max_iter, double* U0, double* XT, double* info, double* X, double* U, int32_t* iters, int32_t* nact, double* hres,
+                                  double* Xol, double* Uol, double* Lam, const double* penalty, double* Eol, int32_t* nviol) {
+  const char* who = "tmpc_mpc_qp_soft_batch_device";
+  int rc = mpc_qp_check(who, nb, p, nx, mb, nd, N, ns, T, k0, A, B, H, D, ndcnt, d, X0, tol, max_iter, U0, XT, info);
+  if (rc == TMPC_OK) rc = mpc_qp_soft_check(who, nx, mb, nd, N, penalty);
+  if (rc != TMPC_OK) return rc;
+  if (!penalty) {
+    if (Eol && nd > 0) HIPCHK(hipMemsetAsync(Eol, 0, (size_t)nb * ns * N * nd * 8, 0));
+    if (nviol) HIPCHK(hipMemsetAsync(nviol, 0, (size_t)nb * T * ns * sizeof(int32_t), 0));
+  }
+  return mpc_qp_launch(nb, p, nx, mb, nd, N, ns, T, k0, A, B, H, q, Pf, D, ndcnt, d, X0, tol, max_iter, U0, XT, info, X, U, iters, nact, hres, Xol, Uol, Lam,
+                       penalty, penalty ? Eol : nullptr, penalty ? nviol : nullptr);
+}
+
+static thread_local EigScratch g_mpc_qp_soft_scratch;      // device images of penalty | Eol | nviol of the host entry
+
+int tmpc_mpc_qp_soft_batch_host(int nb, int p, int nx, int mb, int nd, int N, int ns, int T, int k0, const double* A, const double* B, const double* H,
+                                const double* q, const double* Pf, const double* D, const int32_t* ndcnt, const double* d, const double* X0, double tol,
+                                int max_iter, double* U0, double* XT, double* info, double* X, double* U, int32_t* iters, int32_t* nact, double* hres, double* Xol,
+                                double* Uol, double* Lam, const double* penalty, double* Eol, int32_t* nviol) {
+  const char* who = "tmpc_mpc_qp_soft_batch_host";
+  if (!penalty) {                                                            // the hard entry; no slack, no violated row
+    const int rc = tmpc_mpc_qp_batch_host(nb, p, nx, mb, nd, N, ns, T, k0, A, B, H, q, Pf, D, ndcnt, d, X0, tol, max_iter, U0, XT, info, X, U, iters, nact, hres,
+                                          Xol, Uol, Lam);
+    if (rc != TMPC_OK) return rc;
+    if (Eol) for (size_t i = 0; i < (size_t)nb * ns * N * nd; ++i) Eol[i] = 0.0;
+    if (nviol) for (size_t i = 0; i < (size_t)nb * T * ns; ++i) nviol[i] = 0;
+    return TMPC_OK;
+  }
+  int rc = mpc_qp_check(who, nb, p, nx, mb, nd, N, ns, T, k0, A, B, H, D, ndcnt, d, X0, tol, max_iter, U0, XT, info);
+  if (rc == TMPC_OK) rc = mpc_qp_soft_check(who, nx, mb, nd, N, penalty);
+  if (rc != TMPC_OK) return rc;
+  const size_t st = (size_t)nb * p, sn = (size_t)nb * ns;
+  if (ndcnt) for (size_t i = 0; i < st; ++i) if (ndcnt[i] < 0 || ndcnt[i] > nd) {
+    snprintf(g_err, sizeof(g_err), "%s: ndcnt[%zu][%zu] = %d outside 0 .. nd = %d", who, i / p, i % p, (int)ndcnt[i], nd);
+    return TMPC_E_ARG;
+  }
+  for (size_t i = 0; i < st * nd; ++i) if (!(penalty[i] > 0.0)) {
+    snprintf(g_err, sizeof(g_err), "%s: penalty[%zu][%zu][%zu] = %g: > 0 expected (+inf: a hard row)", who, i / nd / p, i / nd % p, i % nd, penalty[i]);
+    return TMPC_E_ARG;
+  }
+  // the inputs and outputs of the hard entry pass through device buffers of this entry: A | B | H | q | Pf | D | d | X0 | penalty, then the outputs
+  const size_t n = (size_t)nx + mb;
+  const size_t cA = st * nx * nx, cB = st * nx * mb, cH = st * n * n, cq = q ? st * n : 0, cPf = Pf ? cA : 0, cD = st * nd * n, cd = st * nd, c0 = sn * nx;
+  const size_t cU0 = sn * mb, cI = sn * MQ_INFO, cS = sn * T, cX = X ? sn * (T + 1) * nx : 0, cU = U ? sn * T * mb : 0, ch = hres ? cS : 0;
+  const size_t cXo = Xol ? sn * (N + 1) * nx : 0, cUo = Uol ? sn * N * mb : 0, cL = Lam ? sn * N * nd : 0, cE = Eol ? sn * N * nd : 0;
+  const size_t cN = ndcnt ? (st + 1) / 2 : 0, cit = iters ? (cS + 1) / 2 : 0, cna = nact ? (cS + 1) / 2 : 0, cnv = nviol ? (cS + 1) / 2 : 0;   // int32, in doubles
+  HIPCHK(g_mpc_qp_soft_scratch.reserve((cA + cB + cH + cq + cPf + cD + 2 * cd + 2 * c0 + cU0 + cI + cX + cU + ch + cXo + cUo + cL + cE + cN + cit + cna + cnv + 1) * 8));
+  double* dA = (double*)g_mpc_qp_soft_scratch.p; double* dB = dA + cA; double* dH = dB + cB; double* dq = dH + cH; double* dPf = dq + cq; double* dD = dPf + cPf;
+  double* dd = dD + cD; double* dP = dd + cd; double* d0 = dP + cd; double* dU0 = d0 + c0; double* dXT = dU0 + cU0; double* dI = dXT + c0; double* dX = dI + cI;
+  double* dU = dX + cX; double* dh = dU + cU; double* dXo = dh + ch; double* dUo = dXo + cXo; double* dL = dUo + cUo; double* dE = dL + cL;
+  int32_t* dN = (int32_t*)(dE + cE); int32_t* dit = (int32_t*)((double*)dN + cN); int32_t* dna = (int32_t*)((double*)dit + cit);
+  int32_t* dnv = (int32_t*)((double*)dna + cna);
+  HIPCHK(hipMemcpy(dA, A, cA * 8, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dB, B, cB * 8, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dH, H, cH * 8, hipMemcpyHostToDevice));
+  if (q) HIPCHK(hipMemcpy(dq, q, cq * 8, hipMemcpyHostToDevice));
+  if (Pf) HIPCHK(hipMemcpy(dPf, Pf, cPf * 8, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dD, D, cD * 8, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dd, d, cd * 8, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dP, penalty, cd * 8, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(d0, X0, c0 * 8, hipMemcpyHostToDevice));
+  if (ndcnt) HIPCHK(hipMemcpy(dN, ndcnt, st * sizeof(int32_t), hipMemcpyHostToDevice));
+  const int rl = mpc_qp_launch(nb, p, nx, mb, nd, N, ns, T, k0, dA, dB, dH, q ? dq : nullptr, Pf ? dPf : nullptr, dD, ndcnt ? dN : nullptr, dd, d0, tol, max_iter,
+                               dU0, dXT, dI, X ? dX : nullptr, U ? dU : nullptr, iters ? dit : nullptr, nact ? dna : nullptr, hres ? dh : nullptr,
+                               Xol ? dXo : nullptr, Uol ? dUo : nullptr, Lam ? dL : nullptr, dP, Eol ? dE : nullptr, nviol ? dnv : nullptr);
+  if (rl != TMPC_OK) return rl;
+  HIPCHK(hipMemcpy(U0, dU0, cU0 * 8, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(XT, dXT, c0 * 8, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(info, dI, cI * 8, hipMemcpyDeviceToHost));
+  if (X) HIPCHK(hipMemcpy(X, dX, cX * 8, hipMemcpyDeviceToHost));
+  if (U) HIPCHK(hipMemcpy(U, dU, cU * 8, hipMemcpyDeviceToHost));
+  if (hres) HIPCHK(hipMemcpy(hres, dh, cS * 8, hipMemcpyDeviceToHost));
+  if (Xol) HIPCHK(hipMemcpy(Xol, dXo, cXo * 8, hipMemcpyDeviceToHost));
+  if (Uol) HIPCHK(hipMemcpy(Uol, dUo, cUo * 8, hipMemcpyDeviceToHost));
+  if (Lam) HIPCHK(hipMemcpy(Lam, dL, cL * 8, hipMemcpyDeviceToHost));
+  if (Eol) HIPCHK(hipMemcpy(Eol, dE, cE * 8, hipMemcpyDeviceToHost));
+  if (iters) HIPCHK(hipMemcpy(iters, dit, cS * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (nact) HIPCHK(hipMemcpy(nact, dna, cS * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (nviol) HIPCHK(hipMemcpy(nviol, dnv, cS * sizeof(int32_t), hipMemcpyDeviceToHost));
   return TMPC_OK;
 }
 

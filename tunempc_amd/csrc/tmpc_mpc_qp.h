@@ -3,7 +3,7 @@
 //   min  sum_{j<N} (1/2 z_j' H_k z_j + q_k' z_j) + 1/2 x_N' Pf_{k_N} x_N,   z_j = [x_j; u_j],   k = k_j = (k0 + j) mod p,
 //   s.t. x_{j+1} = A_k x_j + B_k u_j,  x_0 given,   D_k z_j <= d_k (first ndcnt_k rows),   j = 0 .. N-1,
 // solved T times in a row: step t starts at phase (k0 + t) mod p, applies u_0 and moves x <- A_k x + B_k u_0 on the linear plant.
-// Not served: equality rows J, the terminal constraint x_N = 0, slack penalties, warm starts between the steps, the nonlinear plant.
+// Not served: equality rows J, the terminal constraint x_N = 0, quadratic slack penalties, warm starts between the steps, the nonlinear plant.
 //
 // Method: a primal-dual interior-point method with Mehrotra's predictor-corrector, started infeasible (z = 0 but x_0, s_i = max(d_i, 1), lam_i = 1).  The
 // multipliers of the dynamics are not variables: they are the adjoint of the iterate, pi_N = Pf x_N, [pi_j; r_u] = H z_j + q + D' lam_j + [A B]' pi_{j+1}, so
@@ -32,6 +32,26 @@
 //
 // Statuses: 0 converged at every step, 1 max_iter reached (an infeasible instance ends here), 2 a stage matrix S not positive definite, 3 non-finite.  An
 // instance that fails at step t keeps what it logged before; U, hres from t on, X from t + 1 on and XT are NaN, iters beyond t and nact from t on are -1.
+//
+// Soft rows (the SOFT instantiation; the reference's preprocessing.add_mpc_slacks, exact L1 penalties): with penalty c_{k,i} < inf row i of stage k reads
+//   D_i z - e_i <= d_i,  e_i >= 0,  cost c_i e_i   (penalty = +inf: the hard row above; hard and soft rows mix freely within a stage).
+// The slack e and the multiplier nu of e >= 0 are eliminated per row, not lifted into the inputs, so the stage matrices keep their size.  The rules
+// (tests/mpc_qp_soft_reference.py states the same ones):
+//   start      s = max(d, 1), lam = nu = c / 2, e = s: stationarity in e, c - lam - nu = 0, holds, and both pairs of the row carry the same product; dnu = -dlam and
+//              the one step length keep it at every iterate (nu is kept as a variable of its own: c - lam would lose it to cancellation on a violated row);
+//   residual   r_in = D z - e + s - d, scaled by max(1, |d|) like a hard row's;
+//   weights    from D dz - de + ds - rho dlam = -r_in, s dlam + lam ds = c1 - s lam, -e dlam + nu de = c2 - e nu:  dlam = w (D dz + beta),
+//              w = 1 / (s / lam + e / nu + rho),  beta = r_in - s + e + c1 / lam - c2 / nu,  de = -e + c2 / nu + (e / nu) dlam,  ds = -r_in - D dz + de + rho dlam:
+//              the Newton system is the same Riccati pass with another weight and right-hand side on that row (h gets D' (lam + w (r_in - s + e)), the
+//              corrector column is w (c1 / lam - c2 / nu)); rho has the role it has on a hard row;
+//   corrector  c1 = sigma mu - ds_aff dlam_aff,  c2 = sigma mu + de_aff dlam_aff;
+//   mu, sigma  every pair counts once: mu = (sum s lam + sum_soft e nu) / (rows + soft rows), mu_aff likewise;
+//   step       alpha_max runs over s, lam and, on soft rows, e and nu;
+//   stop       unchanged; max lam is taken over lam alone (nu ~ c wherever a row is not violated: a threshold that grew with c would loosen the test).
+// hres = max(D z - d) stays and is positive when a soft row of the applied step is violated; nact stays lam > s; nviol counts the rows of stage 0 with e > nu.
+// A penalty <= 0 or NaN makes the instance status 3 before its first step.  The LDS vectors e, nu, c lie after MpcQpLds::total (mpc_qp_soft_lds), the
+// workspace arrays E, NU, dE, C2 (c2 / nu of the corrector) [N][nd] after mpc_qp_ws_doubles (mpc_qp_soft_ws_doubles).  With SOFT = false the kernel is the
+// hard one statement by statement, and a soft launch whose penalties are all +inf takes the hard statements on every row: both give the same bits.
 #pragma once
 #include "tmpc_closed_loop.h"
 
@@ -65,6 +85,20 @@ __host__ __device__ inline MpcQpLds mpc_qp_lds(int nx, int mb, int nd) {
 __host__ __device__ inline long long mpc_qp_ws_doubles(int nx, int mb, int nd, int N) {
   const long long n = nx + mb;
   return 2LL * (N + 1) * n + 6LL * N * nd + (long long)N * nx + (long long)N * mb * (n + 1);
+}
+
+// The SOFT instantiation: the hard layout, then the vectors e, nu, c of the stage [nd] each; the hard workspace, then E, NU, dE, C2 [N][nd] each.
+struct MpcQpSoftLds { MpcQpLds h; int oEs, oNu, oC, total; };
+__host__ __device__ inline MpcQpSoftLds mpc_qp_soft_lds(int nx, int mb, int nd) {
+  MpcQpSoftLds l;
+  l.h = mpc_qp_lds(nx, mb, nd);
+  l.oEs = l.h.total; l.oNu = l.oEs + nd; l.oC = l.oNu + nd;
+  const long long total = (long long)l.oC + nd;
+  l.total = total > 0x7fffffffLL / 8 ? 0x7fffffff / 8 : (int)total;
+  return l;
+}
+__host__ __device__ inline long long mpc_qp_soft_ws_doubles(int nx, int mb, int nd, int N) {
+  return mpc_qp_ws_doubles(nx, mb, nd, N) + 4LL * N * nd;
 }
 
 __device__ __forceinline__ double mq_dot(const double* __restrict__ a, const double* __restrict__ b, int len) {
@@ -102,7 +136,9 @@ __device__ __forceinline__ void mq_fetch(double* El, double* Hl, double* Dl, int
 // H [nb][p][n][n], q [nb][p][n] or null, Pf [nb][p][nx][nx] or null, D [nb][p][nd][n] and d [nb][p][nd] (null when nd = 0), ndcnt [nb][p] or null (all nd rows;
 // counts are clamped to 0 .. nd), X0 [nb][ns][nx]; ws: gridDim.x slots of mpc_qp_ws_doubles.  Outputs: U0 [nb][ns][mb], XT [nb][ns][nx], info [nb][ns][8];
 // each or null: X [nb][T+1][ns][nx], U [nb][T][ns][mb], iters, nact int [nb][T][ns], hres [nb][T][ns], Xol [nb][ns][N+1][nx], Uol [nb][ns][N][mb],
-// Lam [nb][ns][N][nd] (the open-loop solution of step 0).
+// Lam [nb][ns][N][nd] (the open-loop solution of step 0).  SOFT: penalty [nb][p][nd] (+inf: hard row), and each or null Eol [nb][ns][N][nd], nviol int
+// [nb][T][ns]; ws: gridDim.x slots of mpc_qp_soft_ws_doubles, LDS of mpc_qp_soft_lds.  Without SOFT the three are not read or written.
+template <bool SOFT>
 __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd, int lcw, int N, int ns, int T, int k0, long long ninst,
                                                    const double* __restrict__ Ag, const double* __restrict__ Bg, const double* __restrict__ Hg,
                                                    const double* __restrict__ qg, const double* __restrict__ Pfg, const double* __restrict__ Dg,
@@ -110,7 +146,8 @@ __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd
                                                    int max_iter, double* wsg, double* __restrict__ U0g, double* __restrict__ XTg, double* __restrict__ infog,
                                                    double* __restrict__ Xg, double* __restrict__ Ug, int* __restrict__ itersg, int* __restrict__ nactg,
                                                    double* __restrict__ hresg, double* __restrict__ Xolg, double* __restrict__ Uolg,
-                                                   double* __restrict__ Lamg) {
+                                                   double* __restrict__ Lamg, const double* __restrict__ peng, double* __restrict__ Eolg,
+                                                   int* __restrict__ nviolg) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
   const int n = nx + mb;
   const MpcQpLds Ly = mpc_qp_lds(nx, mb, nd);
@@ -124,12 +161,14 @@ __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int cw = 1 << lcw, tx = tid & (cw - 1), ty = tid >> lcw, rs = LQR_NT >> lcw;
   const double qnan = __longlong_as_double(0x7ff8000000000000LL);
-  const long long wsn = mpc_qp_ws_doubles(nx, mb, nd, N);
+  const long long wsn = SOFT ? mpc_qp_soft_ws_doubles(nx, mb, nd, N) : mpc_qp_ws_doubles(nx, mb, nd, N);
   double* ws = wsg + (size_t)blockIdx.x * wsn;
   double* Z = ws; double* dZ = Z + (size_t)(N + 1) * n; double* Sg = dZ + (size_t)(N + 1) * n; double* Lg = Sg + (size_t)N * nd; double* dSg = Lg + (size_t)N * nd;
   double* dLg = dSg + (size_t)N * nd; double* RIN = dLg + (size_t)N * nd; double* COR = RIN + (size_t)N * nd; double* RDYN = COR + (size_t)N * nd;
   double* FAC = RDYN + (size_t)N * nx;
   const int fs = mb * (n + 1);                                               // doubles of [Y | R | y] per stage
+  double* Eg = FAC + (size_t)N * fs; double* NUg = Eg + (size_t)N * nd; double* dEg = NUg + (size_t)N * nd; double* C2g = dEg + (size_t)N * nd;   // (SOFT only)
+  double* ev = lds + Ly.total; double* nuv = ev + nd; double* cv = nuv + nd;                                                                   // (SOFT only)
 
   for (long long inst = blockIdx.x; inst < ninst; inst += gridDim.x) {
     const size_t b = (size_t)(inst / ns), si = (size_t)(inst % ns);
@@ -138,6 +177,7 @@ __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd
     const double* D = nd > 0 ? Dg + b * p * nd * n : nullptr; const double* dd = nd > 0 ? dg + b * p * nd : nullptr;
     const int* ndcnt = ndcntg ? ndcntg + b * p : nullptr;
     auto rows_of = [&](int k) { return nd > 0 ? (ndcnt ? max(0, min(nd, ndcnt[k])) : nd) : 0; };
+    const double* pen = SOFT ? peng + b * p * nd : nullptr;
 
     if (tid < nx) {
       const double v = X0g[(b * ns + si) * nx + tid];
@@ -147,21 +187,40 @@ __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd
     __syncthreads();
     int status = MQ_OK, done = 0, it_total = 0, it_max = 0;
     double mu = 0.0, rp = 0.0, rd = 0.0, pivmin = INFINITY;
+    if (SOFT) {                                                              // a penalty <= 0 or NaN: the instance ends before its first step
+      double bad = 0.0;
+      for (int e = tid; e < p * nd; e += LQR_NT) if (!(pen[e] > 0.0)) bad = 1.0;
+      if (mq_block<1>(bad, red, tid) > 0.0) status = MQ_NONFINITE;
+    }
 
     for (int t = 0; t < T; ++t) {
       const int k0s = (k0 + t % p) % p;
-      int its = 0, nact = -1;
+      int its = 0, nact = -1, nviol = -1;
       double hres = qnan;
       if (status == MQ_OK) {                                                 // (uniform: status is the same in every thread)
         // ---- start of the step: z = 0 but x_0, s = max(d, 1), lam = 1, no direction
         int mt = 0;
         for (int j = 0; j < N; ++j) mt += rows_of((k0s + j % p) % p);
+        // (SOFT) soft_at(e): entry e = j nd + i of the [N][nd] arrays is a soft row of this step
+        auto soft_at = [&](int e) { const int j = e / nd, i = e - j * nd, k = (k0s + j % p) % p; return i < rows_of(k) && pen[k * nd + i] < INFINITY; };
         for (int e = tid; e < (N + 1) * n; e += LQR_NT) { Z[e] = e < nx ? xcur[e] : 0.0; dZ[e] = 0.0; }
         for (int e = tid; e < N * nd; e += LQR_NT) {
           const int j = e / nd, i = e - j * nd, k = (k0s + j % p) % p;
           const bool on = i < rows_of(k);
           Sg[e] = on ? fmax(dd[k * nd + i], 1.0) : 1.0; Lg[e] = on ? 1.0 : 0.0;
           dSg[e] = 0.0; dLg[e] = 0.0; RIN[e] = 0.0; COR[e] = 0.0;
+          if (SOFT) {                                                        // lam = nu = c / 2, e = s; zero on hard and absent rows
+            const bool sf = on && pen[k * nd + i] < INFINITY;
+            const double hc = sf ? 0.5 * pen[k * nd + i] : 0.0;
+            if (sf) Lg[e] = hc;
+            NUg[e] = hc; Eg[e] = sf ? Sg[e] : 0.0; dEg[e] = 0.0; C2g[e] = 0.0;
+          }
+        }
+        int mp = mt;                                                         // complementarity pairs: one per row, one more per soft row
+        if (SOFT) {
+          double cnt = 0.0;
+          for (int e = tid; e < N * nd; e += LQR_NT) if (soft_at(e)) cnt += 1.0;
+          mp = mt + (int)mq_block<0>(cnt, red, tid);
         }
         __syncthreads();
         const int kN = (k0s + N % p) % p;
@@ -186,14 +245,22 @@ __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd
             if (tid < n) { zv[tid] = Z[(size_t)j * n + tid]; qv[tid] = q ? q[k * n + tid] : 0.0; }
             if (tid >= 64 && tid < 64 + nx) xn[tid - 64] = Z[(size_t)(j + 1) * n + tid - 64];
             for (int i = tid; i < m; i += LQR_NT) { lamv[i] = Lg[(size_t)j * nd + i]; sv[i] = Sg[(size_t)j * nd + i]; ddv[i] = dd[k * nd + i]; }
+            if (SOFT) for (int i = tid; i < m; i += LQR_NT) { ev[i] = Eg[(size_t)j * nd + i]; nuv[i] = NUg[(size_t)j * nd + i]; cv[i] = pen[k * nd + i]; }
             __syncthreads();
             // ---- A: the residuals of the rows and of the dynamics, H z + q, Pi E
             for (int e = tid; e < m + nx + n; e += LQR_NT) {
               if (e < m) {
                 const double lam = lamv[e], s = sv[e];
-                const double r = mq_dot(Dl + e * ld, zv, n) + s - ddv[e];
-                const double w = lam / (s + MQ_RHO * lam);
-                rinv[e] = r; wv_[e] = w; bsv[e] = w * (r + MQ_RHO * lam);
+                double r = mq_dot(Dl + e * ld, zv, n) + s - ddv[e];
+                double w = lam / (s + MQ_RHO * lam);
+                double bs = w * (r + MQ_RHO * lam);
+                if (SOFT) if (cv[e] < INFINITY) {                            // lam + w beta of the predictor, beta = r_in - s + e
+                  const double ee = ev[e];
+                  r = mq_dot(Dl + e * ld, zv, n) - ee + s - ddv[e];
+                  w = 1.0 / (s / lam + ee / nuv[e] + MQ_RHO);
+                  bs = lam + w * (r - s + ee);
+                }
+                rinv[e] = r; wv_[e] = w; bsv[e] = bs;
                 RIN[(size_t)j * nd + e] = r;
                 a_rp = cl_absmax(a_rp, r / fmax(1.0, fabs(ddv[e]))); a_lam = cl_absmax(a_lam, lam);
               } else if (e < m + nx) {
@@ -290,11 +357,12 @@ __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd
           // ---- the figures of the iterate and the stop test
           double part = 0.0;
           for (int e = tid; e < N * nd; e += LQR_NT) part = fma(Lg[e], Sg[e], part);
+          if (SOFT) for (int e = tid; e < N * nd; e += LQR_NT) if (soft_at(e)) part = fma(Eg[e], NUg[e], part);
           const double sumc = mq_block<0>(part, red, tid);
           const double xmax = mq_block<1>(a_x, red, tid), lmax = mq_block<1>(a_lam, red, tid), gmax = mq_block<1>(a_g, red, tid);
           rp = fmax(mq_block<1>(a_rp, red, tid), mq_block<1>(a_dyn, red, tid) / fmax(1.0, xmax));
           rd = mq_block<1>(a_rd, red, tid) / fmax(1.0, gmax);
-          mu = mt > 0 ? sumc / mt : 0.0;
+          mu = mt > 0 ? sumc / mp : 0.0;
           if (!(rp < INFINITY && rd < INFINITY && fabs(mu) < INFINITY && lmax < INFINITY && xmax < INFINITY)) { status = MQ_NONFINITE; break; }
           if (rp <= tol && rd <= tol && mu <= MQ_MU_FACTOR * tol * fmax(1.0, lmax)) break;
           if (facfail) { status = MQ_NOT_CONVEX; break; }
@@ -308,11 +376,17 @@ __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd
               const double aa = fmin(1.0, alpha);
               part = 0.0;
               for (int e = tid; e < N * nd; e += LQR_NT) part = fma(Lg[e] + aa * dLg[e], Sg[e] + aa * dSg[e], part);
-              const double r3 = mq_block<0>(part, red, tid) / mt / mu;
+              if (SOFT) for (int e = tid; e < N * nd; e += LQR_NT) if (soft_at(e)) part = fma(Eg[e] + aa * dEg[e], NUg[e] - aa * dLg[e], part);
+              const double r3 = mq_block<0>(part, red, tid) / mp / mu;
               const double sigmu = r3 * r3 * r3 * mu;
               for (int e = tid; e < N * nd; e += LQR_NT) {
                 const int j = e / nd, i = e - j * nd;
                 COR[e] = i < rows_of((k0s + j % p) % p) ? (sigmu - dSg[e] * dLg[e]) / (Sg[e] + MQ_RHO * Lg[e]) : 0.0;
+                if (SOFT) if (soft_at(e)) {                                  // w (c1 / lam - c2 / nu), and c2 / nu for the forward sweep
+                  const double c2 = (sigmu + dEg[e] * dLg[e]) / NUg[e];
+                  COR[e] = ((sigmu - dSg[e] * dLg[e]) / Lg[e] - c2) / (Sg[e] / Lg[e] + Eg[e] / NUg[e] + MQ_RHO);
+                  C2g[e] = c2;
+                }
               }
               if (tid < nx) dxa[tid] = 0.0;                                  // dp_N
               __syncthreads();
@@ -361,6 +435,7 @@ __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd
               for (int i = tid; i < m; i += LQR_NT) {
                 lamv[i] = Lg[(size_t)j * nd + i]; sv[i] = Sg[(size_t)j * nd + i]; rinv[i] = RIN[(size_t)j * nd + i]; corv[i] = sweep ? COR[(size_t)j * nd + i] : 0.0;
               }
+              if (SOFT) for (int i = tid; i < m; i += LQR_NT) { ev[i] = Eg[(size_t)j * nd + i]; nuv[i] = NUg[(size_t)j * nd + i]; cv[i] = pen[k * nd + i]; }
               if (tid >= 64 && tid < 64 + nx) rdynv[tid - 64] = RDYN[(size_t)j * nx + tid - 64];
               __syncthreads();
               if (wave == 0) {                                               // du = -R^-1 (Y dx + y), column by column inside one wave
@@ -380,8 +455,18 @@ __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd
                 if (e < m) {
                   const double lam = lamv[e], s = sv[e], Dz = mq_dot(Dl + e * ld, dzv, n);
                   const double w = lam / (s + MQ_RHO * lam);
-                  const double dl = corv[e] - w * s + w * (rinv[e] + Dz);
-                  const double ds = -rinv[e] - Dz + MQ_RHO * dl;
+                  double dl = corv[e] - w * s + w * (rinv[e] + Dz);
+                  double ds = -rinv[e] - Dz + MQ_RHO * dl;
+                  if (SOFT) if (cv[e] < INFINITY) {
+                    const double ee = ev[e], nu = nuv[e];
+                    const double ws_ = 1.0 / (s / lam + ee / nu + MQ_RHO);
+                    dl = corv[e] + ws_ * (rinv[e] - s + ee + Dz);
+                    const double de = -ee + (sweep ? C2g[(size_t)j * nd + e] : 0.0) + (ee / nu) * dl;
+                    ds = -rinv[e] - Dz + de + MQ_RHO * dl;
+                    dEg[(size_t)j * nd + e] = de;
+                    if (de < 0.0) amin = fmin(amin, -ee / de);
+                    if (dl > 0.0) amin = fmin(amin, nu / dl);                // dnu = -dlam
+                  }
                   dLg[(size_t)j * nd + e] = dl; dSg[(size_t)j * nd + e] = ds;
                   if (ds < 0.0) amin = fmin(amin, -s / ds);
                   if (dl < 0.0) amin = fmin(amin, -lam / dl);
@@ -399,6 +484,7 @@ __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd
           // ================================================================ the step
           const double al = fmin(1.0, MQ_STEP_BACK * alpha);
           for (int e = tid; e < (N + 1) * n; e += LQR_NT) Z[e] = fma(al, dZ[e], Z[e]);
+          if (SOFT) for (int e = tid; e < N * nd; e += LQR_NT) if (soft_at(e)) { Eg[e] = fma(al, dEg[e], Eg[e]); NUg[e] = fma(-al, dLg[e], NUg[e]); }
           for (int e = tid; e < N * nd; e += LQR_NT) { Sg[e] = fma(al, dSg[e], Sg[e]); Lg[e] = fma(al, dLg[e], Lg[e]); }
           __syncthreads();
         }
@@ -418,6 +504,12 @@ __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd
         }
         hres = mq_block<1>(hmax, red, tid);
         nact = (int)mq_block<0>(cnt, red, tid);
+        if (SOFT) {
+          double cv_ = 0.0;
+          for (int i = tid; i < m; i += LQR_NT) if (Eg[i] > NUg[i]) cv_ += 1.0;
+          nviol = (int)mq_block<0>(cv_, red, tid);
+          if (t == 0 && Eolg) for (int e = tid; e < N * nd; e += LQR_NT) Eolg[((b * ns + si) * N) * nd + e] = Eg[e];
+        }
         if (t == 0) {
           if (Xolg) for (int e = tid; e < (N + 1) * nx; e += LQR_NT) { const int j = e / nx; Xolg[((b * ns + si) * (N + 1)) * nx + e] = Z[(size_t)j * n + e - j * nx]; }
           if (Uolg) for (int e = tid; e < N * mb; e += LQR_NT) { const int j = e / mb; Uolg[((b * ns + si) * N) * mb + e] = Z[(size_t)j * n + nx + e - j * mb]; }
@@ -447,6 +539,7 @@ __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd
           if (Xolg) for (int e = tid; e < (N + 1) * nx; e += LQR_NT) Xolg[((b * ns + si) * (N + 1)) * nx + e] = qnan;
           if (Uolg) for (int e = tid; e < N * mb; e += LQR_NT) Uolg[((b * ns + si) * N) * mb + e] = qnan;
           if (Lamg) for (int e = tid; e < N * nd; e += LQR_NT) Lamg[((b * ns + si) * N) * nd + e] = qnan;
+          if (SOFT) if (Eolg) for (int e = tid; e < N * nd; e += LQR_NT) Eolg[((b * ns + si) * N) * nd + e] = qnan;
         }
       }
       if (tid == 0) {
@@ -454,6 +547,7 @@ __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd
         if (itersg) itersg[o] = done >= t ? its : -1;
         if (nactg) nactg[o] = nact;
         if (hresg) hresg[o] = hres;
+        if (SOFT) if (nviolg) nviolg[o] = nviol;
       }
     }
     if (tid < nx) XTg[(b * ns + si) * nx + tid] = status == MQ_OK ? xcur[tid] : qnan;

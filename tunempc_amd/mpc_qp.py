@@ -6,16 +6,20 @@ lqr.py and closed_loop.py serve the laws of a FIXED active set.  This module sol
     min  sum_{j<N} (1/2 z_j' H_k z_j + q_k' z_j) + 1/2 x_N' Pf_{k_N} x_N,   z_j = [x_j; u_j],
     s.t. x_{j+1} = A_k x_j + B_k u_j,   D_k z_j <= d_k (first ndcnt_k rows of the stage),   j = 0 .. N-1,
 
+where a row may be SOFT (`penalty`, the reference's preprocessing.add_mpc_slacks: D_i z - e_i <= d_i, e_i >= 0 at the cost c_i e_i, an exact L1 penalty: the
+hard solution as long as c_i exceeds the row's multiplier, a violated row instead of an infeasible problem otherwise),
+
 with a primal-dual interior-point method (Mehrotra's predictor-corrector, Riccati recursion with a Cholesky factorisation per stage), one 256-thread workgroup
 per instance, the whole interior-point loop and all steps of the closed loop in one launch (csrc/tmpc_mpc_qp.h).
 
     mpc_qp_batch(A, B, H, X0, horizon, phase0=0, D=None, d=None, ...)              one step: u0, the open-loop X, U, lam
     mpc_closed_loop_batch(A, B, H, X0, horizon, steps, phase0=0, ...)              the receding-horizon loop on the linear plant
     mpc_step(A, B, Q, R, N, x0, horizon, ...)                                      one model in the reference's calling style
-    mpc_closed_loop_sim(A, B, Q, R, N, x0, horizon, steps, ...)                    -> the reference's log {'x', 'u', 'l', 'h'}
+    mpc_closed_loop_sim(A, B, Q, R, N, x0, horizon, steps, ...)                    -> the reference's log {'x', 'u', 'l', 'h'} (and 'usc' with penalty=)
+    slack_penalty(lam_h, active_set, slack_flag, factor)                           the reference's rule for the weights of the soft rows
 
-Not served: equality rows J, the terminal constraint x_N = 0, slack penalties (usc), warm starts between the steps, the nonlinear plant; there are no arguments
-for them.  Conventions as in lqr.py / closed_loop.py.  There is no CPU path: the solve runs in the HIP library or the call raises."""
+Not served: equality rows J, the terminal constraint x_N = 0, quadratic slack penalties, warm starts between the steps, the nonlinear plant; there are no
+arguments for them.  Conventions as in lqr.py / closed_loop.py.  There is no CPU path: the solve runs in the HIP library or the call raises."""
 import numpy as np
 
 from . import _lib
@@ -31,17 +35,21 @@ SLOTS = 512            # workgroups (workspace slots) of a launch at the most
 INFO_FIELDS = ('status', 'steps', 'iters_total', 'iters_max', 'mu', 'rp', 'rd', 'pivmin')
 
 
-def lds_layout(nx, nu, nd=0):
-    """mpc_qp_lds of csrc/tmpc_mpc_qp.h restated: dict bytes (LDS of a workgroup), ws_doubles (function of the horizon: doubles of workspace per slot)."""
+def lds_layout(nx, nu, nd=0, soft=False):
+    """mpc_qp_lds of csrc/tmpc_mpc_qp.h restated: dict bytes (LDS of a workgroup), ws_doubles (function of the horizon: doubles of workspace per slot).
+    soft: mpc_qp_soft_lds / mpc_qp_soft_ws_doubles, the layout of a call with penalty (the vectors e, nu, c after the hard layout, E, NU, dE, C2 after the hard
+    workspace)."""
     nx, nu, nd = int(nx), int(nu), int(nd)
     n = nx + nu
     ld, ldp, lv = (n + 1) | 1, nx | 1, max(n + 1, nd)
     total = nx * ld + nx * ldp + nx * ld + n * ld + nd * ld + 24 * lv + 8
+    if soft:
+        return dict(bytes=8 * (total + 3 * nd), ws_doubles=lambda N: 2 * (N + 1) * n + 6 * N * nd + N * nx + N * nu * (n + 1) + 4 * N * nd)
     return dict(bytes=8 * total, ws_doubles=lambda N: 2 * (N + 1) * n + 6 * N * nd + N * nx + N * nu * (n + 1))
 
 
-def _validate(who, A, B, H, X0, horizon, phase0, D, d, ndcnt, q, Pf, tol, max_iter, steps=1):
-    named = [('A', A), ('B', B), ('H', H), ('X0', X0)] + [(nm, x) for nm, x in (('D', D), ('d', d), ('q', q), ('Pf', Pf)) if x is not None]
+def _validate(who, A, B, H, X0, horizon, phase0, D, d, ndcnt, q, Pf, tol, max_iter, steps=1, penalty=None):
+    named = [('A', A), ('B', B), ('H', H), ('X0', X0)] + [(nm, x) for nm, x in (('D', D), ('d', d), ('q', q), ('Pf', Pf), ('penalty', penalty)) if x is not None]
     use_torch = _cl._check_kind(who, named)
     if len(A.shape) != 4 or A.shape[2] != A.shape[3]:
         raise ValueError('{}: A [nb, p, nx, nx] expected, got {}'.format(who, tuple(A.shape)))
@@ -66,6 +74,8 @@ def _validate(who, A, B, H, X0, horizon, phase0, D, d, ndcnt, q, Pf, tol, max_it
         raise ValueError('{}: D and d come together (the rows D z <= d), got {} without {}'.format(who, *(('d', 'D') if D is None else ('D', 'd'))))
     if D is None and ndcnt is not None:
         raise ValueError('{}: ndcnt describes the rows of D, which is None'.format(who))
+    if D is None and penalty is not None:
+        raise ValueError('{}: penalty describes the rows of D, which is None'.format(who))
     nd = 0
     if D is not None:
         if len(D.shape) != 4 or tuple(D.shape[:2]) != (nb, p) or int(D.shape[3]) != n or int(D.shape[2]) < 1:
@@ -96,16 +106,29 @@ def _validate(who, A, B, H, X0, horizon, phase0, D, d, ndcnt, q, Pf, tol, max_it
     lay = lds_layout(nx, nu, nd)
     if lay['bytes'] > LDS_BYTES:
         raise NotImplementedError('{}: nx = {}, nu = {} with room for {} rows per stage needs {} bytes of LDS (limit {})'.format(who, nx, nu, nd, lay['bytes'], LDS_BYTES))
+    if penalty is not None:
+        if tuple(penalty.shape) != (nb, p, nd):
+            raise ValueError('{}: penalty {} expected, got {}'.format(who, (nb, p, nd), tuple(penalty.shape)))
+        if not bool((penalty > 0).all()):                                   # (NaN fails the comparison)
+            raise ValueError('{}: penalty > 0 expected in every entry (inf: a hard row), got min {}'.format(who, float(penalty.min())))
+        soft = lds_layout(nx, nu, nd, soft=True)
+        if soft['bytes'] > LDS_BYTES:
+            raise NotImplementedError('{}: nx = {}, nu = {} with room for {} soft rows per stage needs {} bytes of LDS (limit {})'.format(
+                who, nx, nu, nd, soft['bytes'], LDS_BYTES))
     return use_torch, nd, int(horizon), T, k0
 
 
-def _run(who, A, B, H, X0, horizon, steps, phase0, D, d, ndcnt, q, Pf, tol, max_iter, return_traj, return_ol):
-    use_torch, nd, N, T, k0 = _validate(who, A, B, H, X0, horizon, phase0, D, d, ndcnt, q, Pf, tol, max_iter, steps)
-    A, B, H, X0, D, d, q, Pf = (lqr._contig(x, use_torch) for x in (A, B, H, X0, D, d, q, Pf))
+def _run(who, A, B, H, X0, horizon, steps, phase0, D, d, ndcnt, q, Pf, tol, max_iter, return_traj, return_ol, penalty=None):
+    use_torch, nd, N, T, k0 = _validate(who, A, B, H, X0, horizon, phase0, D, d, ndcnt, q, Pf, tol, max_iter, steps, penalty)
+    A, B, H, X0, D, d, q, Pf, penalty = (lqr._contig(x, use_torch) for x in (A, B, H, X0, D, d, q, Pf, penalty))
     if ndcnt is not None:
         ndcnt = ndcnt.contiguous() if use_torch else np.ascontiguousarray(ndcnt)
-    entry = _lib.mpc_qp_batch_device if use_torch else _lib.mpc_qp_batch_host
-    out = entry(A, B, H, q, Pf, D, ndcnt, d, X0, N, T, k0, float(tol), int(max_iter), bool(return_traj), bool(return_ol))
+    if penalty is None:
+        entry = _lib.mpc_qp_batch_device if use_torch else _lib.mpc_qp_batch_host
+        out = entry(A, B, H, q, Pf, D, ndcnt, d, X0, N, T, k0, float(tol), int(max_iter), bool(return_traj), bool(return_ol))
+    else:
+        entry = _lib.mpc_qp_soft_batch_device if use_torch else _lib.mpc_qp_soft_batch_host
+        out = entry(A, B, H, q, Pf, D, ndcnt, d, penalty, X0, N, T, k0, float(tol), int(max_iter), bool(return_traj), bool(return_ol))
     info = out['info']
     for i, name in enumerate(INFO_FIELDS):
         col = info[..., i]
@@ -117,11 +140,14 @@ def _run(who, A, B, H, X0, horizon, steps, phase0, D, d, ndcnt, q, Pf, tol, max_
     return out
 
 
-def mpc_qp_batch(A, B, H, X0, horizon, phase0=0, D=None, d=None, ndcnt=None, q=None, Pf=None, tol=TOL, max_iter=MAX_ITER, return_traj=True):
+def mpc_qp_batch(A, B, H, X0, horizon, phase0=0, D=None, d=None, ndcnt=None, q=None, Pf=None, tol=TOL, max_iter=MAX_ITER, return_traj=True, penalty=None):
     """One MPC step per (problem, initial deviation): A [nb,p,nx,nx], B [nb,p,nx,nu], H [nb,p,n,n] (used as (H + H') / 2), X0 [nb,ns,nx], fp64, n = nx + nu <= 64;
     the horizon-`horizon` QP from phase `phase0`.  Optional: the rows D [nb,p,nd,n], d [nb,p,nd] (D z <= d; ndcnt int32 [nb,p]: only the first ndcnt rows of a
     stage, None: all nd), q [nb,p,n] (linear cost), Pf [nb,p,nx,nx] (terminal weight 1/2 x_N' Pf[(phase0 + N) mod p] x_N); None: absent / zero.  Without rows
     this is the plain horizon-N LQ problem.  tol, max_iter: the stop rule of csrc/tmpc_mpc_qp.h (residuals and mu relative to the scale of the problem).
+    penalty [nb,p,nd] (fp64): inf a hard row, c > 0 a soft row (D_i z - e_i <= d_i, e_i >= 0, cost c e_i at every stage); None: every row hard, the call as it
+    was.  With a penalty the dict gains eps [nb,ns,N,nd] (the open-loop slacks; 0 on hard rows; None with return_traj=False) and nviol [nb,ns] int32 (rows of
+    stage 0 with e > nu), hres > 0 tells a violated soft row, and a state outside a soft bound is no longer status 1.
 
     numpy arrays run through the host entry; torch tensors on a GPU through the device entry (torch tensors out, the inputs are not copied).  Both run the same
     kernel and agree bit for bit; the numbers of an instance do not depend on ns or on the other instances of the call.
@@ -131,28 +157,35 @@ def mpc_qp_batch(A, B, H, X0, horizon, phase0=0, D=None, d=None, ndcnt=None, q=N
     (0 converged, 1 max_iter reached -- an infeasible instance ends here --, 2 a stage matrix not positive definite: not convex along the path, 3 non-finite), steps,
     iters_total, iters_max [nb,ns] int32, mu, rp, rd, pivmin [nb,ns], info [nb,ns,8].  An instance with status != 0 returns NaN (nact -1); the others are not
     affected.  ValueError: shapes, dtypes, mixed numpy / torch, horizon < 1, phase0 outside 0 .. p-1, D without d, ndcnt outside 0 .. nd, tol <= 0,
-    max_iter < 1; NotImplementedError: n > 64, (nx, nu, nd) beyond the 160 KB LDS layout (lds_layout)."""
-    o = _run('mpc_qp_batch', A, B, H, X0, horizon, 1, phase0, D, d, ndcnt, q, Pf, tol, max_iter, False, return_traj)
+    max_iter < 1, penalty without D or with an entry <= 0 or NaN; NotImplementedError: n > 64, (nx, nu, nd) beyond the 160 KB LDS layout (lds_layout; with a
+    penalty the soft layout)."""
+    o = _run('mpc_qp_batch', A, B, H, X0, horizon, 1, phase0, D, d, ndcnt, q, Pf, tol, max_iter, False, return_traj, penalty)
     out = dict(u0=o['U0'], X=o['Xol'], U=o['Uol'], lam=o['Lam'], nact=o['nact'][..., 0], hres=o['hres'][..., 0], x1=o['XT'], info=o['info'])
+    if penalty is not None:
+        out.update(eps=o['Eol'], nviol=o['nviol'][..., 0])
     out.update({k: o[k] for k in INFO_FIELDS})
     return out
 
 
-def mpc_closed_loop_batch(A, B, H, X0, horizon, steps, phase0=0, D=None, d=None, ndcnt=None, q=None, Pf=None, tol=TOL, max_iter=MAX_ITER, return_traj=True):
+def mpc_closed_loop_batch(A, B, H, X0, horizon, steps, phase0=0, D=None, d=None, ndcnt=None, q=None, Pf=None, tol=TOL, max_iter=MAX_ITER, return_traj=True,
+                          penalty=None):
     """The receding-horizon loop: at t = 0 .. steps-1 the QP of mpc_qp_batch from phase (phase0 + t) mod p, cold-started, u_0 applied, x <- A_k x + B_k u_0 (the
     linear plant, as closed_loop_batch does), all steps in one launch.  Arguments as mpc_qp_batch.
 
     Returns dict: X [nb,ns,steps+1,nx], U [nb,ns,steps,nu] (None with return_traj=False), iters, nact [nb,ns,steps] int32, hres [nb,ns,steps], XT [nb,ns,nx],
     u0 [nb,ns,nu] (the first input of step 0) and the info fields of mpc_qp_batch (steps: steps finished).  An instance that fails at step t (status 1, 2, 3)
     keeps what it logged before: U, hres from t on, X from t + 1 on and XT are NaN, nact from t on and iters beyond t are -1.  X, U and the per-step logs are
-    permuted views of time-major arrays."""
-    o = _run('mpc_closed_loop_batch', A, B, H, X0, horizon, steps, phase0, D, d, ndcnt, q, Pf, tol, max_iter, return_traj, False)
+    permuted views of time-major arrays.  With penalty (as in mpc_qp_batch) the dict gains nviol [nb,ns,steps] int32 (-1 from a failed step on); hres > 0
+    at a step whose applied stage violates a soft row."""
+    o = _run('mpc_closed_loop_batch', A, B, H, X0, horizon, steps, phase0, D, d, ndcnt, q, Pf, tol, max_iter, return_traj, False, penalty)
     out = dict(X=o['X'], U=o['U'], iters=o['iters'], nact=o['nact'], hres=o['hres'], XT=o['XT'], u0=o['U0'], info=o['info'])
+    if penalty is not None:
+        out['nviol'] = o['nviol']
     out.update({k: o[k] for k in INFO_FIELDS})
     return out
 
 
-def _stack_one(who, A, B, Q, R, N, x0, D, d, q, Pf):
+def _stack_one(who, A, B, Q, R, N, x0, D, d, q, Pf, penalty=None):
     """The reference's calling style -> batched arrays of one problem and one state."""
     try:
         As, Bs, Hs, _ = lqr._stack_stages(A, B, Q, R, N)
@@ -163,9 +196,11 @@ def _stack_one(who, A, B, Q, R, N, x0, D, d, q, Pf):
     x = _to_array(x0).astype(np.float64).reshape(-1)
     if x.shape != (nx,):
         raise ValueError('{}: x0 must hold nx = {} entries, got {}'.format(who, nx, _to_array(x0).shape))
-    Ds = ds = cnt = None
+    Ds = ds = cnt = pens = None
     if (D is None) != (d is None):
         raise ValueError('{}: D and d come together (the rows D z <= d)'.format(who))
+    if D is None and penalty is not None:
+        raise ValueError('{}: penalty describes the rows of D, which is None'.format(who))
     if D is not None:
         Dl = [None if m is None else np.atleast_2d(_to_array(m)).astype(np.float64) for m in (D if isinstance(D, (list, tuple)) else [D] * p)]
         dl = [None if v is None else _to_array(v).astype(np.float64).reshape(-1) for v in (d if isinstance(d, (list, tuple)) else [d] * p)]
@@ -181,6 +216,17 @@ def _stack_one(who, A, B, Q, R, N, x0, D, d, q, Pf):
             for k in range(p):
                 if cnts[k]:
                     Ds[0, k, :cnts[k]] = Dl[k]; ds[0, k, :cnts[k]] = dl[k]
+        if penalty is not None:
+            pl = [None if v is None else _to_array(v).astype(np.float64).reshape(-1) for v in (penalty if isinstance(penalty, (list, tuple)) else [penalty] * p)]
+            if len(pl) != p or any(v is not None and v.shape != (cnts[k],) for k, v in enumerate(pl)):
+                raise ValueError('{}: penalty must be one vector or a list of p = {} vectors (None: a stage of hard rows) with one entry per row of D'.format(who, p))
+            if any(v is not None and not (v > 0).all() for v in pl):
+                raise ValueError('{}: penalty > 0 expected in every entry (inf: a hard row)'.format(who))
+            if nd:
+                pens = np.full((1, p, nd), np.inf)
+                for k in range(p):
+                    if pl[k] is not None:
+                        pens[0, k, :cnts[k]] = pl[k]
     qs = None
     if q is not None:
         ql = [_to_array(v).astype(np.float64).reshape(-1) for v in (q if isinstance(q, (list, tuple)) else [q] * p)]
@@ -191,28 +237,31 @@ def _stack_one(who, A, B, Q, R, N, x0, D, d, q, Pf):
         Pfs = lqr._stack_weights(Pf, p, nx, 'Pf')
     except ValueError as e:
         raise ValueError(str(e).replace('horizon_lqr', who)) from None
-    return As, Bs, Hs, np.ascontiguousarray(x[None, None]), dict(D=Ds, d=ds, ndcnt=cnt, q=qs, Pf=Pfs)
+    return As, Bs, Hs, np.ascontiguousarray(x[None, None]), dict(D=Ds, d=ds, ndcnt=cnt, q=qs, Pf=Pfs, penalty=pens)
 
 
-def mpc_step(A, B, Q, R, N, x0, horizon, phase0=0, D=None, d=None, q=None, Pf=None, tol=TOL, max_iter=MAX_ITER):
+def mpc_step(A, B, Q, R, N, x0, horizon, phase0=0, D=None, d=None, q=None, Pf=None, tol=TOL, max_iter=MAX_ITER, penalty=None):
     """One MPC step of one model in the reference's calling style: A, B, Q, R, N (the cross term) single matrices (p = 1) or lists of length p as in horizon_lqr,
     D, d the rows D_k [x; u] <= d_k (single arrays or lists of p; None entries: no rows at that stage), q, Pf likewise.  Returns (u0, X [horizon+1,nx],
-    U [horizon,nu], lam [horizon,nd], info dict).  RuntimeError when the solve did not converge."""
+    U [horizon,nu], lam [horizon,nd], info dict).  penalty: the weights of the soft rows, one vector (every stage) or a list of p vectors, one entry per row of
+    D_k; np.inf entries and None stages are hard.  With it info gains 'eps' [horizon,nd] (the slacks) and 'nviol'.  RuntimeError when the solve did not converge."""
     who = 'mpc_step'
-    As, Bs, Hs, X0, kw = _stack_one(who, A, B, Q, R, N, x0, D, d, q, Pf)
+    As, Bs, Hs, X0, kw = _stack_one(who, A, B, Q, R, N, x0, D, d, q, Pf, penalty)
     r = mpc_qp_batch(As, Bs, Hs, X0, horizon, phase0, tol=tol, max_iter=max_iter, **kw)
     st = int(r['status'][0, 0])
     if st != 0:
         raise RuntimeError('{}: the solve ended with status {} ({}) after {} iterations'.format(who, st, STATUS_NAMES.get(st), int(r['iters_total'][0, 0])))
-    return r['u0'][0, 0], r['X'][0, 0], r['U'][0, 0], r['lam'][0, 0], {k: r[k][0, 0] for k in INFO_FIELDS + ('nact', 'hres')}
+    return r['u0'][0, 0], r['X'][0, 0], r['U'][0, 0], r['lam'][0, 0], {k: r[k][0, 0] for k in INFO_FIELDS + ('nact', 'hres') + (('eps', 'nviol') if 'eps' in r else ())}
 
 
-def mpc_closed_loop_sim(A, B, Q, R, N, x0, horizon, steps, phase0=0, D=None, d=None, q=None, Pf=None, tol=TOL, max_iter=MAX_ITER):
+def mpc_closed_loop_sim(A, B, Q, R, N, x0, horizon, steps, phase0=0, D=None, d=None, q=None, Pf=None, tol=TOL, max_iter=MAX_ITER, penalty=None):
     """The reference's closed_loop_sim with the inequality-constrained tracking MPC in the loop and the linear plant, one model in the calling style of mpc_step.
     Returns the reference's log: {'x': steps + 1 states, 'u': steps inputs, 'l': steps stage costs 1/2 z' H_k z + q_k' z, 'h': steps arrays d_k - D_k [x_t; u_t]
-    (>= 0 when the rows hold; empty at a stage without rows)} and 'iters', 'nact'.  RuntimeError when a step did not converge."""
+    (>= 0 when the rows hold; empty at a stage without rows)} and 'iters', 'nact'.  With penalty (as in mpc_step) 'h' stays d - D z (negative on a violated soft
+    row), 'usc' holds the slack of the applied step, max(0, D z - d) on the soft rows and 0 on the hard ones (the reference's usc), and 'nviol' the count of the
+    solver.  RuntimeError when a step did not converge."""
     who = 'mpc_closed_loop_sim'
-    As, Bs, Hs, X0, kw = _stack_one(who, A, B, Q, R, N, x0, D, d, q, Pf)
+    As, Bs, Hs, X0, kw = _stack_one(who, A, B, Q, R, N, x0, D, d, q, Pf, penalty)
     r = mpc_closed_loop_batch(As, Bs, Hs, X0, horizon, steps, phase0, tol=tol, max_iter=max_iter, **kw)
     st = int(r['status'][0, 0])
     if st != 0:
@@ -228,4 +277,34 @@ def mpc_closed_loop_sim(A, B, Q, R, N, x0, horizon, steps, phase0=0, D=None, d=N
         log['l'].append(float(0.5 * z @ Hk @ z + (kw['q'][0, k] @ z if kw['q'] is not None else 0.0)))
         m = int(kw['ndcnt'][0, k]) if kw['D'] is not None else 0
         log['h'].append(kw['d'][0, k, :m] - kw['D'][0, k, :m] @ z if m else np.zeros(0))
+        if kw['penalty'] is not None:
+            log.setdefault('usc', []).append(np.where(np.isfinite(kw['penalty'][0, k, :m]), np.maximum(0.0, -log['h'][-1]), 0.0))
+    if kw['penalty'] is not None:
+        log['nviol'] = [int(v) for v in r['nviol'][0, 0]]
     return log
+
+
+def slack_penalty(lam_h, active_set=None, slack_flag='active', factor=1e3):
+    """The reference's rule for the weights of the soft rows (preprocessing.add_mpc_slacks), restated on the host: lam_h [N, nh] the multipliers of h(x, u) >= 0
+    along the optimal periodic orbit (<= 0 where a row is active, the reference's sign), active_set a list of N index lists (the rows active at each stage).
+    slack_flag 'active': the rows that are active at some stage; 'all': every row; 'none': no row.  Returns penalty [nh]: factor max_k(-lam_h[k, i]) on the selected
+    rows, inf elsewhere (a selected row whose multiplier is 0 everywhere stays hard: a weight of 0 is no penalty).  Pass it as penalty= (one vector for every stage)."""
+    lam = np.atleast_2d(_to_array(lam_h)).astype(np.float64)
+    nh = lam.shape[1]
+    if slack_flag not in ('active', 'all', 'none'):
+        raise ValueError("slack_penalty: slack_flag must be 'active', 'all' or 'none', got {!r}".format(slack_flag))
+    if not float(factor) > 0.0:
+        raise ValueError('slack_penalty: factor > 0 expected, got {!r}'.format(factor))
+    if slack_flag == 'active' and active_set is None:
+        raise ValueError("slack_penalty: slack_flag 'active' needs the active set")
+    out = np.full(nh, np.inf)
+    if slack_flag == 'none':
+        return out
+    sel = range(nh) if slack_flag == 'all' else sorted({int(i) for a in active_set for i in a})
+    if any(i < 0 or i >= nh for i in sel):
+        raise ValueError('slack_penalty: the active set names a row outside 0 .. {}'.format(nh - 1))
+    for i in sel:
+        w = float(factor) * float(np.max(-lam[:, i]))
+        if w > 0.0:
+            out[i] = w
+    return out
