@@ -398,8 +398,9 @@ int tmpc_closed_loop_batch_device(int nb, int p, int nx, int mb, int nr, int ng,
  *     min  sum_{j<N} (1/2 z_j' H_k z_j + q_k' z_j) + 1/2 x_N' Pf_{k_N} x_N,   z_j = [x_j; u_j],   k = k_j = (k0 + j) mod p,
  *     s.t. x_{j+1} = A_k x_j + B_k u_j,  x_0 given,   D_k z_j <= d_k (first ndcnt_k rows of the stage),   j = 0 .. N-1,
  * solved at the steps t = 0 .. T-1 from the phase (k0 + t) mod p; u_0 is applied and x <- A_k x + B_k u_0 (the linear plant), one launch for the whole batch.
- * Not served (there are no arguments for them): equality rows J, the terminal constraint x_N = 0, quadratic slack penalties, warm starts between steps, the
- * nonlinear plant.  Soft rows (exact L1 slack penalties, the reference's `usc`): the tmpc_mpc_qp_soft_batch_* entries below.
+ * Not served (there are no arguments for them): a terminal right-hand side != 0, quadratic slack penalties, warm starts between steps, the nonlinear plant.
+ * Soft rows (exact L1 slack penalties, the reference's `usc`): the tmpc_mpc_qp_soft_batch_* entries below.  Equality rows J z = r and the terminal
+ * constraint Tx x_N = 0 (the reference's g and p_operator): the tmpc_mpc_qp_eq_batch_* entries below.
  * Method: primal-dual interior point with Mehrotra's predictor-corrector, started infeasible, the Newton system solved by a Riccati pass with a Cholesky
  * factorisation per stage; the stop rule is r_p <= tol, r_d <= tol, mu <= 1e-3 tol max(1, max lam), residuals relative to the scale of the problem (stated
  * in tmpc_mpc_qp.h and in tests/mpc_qp_reference.py).  H is used as (H + H') / 2, likewise Pf.
@@ -448,6 +449,32 @@ int tmpc_mpc_qp_soft_batch_device(int nb, int p, int nx, int mb, int nd, int N, 
                                   const double* q, const double* Pf, const double* D, const int32_t* ndcnt, const double* d, const double* X0, double tol,
                                   int max_iter, double* U0, double* XT, double* info, double* X, double* U, int32_t* iters, int32_t* nact, double* hres,
                                   double* Xol, double* Uol, double* Lam, const double* penalty, double* Eol, int32_t* nviol);
+
+/* The same step and loop with EQUALITY rows at every stage and a TERMINAL constraint (the reference's pmpc.py: g(x, u) = 0 and p_operator(x_N - x_ref) = 0):
+ *     J_k z_j = r_k (first necnt_k rows of the stage),  j = 0 .. N-1,      Tx_{k_N} x_N = 0,  k_N = (k0 + N) mod p.
+ * The 34 arguments of the soft entries (penalty NULL: every inequality row hard), then
+ *   ne, J [nb][p][ne][n] (NULL exactly when ne = 0), r [nb][p][ne] (NULL: zero), necnt int32 [nb][p] (NULL: all ne rows);
+ *   nt, Tx [nb][p][nt][nx], indexed by k_N like Pf: nt = 0 and Tx NULL: no terminal rows; nt = -1 and Tx NULL: x_N = 0 (Tx = I); 1 <= nt <= nx with Tx;
+ *   optional outputs Nu [nb][ns][N][ne] and NuT [nb][ns][nt] (nx entries for nt = -1): the multipliers of the rows in the open-loop solution of step 0 (free sign;
+ *   rows beyond necnt zero; NaN when step 0 failed); eres [nb][T][ns], time-major: max|J z_0 - r| of the applied stage (0 at a stage without rows; NaN from a
+ *   failed step on).
+ * An equality row is a hard row without a slack: a multiplier of free sign, the constant barrier weight 1 / rho = 1e12, no step-length limit, no part in mu or
+ * the corrector; the terminal rows enter the Riccati pass where it starts (tmpc_mpc_qp.h; tests/mpc_qp_eq_reference.py states the same rules).  r_p of the stop
+ * rule also takes max|J z - r| / max(1, |r|) and max|Tx x_N| / max(1, max|x|).  An instance whose rows cannot be met (N mb too short to reach Tx x_N = 0, a
+ * stage-0 row on x_0 alone that x_0 violates) ends with status 1.  With ne = 0 and nt = 0 the entries above run (the same bits), eres is zero.
+ * Workspace per slot: 8 (2 N ne + nt) bytes more; LDS: 8 ne (ld + 3) bytes more, ld = (n + 1) | 1.
+ * TMPC_E_ARG, besides the above: ne < 0, J / ne mismatch, r or necnt without J, nt < -1, Tx / nt mismatch, (host entry) necnt outside 0 .. ne.
+ * TMPC_E_UNSUPPORTED: nt > nx; the layout with the equality rows beyond 160 KB, with the byte count. */
+int tmpc_mpc_qp_eq_batch_host(int nb, int p, int nx, int mb, int nd, int N, int ns, int T, int k0, const double* A, const double* B, const double* H,
+                              const double* q, const double* Pf, const double* D, const int32_t* ndcnt, const double* d, const double* X0, double tol,
+                              int max_iter, double* U0, double* XT, double* info, double* X, double* U, int32_t* iters, int32_t* nact, double* hres,
+                              double* Xol, double* Uol, double* Lam, const double* penalty, double* Eol, int32_t* nviol, int ne, const double* J,
+                              const double* r, const int32_t* necnt, int nt, const double* Tx, double* Nu, double* NuT, double* eres);
+int tmpc_mpc_qp_eq_batch_device(int nb, int p, int nx, int mb, int nd, int N, int ns, int T, int k0, const double* A, const double* B, const double* H,
+                                const double* q, const double* Pf, const double* D, const int32_t* ndcnt, const double* d, const double* X0, double tol,
+                                int max_iter, double* U0, double* XT, double* info, double* X, double* U, int32_t* iters, int32_t* nact, double* hres,
+                                double* Xol, double* Uol, double* Lam, const double* penalty, double* Eol, int32_t* nviol, int ne, const double* J,
+                                const double* r, const int32_t* necnt, int nt, const double* Tx, double* Nu, double* NuT, double* eres);
 
 /* Accumulated hipEvent timings since the last call (ms) when TMPC_FLAG_PROFILE is set, 16 doubles:
  * out[0] stage_pre+ctrl, [1] schur assembly, [2] block factorisation (all kernels of tmpc_cr.h's factor phase), [3] predictor

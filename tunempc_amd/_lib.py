@@ -26,7 +26,7 @@ EXPORTS = [
     'tmpc_periodic_lqr_batch_host', 'tmpc_periodic_lqr_batch_device', 'tmpc_periodic_lqr_rows_batch_host', 'tmpc_periodic_lqr_rows_batch_device',
     'tmpc_periodic_lqr_ctg_batch_host', 'tmpc_periodic_lqr_ctg_batch_device', 'tmpc_horizon_lqr_batch_host', 'tmpc_horizon_lqr_batch_device',
     'tmpc_closed_loop_batch_host', 'tmpc_closed_loop_batch_device', 'tmpc_mpc_qp_batch_host', 'tmpc_mpc_qp_batch_device',
-    'tmpc_mpc_qp_soft_batch_host', 'tmpc_mpc_qp_soft_batch_device',
+    'tmpc_mpc_qp_soft_batch_host', 'tmpc_mpc_qp_soft_batch_device', 'tmpc_mpc_qp_eq_batch_host', 'tmpc_mpc_qp_eq_batch_device',
     'tmpc_last_error', 'tmpc_version',
 ]
 # ... and in include/tunempc_hip_debug.h (unit-test / diagnostic entries)
@@ -155,6 +155,10 @@ def load_library():
     lib.tmpc_mpc_qp_soft_batch_host.argtypes = lib.tmpc_mpc_qp_batch_host.argtypes + [dp, dp, ip]
     lib.tmpc_mpc_qp_soft_batch_device.restype = C.c_int
     lib.tmpc_mpc_qp_soft_batch_device.argtypes = lib.tmpc_mpc_qp_batch_device.argtypes + [vp] * 3
+    lib.tmpc_mpc_qp_eq_batch_host.restype = C.c_int
+    lib.tmpc_mpc_qp_eq_batch_host.argtypes = lib.tmpc_mpc_qp_soft_batch_host.argtypes + [C.c_int, dp, dp, ip, C.c_int, dp, dp, dp, dp]
+    lib.tmpc_mpc_qp_eq_batch_device.restype = C.c_int
+    lib.tmpc_mpc_qp_eq_batch_device.argtypes = lib.tmpc_mpc_qp_soft_batch_device.argtypes + [C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, vp]
     lib.tmpc_get_profile.restype = C.c_int
     lib.tmpc_get_profile.argtypes = [vp, dp]
     lib.tmpc_get_trace.restype = C.c_int
@@ -980,6 +984,92 @@ def mpc_qp_soft_batch_device(A, B, H, q, Pf, D, ndcnt, d, penalty, X0, N, T, k0,
     _check_lqr(lib, rc, 'tmpc_mpc_qp_soft_batch_device')
     out = _mpc_qp_views(U0, XT, info, X, U, iters, nact, hres, Xol, Uol, Lam, lambda a: a.permute(0, 2, 1, 3), lambda a: a.permute(0, 2, 1))
     out.update(Eol=Eol, nviol=nviol.permute(0, 2, 1))
+    return out
+
+
+def _mpc_qp_eq_terminal(Tx, nx):
+    """Tx None / 'constraint' / array [nb,p,nt,nx] -> (nt argument of the C entry, array or None, rows of NuT)."""
+    if Tx is None:
+        return 0, None, 0
+    if isinstance(Tx, str):
+        return -1, None, nx
+    return int(Tx.shape[2]), Tx, int(Tx.shape[2])
+
+
+def mpc_qp_eq_batch_host(A, B, H, q, Pf, D, ndcnt, d, penalty, J, r, necnt, Tx, X0, N, T, k0, tol, max_iter, return_traj, return_ol):
+    """tmpc_mpc_qp_eq_batch_host on validated, contiguous numpy arrays (penalty, J [nb,p,ne,n], r, necnt int32 None or arrays; Tx None, 'constraint' or
+    [nb,p,nt,nx]) -> the dict of mpc_qp_soft_batch_host (Eol None and no nviol without penalty) with Nu [nb,ns,N,ne], NuT [nb,ns,nt] (None without return_ol)
+    and eres [nb,ns,T]."""
+    lib = load_library()
+    nb, p, nx, mb = B.shape
+    ns, T, N = X0.shape[1], int(T), int(N)
+    nd = 0 if D is None else D.shape[2]
+    ne = 0 if J is None else J.shape[2]
+    nt, Txa, ntr = _mpc_qp_eq_terminal(Tx, nx)
+    X = np.empty((nb, T + 1, ns, nx)) if return_traj else None
+    U = np.empty((nb, T, ns, mb)) if return_traj else None
+    iters = np.empty((nb, T, ns), np.int32); nact = np.empty((nb, T, ns), np.int32); hres = np.empty((nb, T, ns)); eres = np.empty((nb, T, ns))
+    nviol = np.empty((nb, T, ns), np.int32) if penalty is not None else None
+    Xol = np.empty((nb, ns, N + 1, nx)) if return_ol else None
+    Uol = np.empty((nb, ns, N, mb)) if return_ol else None
+    Lam = np.empty((nb, ns, N, nd)) if return_ol else None
+    Eol = np.empty((nb, ns, N, nd)) if return_ol and penalty is not None else None
+    Nu = np.empty((nb, ns, N, ne)) if return_ol else None
+    NuT = np.empty((nb, ns, ntr)) if return_ol else None
+    U0 = np.empty((nb, ns, mb)); XT = np.empty((nb, ns, nx)); info = np.zeros((nb, ns, MPC_QP_INFO_STRIDE))
+    opt = lambda a: _dptr(a) if a is not None and a.size else None
+    rc = lib.tmpc_mpc_qp_eq_batch_host(nb, p, nx, mb, nd, N, ns, T, int(k0), _dptr(A), _dptr(B), _dptr(H), _dptr(q), _dptr(Pf), _dptr(D) if nd else None,
+                                       _iptr(ndcnt) if nd else None, _dptr(d) if nd else None, _dptr(X0), float(tol), int(max_iter), _dptr(U0), _dptr(XT),
+                                       _dptr(info), _dptr(X), _dptr(U), _iptr(iters), _iptr(nact), _dptr(hres), _dptr(Xol), _dptr(Uol), opt(Lam), _dptr(penalty),
+                                       opt(Eol), _iptr(nviol), ne, _dptr(J) if ne else None, _dptr(r) if ne else None, _iptr(necnt) if ne else None, nt, _dptr(Txa),
+                                       opt(Nu), opt(NuT), _dptr(eres))
+    if rc == -1:
+        raise ValueError(lib.tmpc_last_error().decode())
+    _check_lqr(lib, rc, 'tmpc_mpc_qp_eq_batch_host')
+    out = _mpc_qp_views(U0, XT, info, X, U, iters, nact, hres, Xol, Uol, Lam, lambda a: a.transpose(0, 2, 1, 3), lambda a: a.transpose(0, 2, 1))
+    out.update(Nu=Nu, NuT=NuT, eres=eres.transpose(0, 2, 1))
+    if penalty is not None:
+        out.update(Eol=Eol, nviol=nviol.transpose(0, 2, 1))
+    return out
+
+
+def mpc_qp_eq_batch_device(A, B, H, q, Pf, D, ndcnt, d, penalty, J, r, necnt, Tx, X0, N, T, k0, tol, max_iter, return_traj, return_ol):
+    """tmpc_mpc_qp_eq_batch_device on validated, contiguous torch tensors of one GPU -> the dict of mpc_qp_eq_batch_host with torch tensors."""
+    import torch
+    lib = load_library()
+    nb, p, nx, mb = B.shape
+    ns, T, N = X0.shape[1], int(T), int(N)
+    nd = 0 if D is None else D.shape[2]
+    ne = 0 if J is None else J.shape[2]
+    nt, Txa, ntr = _mpc_qp_eq_terminal(Tx, nx)
+    dev = A.device
+    f64 = lambda *sh: torch.empty(sh, dtype=torch.float64, device=dev)
+    i32 = lambda *sh: torch.empty(sh, dtype=torch.int32, device=dev)
+    X = f64(nb, T + 1, ns, nx) if return_traj else None
+    U = f64(nb, T, ns, mb) if return_traj else None
+    iters = i32(nb, T, ns); nact = i32(nb, T, ns); hres = f64(nb, T, ns); eres = f64(nb, T, ns)
+    nviol = i32(nb, T, ns) if penalty is not None else None
+    Xol = f64(nb, ns, N + 1, nx) if return_ol else None
+    Uol = f64(nb, ns, N, mb) if return_ol else None
+    Lam = f64(nb, ns, N, nd) if return_ol else None
+    Eol = f64(nb, ns, N, nd) if return_ol and penalty is not None else None
+    Nu = f64(nb, ns, N, ne) if return_ol else None
+    NuT = f64(nb, ns, ntr) if return_ol else None
+    U0 = f64(nb, ns, mb); XT = f64(nb, ns, nx); info = torch.zeros((nb, ns, MPC_QP_INFO_STRIDE), dtype=torch.float64, device=dev)
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+    with torch.cuda.device(dev):
+        torch.cuda.current_stream(dev).synchronize()      # the entry runs on the null stream: the inputs must be complete
+        rc = lib.tmpc_mpc_qp_eq_batch_device(nb, p, nx, mb, nd, N, ns, T, int(k0), ptr(A), ptr(B), ptr(H), ptr(q), ptr(Pf), ptr(D) if nd else None,
+                                             ptr(ndcnt) if nd else None, ptr(d) if nd else None, ptr(X0), float(tol), int(max_iter), ptr(U0), ptr(XT), ptr(info),
+                                             ptr(X), ptr(U), ptr(iters), ptr(nact), ptr(hres), ptr(Xol), ptr(Uol), ptr(Lam), ptr(penalty), ptr(Eol), ptr(nviol), ne,
+                                             ptr(J) if ne else None, ptr(r) if ne else None, ptr(necnt) if ne else None, nt, ptr(Txa), ptr(Nu), ptr(NuT), ptr(eres))
+    if rc == -1:
+        raise ValueError(lib.tmpc_last_error().decode())
+    _check_lqr(lib, rc, 'tmpc_mpc_qp_eq_batch_device')
+    out = _mpc_qp_views(U0, XT, info, X, U, iters, nact, hres, Xol, Uol, Lam, lambda a: a.permute(0, 2, 1, 3), lambda a: a.permute(0, 2, 1))
+    out.update(Nu=Nu, NuT=NuT, eres=eres.permute(0, 2, 1))
+    if penalty is not None:
+        out.update(Eol=Eol, nviol=nviol.permute(0, 2, 1))
     return out
 
 

@@ -2212,25 +2212,37 @@ static int mpc_qp_check(const char* who, int nb, int p, int nx, int mb, int nd, 
   return TMPC_OK;
 }
 
+// The arguments of the EQ instantiations (tmpc_mpc_qp.h): device pointers; nt counts the terminal rows (Tx null: the identity, nt = nx).
+struct MpcQpEqArgs {
+  int ne = 0; const double* J = nullptr; const double* r = nullptr; const int32_t* necnt = nullptr; int nt = 0; const double* Tx = nullptr;
+  double* Nu = nullptr; double* NuT = nullptr; double* eres = nullptr;
+};
+
 static thread_local EigScratch g_mpc_qp_ws;           // workspace slots of both entries, kept between calls and grown on demand
 
 static int mpc_qp_launch(int nb, int p, int nx, int mb, int nd, int N, int ns, int T, int k0, const double* A, const double* B, const double* H, const double* q,
                          const double* Pf, const double* D, const int32_t* ndcnt, const double* d, const double* X0, double tol, int max_iter, double* U0,
                          double* XT, double* info, double* X, double* U, int32_t* iters, int32_t* nact, double* hres, double* Xol, double* Uol, double* Lam,
-                         const double* penalty = nullptr, double* Eol = nullptr, int32_t* nviol = nullptr) {
+                         const double* penalty = nullptr, double* Eol = nullptr, int32_t* nviol = nullptr, const MpcQpEqArgs* eq = nullptr) {
   // penalty: the SOFT instantiation with its longer LDS layout and workspace slots; without it the hard kernel (Eol, nviol are not passed then)
-  const size_t lds_bytes = (size_t)(penalty ? mpc_qp_soft_lds(nx, mb, nd).total : mpc_qp_lds(nx, mb, nd).total) * sizeof(double);
-  const long long ninst = (long long)nb * ns, per = (penalty ? mpc_qp_soft_ws_doubles(nx, mb, nd, N) : mpc_qp_ws_doubles(nx, mb, nd, N)) * 8;
+  // eq: the EQ instantiations (equality rows and / or terminal rows), their layout after the hard or soft one
+  const MpcQpEqArgs none;
+  const MpcQpEqArgs& e = eq ? *eq : none;
+  const size_t lds_bytes = (size_t)(eq ? mpc_qp_eq_lds(nx, mb, nd, e.ne, penalty != nullptr).total
+                                       : (penalty ? mpc_qp_soft_lds(nx, mb, nd).total : mpc_qp_lds(nx, mb, nd).total)) * sizeof(double);
+  const long long ninst = (long long)nb * ns, per = (eq ? mpc_qp_eq_ws_doubles(nx, mb, nd, N, e.ne, e.nt, penalty != nullptr)
+                                                        : (penalty ? mpc_qp_soft_ws_doubles(nx, mb, nd, N) : mpc_qp_ws_doubles(nx, mb, nd, N))) * 8;
   long long slots = ninst < MQ_SLOTS ? ninst : MQ_SLOTS;
   if (slots * per > MQ_WS_CAP_BYTES) slots = MQ_WS_CAP_BYTES / per;
   if (slots < 1) slots = 1;
   HIPCHK(g_mpc_qp_ws.reserve((size_t)(slots * per)));
-  auto kern = penalty ? k_mpc_qp<true> : k_mpc_qp<false>;
+  auto kern = eq ? (penalty ? k_mpc_qp<true, true> : k_mpc_qp<false, true>) : (penalty ? k_mpc_qp<true, false> : k_mpc_qp<false, false>);
   HIPCHK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LQR_LDS_BYTES));
   int lcw = 0;
   while ((1 << lcw) < nx + mb) ++lcw;
   hipLaunchKernelGGL(kern, dim3((unsigned)slots), dim3(LQR_NT), lds_bytes, 0, p, nx, mb, nd, lcw, N, ns, T, k0, ninst, A, B, H, q, Pf, D, (const int*)ndcnt, d,
-                     X0, tol, max_iter, (double*)g_mpc_qp_ws.p, U0, XT, info, X, U, (int*)iters, (int*)nact, hres, Xol, Uol, Lam, penalty, Eol, (int*)nviol);
+                     X0, tol, max_iter, (double*)g_mpc_qp_ws.p, U0, XT, info, X, U, (int*)iters, (int*)nact, hres, Xol, Uol, Lam, penalty, Eol, (int*)nviol,
+                     e.ne, e.J, e.r, (const int*)e.necnt, e.nt, e.Tx, e.Nu, e.NuT, e.eres);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(0));
   return TMPC_OK;
@@ -2311,6 +2323,21 @@ static int mpc_qp_soft_check(const char* who, int nx, int mb, int nd, int N, con
   return TMPC_OK;
 }
 
+// Host entries only: the counts within their capacity and every penalty > 0 (NaN fails), the offending element named.
+static int mpc_qp_host_ranges(const char* who, size_t nb, size_t p, const int32_t* cnt, int cap, const char* cnt_name, const char* cap_name, const double* penalty,
+                              int nd) {
+  const size_t st = nb * p;
+  if (cnt) for (size_t i = 0; i < st; ++i) if (cnt[i] < 0 || cnt[i] > cap) {
+    snprintf(g_err, sizeof(g_err), "%s: %s[%zu][%zu] = %d outside 0 .. %s = %d", who, cnt_name, i / p, i % p, (int)cnt[i], cap_name, cap);
+    return TMPC_E_ARG;
+  }
+  if (penalty) for (size_t i = 0; i < st * nd; ++i) if (!(penalty[i] > 0.0)) {
+    snprintf(g_err, sizeof(g_err), "%s: penalty[%zu][%zu][%zu] = %g: > 0 expected (+inf: a hard row)", who, i / nd / p, i / nd % p, i % nd, penalty[i]);
+    return TMPC_E_ARG;
+  }
+  return TMPC_OK;
+}
+
 int tmpc_mpc_qp_soft_batch_device(int nb, int p, int nx, int mb, int nd, int N, int ns, int T, int k0, const double* A, const double* B, const double* H,
                                   const double* q, const double* Pf, const double* D, const int32_t* ndcnt, const double* d, const double* X0, double tol,
                                   int max_iter, double* U0, double* XT, double* info, double* X, double* U, int32_t* iters, int32_t* nact, double* hres,
@@ -2346,14 +2373,8 @@ int tmpc_mpc_qp_soft_batch_host(int nb, int p, int nx, int mb, int nd, int N, in
   if (rc == TMPC_OK) rc = mpc_qp_soft_check(who, nx, mb, nd, N, penalty);
   if (rc != TMPC_OK) return rc;
   const size_t st = (size_t)nb * p, sn = (size_t)nb * ns;
-  if (ndcnt) for (size_t i = 0; i < st; ++i) if (ndcnt[i] < 0 || ndcnt[i] > nd) {
-    snprintf(g_err, sizeof(g_err), "%s: ndcnt[%zu][%zu] = %d outside 0 .. nd = %d", who, i / p, i % p, (int)ndcnt[i], nd);
-    return TMPC_E_ARG;
-  }
-  for (size_t i = 0; i < st * nd; ++i) if (!(penalty[i] > 0.0)) {
-    snprintf(g_err, sizeof(g_err), "%s: penalty[%zu][%zu][%zu] = %g: > 0 expected (+inf: a hard row)", who, i / nd / p, i / nd % p, i % nd, penalty[i]);
-    return TMPC_E_ARG;
-  }
+  rc = mpc_qp_host_ranges(who, nb, p, ndcnt, nd, "ndcnt", "nd", penalty, nd);
+  if (rc != TMPC_OK) return rc;
   // the inputs and outputs of the hard entry pass through device buffers of this entry: A | B | H | q | Pf | D | d | X0 | penalty, then the outputs
   const size_t n = (size_t)nx + mb;
   const size_t cA = st * nx * nx, cB = st * nx * mb, cH = st * n * n, cq = q ? st * n : 0, cPf = Pf ? cA : 0, cD = st * nd * n, cd = st * nd, c0 = sn * nx;
@@ -2393,6 +2414,128 @@ int tmpc_mpc_qp_soft_batch_host(int nb, int p, int nx, int mb, int nd, int N, in
   if (iters) HIPCHK(hipMemcpy(iters, dit, cS * sizeof(int32_t), hipMemcpyDeviceToHost));
   if (nact) HIPCHK(hipMemcpy(nact, dna, cS * sizeof(int32_t), hipMemcpyDeviceToHost));
   if (nviol) HIPCHK(hipMemcpy(nviol, dnv, cS * sizeof(int32_t), hipMemcpyDeviceToHost));
+  return TMPC_OK;
+}
+
+// The same entries with equality rows J z = r at every stage and terminal rows Tx x_N = 0 (tmpc_mpc_qp.h, the EQ instantiations).  ne = 0 and nt = 0: the
+// entries above, Nu and NuT empty, eres zero.
+static int mpc_qp_eq_check(const char* who, int nx, int mb, int nd, int N, bool soft, int ne, const void* J, const void* r, const void* necnt, int nt,
+                           const void* Tx) {
+  if (ne < 0 || ((ne > 0) != (J != nullptr)) || ((r || necnt) && !J)) {
+    snprintf(g_err, sizeof(g_err), "%s: bad argument (J non-null exactly when ne > 0, the equality-row capacity per stage; r and necnt only with J; got ne = %d)",
+             who, ne);
+    return TMPC_E_ARG;
+  }
+  if (nt < -1 || (nt == -1 && Tx) || (nt > 0 && !Tx) || (nt == 0 && Tx)) {
+    snprintf(g_err, sizeof(g_err), "%s: bad argument (nt = -1: x_N = 0 without Tx; nt = 0: no terminal rows, Tx null; nt > 0: Tx [nb][p][nt][nx]; got nt = %d)",
+             who, nt);
+    return TMPC_E_ARG;
+  }
+  if (nt > nx) {
+    snprintf(g_err, sizeof(g_err), "%s: at most nx = %d terminal rows (got nt = %d)", who, nx, nt);
+    return TMPC_E_UNSUPPORTED;
+  }
+  const long long bytes = (long long)mpc_qp_eq_lds(nx, mb, nd, ne < 65536 ? ne : 65536, soft).total * (long long)sizeof(double);
+  if (bytes > LQR_LDS_BYTES) {
+    snprintf(g_err, sizeof(g_err), "%s: nx = %d, nu = %d with room for %d %srows and %d equality rows per stage needs %lld bytes of LDS (limit %d)", who, nx, mb,
+             nd, soft ? "soft " : "", ne, bytes, LQR_LDS_BYTES);
+    return TMPC_E_UNSUPPORTED;
+  }
+  if ((long long)N * ne > 0x7fffffffLL / 4) {
+    snprintf(g_err, sizeof(g_err), "%s: horizon N = %d too long for %d equality rows per stage (32-bit indices inside a slot)", who, N, ne);
+    return TMPC_E_UNSUPPORTED;
+  }
+  return TMPC_OK;
+}
+
+int tmpc_mpc_qp_eq_batch_device(int nb, int p, int nx, int mb, int nd, int N, int ns, int T, int k0, const double* A, const double* B, const double* H,
+                                const double* q, const double* Pf, const double* D, const int32_t* ndcnt, const double* d, const double* X0, double tol,
+                                int max_iter, double* U0, double* XT, double* info, double* X, double* U, int32_t* iters, int32_t* nact, double* hres,
+                                double* Xol, double* Uol, double* Lam, const double* penalty, double* Eol, int32_t* nviol, int ne, const double* J,
+                                const double* r, const int32_t* necnt, int nt, const double* Tx, double* Nu, double* NuT, double* eres) {
+  const char* who = "tmpc_mpc_qp_eq_batch_device";
+  int rc = mpc_qp_check(who, nb, p, nx, mb, nd, N, ns, T, k0, A, B, H, D, ndcnt, d, X0, tol, max_iter, U0, XT, info);
+  if (rc == TMPC_OK) rc = mpc_qp_soft_check(who, nx, mb, nd, N, penalty);
+  if (rc == TMPC_OK) rc = mpc_qp_eq_check(who, nx, mb, nd, N, penalty != nullptr, ne, J, r, necnt, nt, Tx);
+  if (rc != TMPC_OK) return rc;
+  if (ne == 0 && nt == 0) {
+    if (eres) HIPCHK(hipMemsetAsync(eres, 0, (size_t)nb * T * ns * 8, 0));
+    return tmpc_mpc_qp_soft_batch_device(nb, p, nx, mb, nd, N, ns, T, k0, A, B, H, q, Pf, D, ndcnt, d, X0, tol, max_iter, U0, XT, info, X, U, iters, nact, hres,
+                                         Xol, Uol, Lam, penalty, Eol, nviol);
+  }
+  if (!penalty) {
+    if (Eol && nd > 0) HIPCHK(hipMemsetAsync(Eol, 0, (size_t)nb * ns * N * nd * 8, 0));
+    if (nviol) HIPCHK(hipMemsetAsync(nviol, 0, (size_t)nb * T * ns * sizeof(int32_t), 0));
+  }
+  MpcQpEqArgs e;
+  e.ne = ne; e.J = J; e.r = r; e.necnt = necnt; e.nt = nt < 0 ? nx : nt; e.Tx = Tx; e.Nu = Nu; e.NuT = NuT; e.eres = eres;
+  return mpc_qp_launch(nb, p, nx, mb, nd, N, ns, T, k0, A, B, H, q, Pf, D, ndcnt, d, X0, tol, max_iter, U0, XT, info, X, U, iters, nact, hres, Xol, Uol, Lam,
+                       penalty, penalty ? Eol : nullptr, penalty ? nviol : nullptr, &e);
+}
+
+static thread_local EigScratch g_mpc_qp_eq_scratch;      // device images of the host entry with equality rows
+
+int tmpc_mpc_qp_eq_batch_host(int nb, int p, int nx, int mb, int nd, int N, int ns, int T, int k0, const double* A, const double* B, const double* H,
+                              const double* q, const double* Pf, const double* D, const int32_t* ndcnt, const double* d, const double* X0, double tol,
+                              int max_iter, double* U0, double* XT, double* info, double* X, double* U, int32_t* iters, int32_t* nact, double* hres,
+                              double* Xol, double* Uol, double* Lam, const double* penalty, double* Eol, int32_t* nviol, int ne, const double* J,
+                              const double* r, const int32_t* necnt, int nt, const double* Tx, double* Nu, double* NuT, double* eres) {
+  const char* who = "tmpc_mpc_qp_eq_batch_host";
+  int rc = mpc_qp_check(who, nb, p, nx, mb, nd, N, ns, T, k0, A, B, H, D, ndcnt, d, X0, tol, max_iter, U0, XT, info);
+  if (rc == TMPC_OK) rc = mpc_qp_soft_check(who, nx, mb, nd, N, penalty);
+  if (rc == TMPC_OK) rc = mpc_qp_eq_check(who, nx, mb, nd, N, penalty != nullptr, ne, J, r, necnt, nt, Tx);
+  if (rc != TMPC_OK) return rc;
+  const size_t st = (size_t)nb * p, sn = (size_t)nb * ns, n = (size_t)nx + mb, cS = sn * T;
+  if (ne == 0 && nt == 0) {
+    rc = tmpc_mpc_qp_soft_batch_host(nb, p, nx, mb, nd, N, ns, T, k0, A, B, H, q, Pf, D, ndcnt, d, X0, tol, max_iter, U0, XT, info, X, U, iters, nact, hres, Xol,
+                                     Uol, Lam, penalty, Eol, nviol);
+    if (rc != TMPC_OK) return rc;
+    if (eres) for (size_t i = 0; i < cS; ++i) eres[i] = 0.0;
+    return TMPC_OK;
+  }
+  rc = mpc_qp_host_ranges(who, nb, p, ndcnt, nd, "ndcnt", "nd", penalty, nd);
+  if (rc == TMPC_OK) rc = mpc_qp_host_ranges(who, nb, p, necnt, ne, "necnt", "ne", nullptr, 0);
+  if (rc != TMPC_OK) return rc;
+  const int ntk = nt < 0 ? nx : nt;
+  // every array passes through one device buffer: (host pointer, bytes, input?) in the order of the arguments, each image 8-byte aligned
+  struct Img { const void* in; void* out; size_t bytes; size_t off; };
+  std::vector<Img> im;
+  size_t total = 0;
+  auto add = [&](const void* in, void* out, size_t bytes) {
+    const bool on = (in || out) && bytes > 0;
+    im.push_back(Img{on ? in : nullptr, on ? out : nullptr, on ? bytes : 0, total});
+    if (on) total += (bytes + 7) / 8 * 8;
+    return (int)im.size() - 1;
+  };
+  const int iA = add(A, nullptr, st * nx * nx * 8), iB = add(B, nullptr, st * nx * mb * 8), iH = add(H, nullptr, st * n * n * 8), iq = add(q, nullptr, st * n * 8);
+  const int iPf = add(Pf, nullptr, st * nx * nx * 8), iD = add(D, nullptr, st * nd * n * 8), icnt = add(ndcnt, nullptr, st * sizeof(int32_t));
+  const int id = add(d, nullptr, st * nd * 8), i0 = add(X0, nullptr, sn * nx * 8), ipen = add(penalty, nullptr, st * nd * 8);
+  const int iJ = add(J, nullptr, st * ne * n * 8), ir = add(r, nullptr, st * ne * 8), iec = add(necnt, nullptr, st * sizeof(int32_t));
+  const int iTx = add(Tx, nullptr, st * ntk * nx * 8);
+  const int oU0 = add(nullptr, U0, sn * mb * 8), oXT = add(nullptr, XT, sn * nx * 8), oI = add(nullptr, info, sn * MQ_INFO * 8);
+  const int oX = add(nullptr, X, sn * (T + 1) * nx * 8), oU = add(nullptr, U, cS * mb * 8), oit = add(nullptr, iters, cS * sizeof(int32_t));
+  const int ona = add(nullptr, nact, cS * sizeof(int32_t)), oh = add(nullptr, hres, cS * 8), oXo = add(nullptr, Xol, sn * (N + 1) * nx * 8);
+  const int oUo = add(nullptr, Uol, sn * N * mb * 8), oL = add(nullptr, Lam, sn * N * nd * 8), oE = add(nullptr, penalty ? Eol : nullptr, sn * N * nd * 8);
+  const int onv = add(nullptr, penalty ? nviol : nullptr, cS * sizeof(int32_t)), oNu = add(nullptr, Nu, sn * N * ne * 8), oNT = add(nullptr, NuT, sn * ntk * 8);
+  const int oer = add(nullptr, eres, cS * 8);
+  HIPCHK(g_mpc_qp_eq_scratch.reserve(total + 8));
+  char* base = (char*)g_mpc_qp_eq_scratch.p;
+  auto dev = [&](int i) -> void* { return im[i].bytes ? base + im[i].off : nullptr; };
+  for (int i = 0; i < (int)im.size(); ++i) if (im[i].in) HIPCHK(hipMemcpy(dev(i), im[i].in, im[i].bytes, hipMemcpyHostToDevice));
+  MpcQpEqArgs e;
+  e.ne = ne; e.J = (const double*)dev(iJ); e.r = (const double*)dev(ir); e.necnt = (const int32_t*)dev(iec); e.nt = ntk; e.Tx = (const double*)dev(iTx);
+  e.Nu = (double*)dev(oNu); e.NuT = (double*)dev(oNT); e.eres = (double*)dev(oer);
+  const int rl = mpc_qp_launch(nb, p, nx, mb, nd, N, ns, T, k0, (const double*)dev(iA), (const double*)dev(iB), (const double*)dev(iH), (const double*)dev(iq),
+                               (const double*)dev(iPf), (const double*)dev(iD), (const int32_t*)dev(icnt), (const double*)dev(id), (const double*)dev(i0), tol,
+                               max_iter, (double*)dev(oU0), (double*)dev(oXT), (double*)dev(oI), (double*)dev(oX), (double*)dev(oU), (int32_t*)dev(oit),
+                               (int32_t*)dev(ona), (double*)dev(oh), (double*)dev(oXo), (double*)dev(oUo), (double*)dev(oL), (const double*)dev(ipen),
+                               (double*)dev(oE), (int32_t*)dev(onv), &e);
+  if (rl != TMPC_OK) return rl;
+  for (int i = 0; i < (int)im.size(); ++i) if (im[i].out) HIPCHK(hipMemcpy(im[i].out, dev(i), im[i].bytes, hipMemcpyDeviceToHost));
+  if (!penalty) {
+    if (Eol) for (size_t i = 0; i < sn * N * nd; ++i) Eol[i] = 0.0;
+    if (nviol) for (size_t i = 0; i < cS; ++i) nviol[i] = 0;
+  }
   return TMPC_OK;
 }
 

@@ -2,8 +2,9 @@
 // closed_loop_tools.check_equivalence and closed_loop_sim): one small structured QP per (problem, initial state),
 //   min  sum_{j<N} (1/2 z_j' H_k z_j + q_k' z_j) + 1/2 x_N' Pf_{k_N} x_N,   z_j = [x_j; u_j],   k = k_j = (k0 + j) mod p,
 //   s.t. x_{j+1} = A_k x_j + B_k u_j,  x_0 given,   D_k z_j <= d_k (first ndcnt_k rows),   j = 0 .. N-1,
+//        and, in the EQ instantiations,   J_k z_j = r_k (first necnt_k rows),  j = 0 .. N-1,   Tx_{k_N} x_N = 0 (nt rows; Tx absent: the identity, x_N = 0),
 // solved T times in a row: step t starts at phase (k0 + t) mod p, applies u_0 and moves x <- A_k x + B_k u_0 on the linear plant.
-// Not served: equality rows J, the terminal constraint x_N = 0, quadratic slack penalties, warm starts between the steps, the nonlinear plant.
+// Not served: a terminal right-hand side != 0, quadratic slack penalties, warm starts between the steps, the nonlinear plant.
 //
 // Method: a primal-dual interior-point method with Mehrotra's predictor-corrector, started infeasible (z = 0 but x_0, s_i = max(d_i, 1), lam_i = 1).  The
 // multipliers of the dynamics are not variables: they are the adjoint of the iterate, pi_N = Pf x_N, [pi_j; r_u] = H z_j + q + D' lam_j + [A B]' pi_{j+1}, so
@@ -52,6 +53,21 @@
 // A penalty <= 0 or NaN makes the instance status 3 before its first step.  The LDS vectors e, nu, c lie after MpcQpLds::total (mpc_qp_soft_lds), the
 // workspace arrays E, NU, dE, C2 (c2 / nu of the corrector) [N][nd] after mpc_qp_ws_doubles (mpc_qp_soft_ws_doubles).  With SOFT = false the kernel is the
 // hard one statement by statement, and a soft launch whose penalties are all +inf takes the hard statements on every row: both give the same bits.
+//
+// Equality rows and the terminal constraint (the EQ instantiations, with or without SOFT; the reference's pmpc.py carries g(x, u) = 0 at every stage and
+// p_operator(x_N - x_ref) = 0 at the end).  An equality row is a hard row WITHOUT a slack (tests/mpc_qp_eq_reference.py states the same rules):
+//   multiplier nu: free sign, starts at 0, no step-length limit, no part in mu, sigma or the corrector (the corrector's backward sweep is unchanged);
+//   weight     the constant 1 / rho, what an inequality row may reach: Hb gets J' (1 / rho) J, h gets J' (nu + (1 / rho)(J z - r)), the adjoint of the iterate
+//              gets J' nu, and the forward sweep gives dnu = (1 / rho)(J dz + J z - r).  The error of the regularisation in the row equation is rho dnu and
+//              vanishes with the step; J z - r is taken from the iterate (pass 1), so cancellation at weight 1e12 costs iterations, not accuracy;
+//   terminal   the rows enter where the recursion starts: Pi_N = Pf + (1 / rho) Tx' Tx,  p_N = Pf x_N + Tx' (nu_T + (1 / rho) Tx x_N),
+//              pi_N = Pf x_N + Tx' nu_T, and after the sweep dnu_T = (1 / rho)(Tx dx_N + Tx x_N).  Tx is read from global memory at these two ends;
+//   stop       r_p also takes max_i |J z - r|_i / max(1, |r_i|) and max|Tx x_N| / max(1, max|x|); the scale of r_d takes J' nu into g; max lam stays over lam.
+// dnu is needed only for the step, so only the last forward sweep of an iteration computes it (into REQ, whose residual pass 1 writes again).  An instance
+// whose rows cannot be met -- N nu too short to reach Tx x_N = 0, a stage-0 row on x_0 alone that x_0 violates -- ends with status 1 like contradictory
+// inequality rows.  eres = max|J z_0 - r| of the applied stage (0 at a stage without rows).  LDS: J_k [ne x ld] and the vectors nu, J z - r, r after the hard or
+// soft layout (mpc_qp_eq_lds); workspace: NUe, REQ [N][ne] and NUT [nt] after the hard or soft workspace (mpc_qp_eq_ws_doubles); nt <= nx (Tx x_N and dnu_T
+// share the last vector slot of the hard layout).  With EQ = false both instantiations are what they were, statement by statement.
 #pragma once
 #include "tmpc_closed_loop.h"
 
@@ -61,6 +77,7 @@ constexpr int MQ_INFO = 8;                   // doubles of info per instance (TM
 constexpr int MQ_SLOTS = 512;                // workgroups (and workspace slots) per launch at the most
 constexpr int MQ_NVEC = 24;                  // vector slots of the LDS layout
 constexpr double MQ_RHO = 1e-12, MQ_STEP_BACK = 0.995, MQ_MU_FACTOR = 1e-3;
+constexpr double MQ_RINV = 1.0 / MQ_RHO;     // the weight of an equality row
 enum { MQ_OK = 0, MQ_MAXITER = 1, MQ_NOT_CONVEX = 2, MQ_NONFINITE = 3 };
 
 struct MpcQpLds { int ld, ldp, lv, oE, oP, oW, oH, oD, oV, oR, total; };      // offsets in doubles
@@ -101,6 +118,23 @@ __host__ __device__ inline long long mpc_qp_soft_ws_doubles(int nx, int mb, int 
   return mpc_qp_ws_doubles(nx, mb, nd, N) + 4LL * N * nd;
 }
 
+// The EQ instantiations: the hard (or soft) layout, then J_k [ne x ld] and the vectors nu, J z - r, r of the stage [ne] each; the hard (or soft) workspace,
+// then NUe, REQ [N][ne] each and NUT [nt].
+struct MpcQpEqLds { int base, oJ, oNu, oReq, oR, total; };
+__host__ __device__ inline MpcQpEqLds mpc_qp_eq_lds(int nx, int mb, int nd, int ne, bool soft) {
+  MpcQpEqLds l;
+  l.base = soft ? mpc_qp_soft_lds(nx, mb, nd).total : mpc_qp_lds(nx, mb, nd).total;
+  const long long ld = ((nx + mb + 1) | 1);
+  const long long oNu = (long long)l.base + (long long)ne * ld, total = oNu + 3LL * ne;
+  const bool big = total > 0x7fffffffLL / 8;
+  l.oJ = l.base; l.oNu = big ? l.base : (int)oNu; l.oReq = l.oNu + (big ? 0 : ne); l.oR = l.oReq + (big ? 0 : ne);
+  l.total = big ? 0x7fffffff / 8 : (int)total;
+  return l;
+}
+__host__ __device__ inline long long mpc_qp_eq_ws_doubles(int nx, int mb, int nd, int N, int ne, int nt, bool soft) {
+  return (soft ? mpc_qp_soft_ws_doubles(nx, mb, nd, N) : mpc_qp_ws_doubles(nx, mb, nd, N)) + 2LL * N * ne + nt;
+}
+
 __device__ __forceinline__ double mq_dot(const double* __restrict__ a, const double* __restrict__ b, int len) {
   double acc = 0.0;
   for (int c = 0; c < len; ++c) acc = fma(a[c], b[c], acc);
@@ -138,7 +172,10 @@ __device__ __forceinline__ void mq_fetch(double* El, double* Hl, double* Dl, int
 // each or null: X [nb][T+1][ns][nx], U [nb][T][ns][mb], iters, nact int [nb][T][ns], hres [nb][T][ns], Xol [nb][ns][N+1][nx], Uol [nb][ns][N][mb],
 // Lam [nb][ns][N][nd] (the open-loop solution of step 0).  SOFT: penalty [nb][p][nd] (+inf: hard row), and each or null Eol [nb][ns][N][nd], nviol int
 // [nb][T][ns]; ws: gridDim.x slots of mpc_qp_soft_ws_doubles, LDS of mpc_qp_soft_lds.  Without SOFT the three are not read or written.
-template <bool SOFT>
+// EQ: J [nb][p][ne][n] (null when ne = 0), req [nb][p][ne] or null (zero), necnt [nb][p] or null (all ne rows; clamped to 0 .. ne), Tx [nb][p][nt][nx] or null
+// (nt = nx: the identity), nt <= nx, and each or null Nu [nb][ns][N][ne], NuT [nb][ns][nt], eres [nb][T][ns]; ws: slots of mpc_qp_eq_ws_doubles, LDS of
+// mpc_qp_eq_lds.  Without EQ none of these is read or written.
+template <bool SOFT, bool EQ>
 __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd, int lcw, int N, int ns, int T, int k0, long long ninst,
                                                    const double* __restrict__ Ag, const double* __restrict__ Bg, const double* __restrict__ Hg,
                                                    const double* __restrict__ qg, const double* __restrict__ Pfg, const double* __restrict__ Dg,
@@ -147,7 +184,9 @@ __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd
                                                    double* __restrict__ Xg, double* __restrict__ Ug, int* __restrict__ itersg, int* __restrict__ nactg,
                                                    double* __restrict__ hresg, double* __restrict__ Xolg, double* __restrict__ Uolg,
                                                    double* __restrict__ Lamg, const double* __restrict__ peng, double* __restrict__ Eolg,
-                                                   int* __restrict__ nviolg) {
+                                                   int* __restrict__ nviolg, int ne, const double* __restrict__ Jg, const double* __restrict__ reqg,
+                                                   const int* __restrict__ necntg, int nt, const double* __restrict__ Txg, double* __restrict__ Nug,
+                                                   double* __restrict__ NuTg, double* __restrict__ eresg) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
   const int n = nx + mb;
   const MpcQpLds Ly = mpc_qp_lds(nx, mb, nd);
@@ -161,7 +200,7 @@ __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int cw = 1 << lcw, tx = tid & (cw - 1), ty = tid >> lcw, rs = LQR_NT >> lcw;
   const double qnan = __longlong_as_double(0x7ff8000000000000LL);
-  const long long wsn = SOFT ? mpc_qp_soft_ws_doubles(nx, mb, nd, N) : mpc_qp_ws_doubles(nx, mb, nd, N);
+  const long long wsn = EQ ? mpc_qp_eq_ws_doubles(nx, mb, nd, N, ne, nt, SOFT) : (SOFT ? mpc_qp_soft_ws_doubles(nx, mb, nd, N) : mpc_qp_ws_doubles(nx, mb, nd, N));
   double* ws = wsg + (size_t)blockIdx.x * wsn;
   double* Z = ws; double* dZ = Z + (size_t)(N + 1) * n; double* Sg = dZ + (size_t)(N + 1) * n; double* Lg = Sg + (size_t)N * nd; double* dSg = Lg + (size_t)N * nd;
   double* dLg = dSg + (size_t)N * nd; double* RIN = dLg + (size_t)N * nd; double* COR = RIN + (size_t)N * nd; double* RDYN = COR + (size_t)N * nd;
@@ -169,6 +208,11 @@ __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd
   const int fs = mb * (n + 1);                                               // doubles of [Y | R | y] per stage
   double* Eg = FAC + (size_t)N * fs; double* NUg = Eg + (size_t)N * nd; double* dEg = NUg + (size_t)N * nd; double* C2g = dEg + (size_t)N * nd;   // (SOFT only)
   double* ev = lds + Ly.total; double* nuv = ev + nd; double* cv = nuv + nd;                                                                   // (SOFT only)
+  // (EQ only) J_k and the vectors nu, J z - r, r (then nu + (1 / rho)(J z - r)) of the stage; Tx x_N, then dnu_T; the multipliers and the residuals per stage
+  double* Jl = lds + (SOFT ? Ly.total + 3 * nd : Ly.total); double* nuev = Jl + ne * ld; double* reqv = nuev + ne; double* rrv = reqv + ne;
+  double* tv = V + 23 * lv;
+  double* NUe = ws + (SOFT ? mpc_qp_soft_ws_doubles(nx, mb, nd, N) : mpc_qp_ws_doubles(nx, mb, nd, N)); double* REQ = NUe + (size_t)N * ne;
+  double* NUT = REQ + (size_t)N * ne;
 
   for (long long inst = blockIdx.x; inst < ninst; inst += gridDim.x) {
     const size_t b = (size_t)(inst / ns), si = (size_t)(inst % ns);
@@ -178,6 +222,10 @@ __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd
     const int* ndcnt = ndcntg ? ndcntg + b * p : nullptr;
     auto rows_of = [&](int k) { return nd > 0 ? (ndcnt ? max(0, min(nd, ndcnt[k])) : nd) : 0; };
     const double* pen = SOFT ? peng + b * p * nd : nullptr;
+    const double* J = EQ && ne > 0 ? Jg + b * p * ne * n : nullptr; const double* rq = EQ && reqg ? reqg + b * p * ne : nullptr;
+    const int* necnt = EQ && necntg ? necntg + b * p : nullptr;
+    const double* Tx = EQ && Txg ? Txg + b * p * nt * nx : nullptr;
+    auto erows_of = [&](int k) { return ne > 0 ? (necnt ? max(0, min(ne, necnt[k])) : ne) : 0; };
 
     if (tid < nx) {
       const double v = X0g[(b * ns + si) * nx + tid];
@@ -196,7 +244,7 @@ __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd
     for (int t = 0; t < T; ++t) {
       const int k0s = (k0 + t % p) % p;
       int its = 0, nact = -1, nviol = -1;
-      double hres = qnan;
+      double hres = qnan, eres = qnan;
       if (status == MQ_OK) {                                                 // (uniform: status is the same in every thread)
         // ---- start of the step: z = 0 but x_0, s = max(d, 1), lam = 1, no direction
         int mt = 0;
@@ -216,6 +264,10 @@ __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd
             NUg[e] = hc; Eg[e] = sf ? Sg[e] : 0.0; dEg[e] = 0.0; C2g[e] = 0.0;
           }
         }
+        if (EQ) {                                                            // nu = 0
+          for (int e = tid; e < N * ne; e += LQR_NT) { NUe[e] = 0.0; REQ[e] = 0.0; }
+          if (tid < nt) NUT[tid] = 0.0;
+        }
         int mp = mt;                                                         // complementarity pairs: one per row, one more per soft row
         if (SOFT) {
           double cnt = 0.0;
@@ -224,6 +276,7 @@ __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd
         }
         __syncthreads();
         const int kN = (k0s + N % p) % p;
+        auto tx_at = [&](int i, int c) { return Tx ? Tx[((size_t)kN * nt + i) * nx + c] : (i == c ? 1.0 : 0.0); };      // (EQ) row i of Tx_{k_N}
 
         for (int it = 0;; ++it) {
           its = it;
@@ -239,6 +292,25 @@ __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd
           }
           int facfail = 0;
           __syncthreads();
+          if (EQ) {                                                          // the terminal rows: Tx x_N, pi_N, p_N and Pi_N
+            if (tid < nt) {
+              double acc = 0.0;
+              for (int c = 0; c < nx; ++c) acc = fma(tx_at(tid, c), xn[c], acc);
+              tv[tid] = acc;
+            }
+            __syncthreads();
+            if (tid < nx) {
+              double s1 = 0.0, s2 = 0.0;
+              for (int i = 0; i < nt; ++i) { const double x = tx_at(i, tid), nuT = NUT[i]; s1 = fma(x, nuT, s1); s2 = fma(x, nuT + MQ_RINV * tv[i], s2); }
+              pin[tid] += s1; pv[tid] += s2;
+            }
+            if (tx < nx) for (int r = ty; r < nx; r += rs) {
+              double acc = 0.0;
+              for (int i = 0; i < nt; ++i) acc = fma(tx_at(i, r) * MQ_RINV, tx_at(i, tx), acc);
+              Pl[r * ldp + tx] += acc;
+            }
+            __syncthreads();
+          }
           for (int j = N - 1; j >= 0; --j) {
             const int k = (k0s + j % p) % p, m = rows_of(k);
             mq_fetch(El, Hl, Dl, ld, A + (size_t)k * nx * nx, B + (size_t)k * nx * mb, H + (size_t)k * n * n, D ? D + (size_t)k * nd * n : nullptr, nx, mb, m, tx, ty, rs);
@@ -246,6 +318,11 @@ __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd
             if (tid >= 64 && tid < 64 + nx) xn[tid - 64] = Z[(size_t)(j + 1) * n + tid - 64];
             for (int i = tid; i < m; i += LQR_NT) { lamv[i] = Lg[(size_t)j * nd + i]; sv[i] = Sg[(size_t)j * nd + i]; ddv[i] = dd[k * nd + i]; }
             if (SOFT) for (int i = tid; i < m; i += LQR_NT) { ev[i] = Eg[(size_t)j * nd + i]; nuv[i] = NUg[(size_t)j * nd + i]; cv[i] = pen[k * nd + i]; }
+            const int me = EQ ? erows_of(k) : 0;
+            if (EQ) {
+              if (tx < n) for (int i = ty; i < me; i += rs) Jl[i * ld + tx] = J[((size_t)k * ne + i) * n + tx];
+              for (int i = tid; i < me; i += LQR_NT) { nuev[i] = NUe[(size_t)j * ne + i]; rrv[i] = rq ? rq[k * ne + i] : 0.0; }
+            }
             __syncthreads();
             // ---- A: the residuals of the rows and of the dynamics, H z + q, Pi E
             for (int e = tid; e < m + nx + n; e += LQR_NT) {
@@ -273,6 +350,12 @@ __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd
                 gq[i] = mq_dot(Hl + i * ld, zv, n) + qv[i];
               }
             }
+            if (EQ) for (int e = tid; e < me; e += LQR_NT) {                 // J z - r, and nu + (1 / rho)(J z - r) in the place of r
+              const double r = mq_dot(Jl + e * ld, zv, n) - rrv[e];
+              a_rp = cl_absmax(a_rp, r / fmax(1.0, fabs(rrv[e])));
+              reqv[e] = r; REQ[(size_t)j * ne + e] = r;
+              rrv[e] = nuev[e] + MQ_RINV * r;
+            }
             if (tx < n) for (int r = ty; r < nx; r += rs) {
               double acc = 0.0;
               for (int c = 0; c < nx; ++c) acc = fma(Pl[r * ldp + c], El[c * ld + tx], acc);
@@ -284,6 +367,7 @@ __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd
               if (e < n) {
                 double dl = 0.0, db = 0.0, ep = 0.0;
                 for (int r = 0; r < m; ++r) { const double x = Dl[r * ld + e]; dl = fma(x, lamv[r], dl); db = fma(x, bsv[r], db); }
+                if (EQ) for (int r = 0; r < me; ++r) { const double x = Jl[r * ld + e]; dl = fma(x, nuev[r], dl); db = fma(x, rrv[r], db); }
                 for (int r = 0; r < nx; ++r) ep = fma(El[r * ld + e], pin[r], ep);
                 const double g = gq[e] + dl;
                 a_g = cl_absmax(a_g, g);
@@ -299,6 +383,7 @@ __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd
               double acc = Hl[i * ld + tx];
               for (int r = 0; r < nx; ++r) acc = fma(El[r * ld + i], Wl[r * ld + tx], acc);
               for (int r = 0; r < m; ++r) acc = fma(Dl[r * ld + i] * wv_[r], Dl[r * ld + tx], acc);
+              if (EQ) for (int r = 0; r < me; ++r) acc = fma(Jl[r * ld + i] * MQ_RINV, Jl[r * ld + tx], acc);
               Hl[i * ld + tx] = acc;
             }
             __syncthreads();
@@ -361,6 +446,7 @@ __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd
           const double sumc = mq_block<0>(part, red, tid);
           const double xmax = mq_block<1>(a_x, red, tid), lmax = mq_block<1>(a_lam, red, tid), gmax = mq_block<1>(a_g, red, tid);
           rp = fmax(mq_block<1>(a_rp, red, tid), mq_block<1>(a_dyn, red, tid) / fmax(1.0, xmax));
+          if (EQ) rp = fmax(rp, mq_block<1>(tid < nt ? cl_absmax(0.0, tv[tid]) : 0.0, red, tid) / fmax(1.0, xmax));      // (tv: still Tx x_N of this pass)
           rd = mq_block<1>(a_rd, red, tid) / fmax(1.0, gmax);
           mu = mt > 0 ? sumc / mp : 0.0;
           if (!(rp < INFINITY && rd < INFINITY && fabs(mu) < INFINITY && lmax < INFINITY && xmax < INFINITY)) { status = MQ_NONFINITE; break; }
@@ -428,8 +514,14 @@ __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd
             __syncthreads();
             double* dx = dxa; double* dxn = dxb;
             double amin = 1e300;
+            const bool last = EQ && (sweep == 1 || mt == 0);                 // (EQ) the sweep whose direction is taken: it computes dnu
             for (int j = 0; j < N; ++j) {
               const int k = (k0s + j % p) % p, m = rows_of(k);
+              const int me = last ? erows_of(k) : 0;
+              if (EQ) if (last) {
+                if (tx < n) for (int i = ty; i < me; i += rs) Jl[i * ld + tx] = J[((size_t)k * ne + i) * n + tx];
+                for (int i = tid; i < me; i += LQR_NT) reqv[i] = REQ[(size_t)j * ne + i];
+              }
               mq_fetch(El, nullptr, Dl, ld, A + (size_t)k * nx * nx, B + (size_t)k * nx * mb, nullptr, D ? D + (size_t)k * nd * n : nullptr, nx, mb, m, tx, ty, rs);
               for (int i = ty; i < mb; i += rs) for (int col = tx; col <= n; col += cw) Hl[(nx + i) * ld + col] = FAC[(size_t)j * fs + i * (n + 1) + col];
               for (int i = tid; i < m; i += LQR_NT) {
@@ -475,10 +567,16 @@ __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd
                   dxn[r] = mq_dot(El + r * ld, dzv, n) + rdynv[r];
                 }
               }
+              if (EQ) for (int e = tid; e < me; e += LQR_NT) REQ[(size_t)j * ne + e] = MQ_RINV * (mq_dot(Jl + e * ld, dzv, n) + reqv[e]);     // dnu
               __syncthreads();
               { double* t_ = dx; dx = dxn; dxn = t_; }
             }
             if (tid < nx) dZ[(size_t)N * n + tid] = dx[tid];
+            if (EQ) if (last && tid < nt) {                                  // dnu_T
+              double acc = 0.0;
+              for (int c = 0; c < nx; ++c) acc = fma(tx_at(tid, c), dx[c], acc);
+              tv[tid] = MQ_RINV * (acc + tv[tid]);
+            }
             alpha = mq_block<2>(amin, red, tid);
           }
           // ================================================================ the step
@@ -486,6 +584,10 @@ __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd
           for (int e = tid; e < (N + 1) * n; e += LQR_NT) Z[e] = fma(al, dZ[e], Z[e]);
           if (SOFT) for (int e = tid; e < N * nd; e += LQR_NT) if (soft_at(e)) { Eg[e] = fma(al, dEg[e], Eg[e]); NUg[e] = fma(-al, dLg[e], NUg[e]); }
           for (int e = tid; e < N * nd; e += LQR_NT) { Sg[e] = fma(al, dSg[e], Sg[e]); Lg[e] = fma(al, dLg[e], Lg[e]); }
+          if (EQ) {
+            for (int e = tid; e < N * ne; e += LQR_NT) NUe[e] = fma(al, REQ[e], NUe[e]);
+            if (tid < nt) NUT[tid] = fma(al, tv[tid], NUT[tid]);
+          }
           __syncthreads();
         }
         it_total += its; it_max = max(it_max, its);
@@ -496,6 +598,8 @@ __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd
         const int m = rows_of(k0s);
         mq_fetch(El, nullptr, Dl, ld, A + (size_t)k0s * nx * nx, B + (size_t)k0s * nx * mb, nullptr, D ? D + (size_t)k0s * nd * n : nullptr, nx, mb, m, tx, ty, rs);
         if (tid < n) zv[tid] = Z[tid];
+        const int me0 = EQ ? erows_of(k0s) : 0;
+        if (EQ) if (tx < n) for (int i = ty; i < me0; i += rs) Jl[i * ld + tx] = J[((size_t)k0s * ne + i) * n + tx];
         __syncthreads();
         double hmax = -INFINITY, cnt = 0.0;
         for (int i = tid; i < m; i += LQR_NT) {
@@ -509,6 +613,15 @@ __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd
           for (int i = tid; i < m; i += LQR_NT) if (Eg[i] > NUg[i]) cv_ += 1.0;
           nviol = (int)mq_block<0>(cv_, red, tid);
           if (t == 0 && Eolg) for (int e = tid; e < N * nd; e += LQR_NT) Eolg[((b * ns + si) * N) * nd + e] = Eg[e];
+        }
+        if (EQ) {
+          double em = 0.0;
+          for (int i = tid; i < me0; i += LQR_NT) em = cl_absmax(em, mq_dot(Jl + i * ld, zv, n) - (rq ? rq[k0s * ne + i] : 0.0));
+          eres = mq_block<1>(em, red, tid);
+          if (t == 0) {
+            if (Nug) for (int e = tid; e < N * ne; e += LQR_NT) Nug[((b * ns + si) * N) * ne + e] = NUe[e];
+            if (NuTg && tid < nt) NuTg[(b * ns + si) * nt + tid] = NUT[tid];
+          }
         }
         if (t == 0) {
           if (Xolg) for (int e = tid; e < (N + 1) * nx; e += LQR_NT) { const int j = e / nx; Xolg[((b * ns + si) * (N + 1)) * nx + e] = Z[(size_t)j * n + e - j * nx]; }
@@ -540,6 +653,10 @@ __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd
           if (Uolg) for (int e = tid; e < N * mb; e += LQR_NT) Uolg[((b * ns + si) * N) * mb + e] = qnan;
           if (Lamg) for (int e = tid; e < N * nd; e += LQR_NT) Lamg[((b * ns + si) * N) * nd + e] = qnan;
           if (SOFT) if (Eolg) for (int e = tid; e < N * nd; e += LQR_NT) Eolg[((b * ns + si) * N) * nd + e] = qnan;
+          if (EQ) {
+            if (Nug) for (int e = tid; e < N * ne; e += LQR_NT) Nug[((b * ns + si) * N) * ne + e] = qnan;
+            if (NuTg && tid < nt) NuTg[(b * ns + si) * nt + tid] = qnan;
+          }
         }
       }
       if (tid == 0) {
@@ -548,6 +665,7 @@ __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd
         if (nactg) nactg[o] = nact;
         if (hresg) hresg[o] = hres;
         if (SOFT) if (nviolg) nviolg[o] = nviol;
+        if (EQ) if (eresg) eresg[o] = eres;
       }
     }
     if (tid < nx) XTg[(b * ns + si) * nx + tid] = status == MQ_OK ? xcur[tid] : qnan;

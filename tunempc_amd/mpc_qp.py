@@ -5,9 +5,11 @@ lqr.py and closed_loop.py serve the laws of a FIXED active set.  This module sol
 
     min  sum_{j<N} (1/2 z_j' H_k z_j + q_k' z_j) + 1/2 x_N' Pf_{k_N} x_N,   z_j = [x_j; u_j],
     s.t. x_{j+1} = A_k x_j + B_k u_j,   D_k z_j <= d_k (first ndcnt_k rows of the stage),   j = 0 .. N-1,
+         J_k z_j = r_k (first necnt_k rows of the stage),   Tx_{k_N} x_N = 0,  k_N = (phase0 + N) mod p   (J=, r=, necnt=, terminal=),
 
 where a row may be SOFT (`penalty`, the reference's preprocessing.add_mpc_slacks: D_i z - e_i <= d_i, e_i >= 0 at the cost c_i e_i, an exact L1 penalty: the
-hard solution as long as c_i exceeds the row's multiplier, a violated row instead of an infeasible problem otherwise),
+hard solution as long as c_i exceeds the row's multiplier, a violated row instead of an infeasible problem otherwise), the equality rows are the reference's
+g(x, u) = 0 and the terminal rows its p_operator(x_N - x_ref) = 0 in deviation coordinates (pmpc.py always carries one; terminal='constraint' is x_N = 0),
 
 with a primal-dual interior-point method (Mehrotra's predictor-corrector, Riccati recursion with a Cholesky factorisation per stage), one 256-thread workgroup
 per instance, the whole interior-point loop and all steps of the closed loop in one launch (csrc/tmpc_mpc_qp.h).
@@ -18,8 +20,11 @@ per instance, the whole interior-point loop and all steps of the closed loop in 
     mpc_closed_loop_sim(A, B, Q, R, N, x0, horizon, steps, ...)                    -> the reference's log {'x', 'u', 'l', 'h'} (and 'usc' with penalty=)
     slack_penalty(lam_h, active_set, slack_flag, factor)                           the reference's rule for the weights of the soft rows
 
-Not served: equality rows J, the terminal constraint x_N = 0, quadratic slack penalties, warm starts between the steps, the nonlinear plant; there are no
-arguments for them.  Conventions as in lqr.py / closed_loop.py.  There is no CPU path: the solve runs in the HIP library or the call raises."""
+An equality row is a hard row without a slack: a multiplier of free sign at the constant barrier weight 1e12 (csrc/tmpc_mpc_qp.h states the rules).  An
+instance whose rows cannot be met -- horizon * nu too short to reach Tx x_N = 0, a row of stage 0 on x_0 alone that x_0 violates (the reference drops state-only
+h rows at stage 0 for the same reason) -- is infeasible and ends with status 1, like contradictory inequality rows.
+
+Not served: a terminal right-hand side != 0, quadratic slack penalties, warm starts between the steps, the nonlinear plant; there are no arguments for them.  Conventions as in lqr.py / closed_loop.py.  There is no CPU path: the solve runs in the HIP library or the call raises."""
 import numpy as np
 
 from . import _lib
@@ -35,21 +40,30 @@ SLOTS = 512            # workgroups (workspace slots) of a launch at the most
 INFO_FIELDS = ('status', 'steps', 'iters_total', 'iters_max', 'mu', 'rp', 'rd', 'pivmin')
 
 
-def lds_layout(nx, nu, nd=0, soft=False):
+def lds_layout(nx, nu, nd=0, soft=False, ne=None, nt=0):
     """mpc_qp_lds of csrc/tmpc_mpc_qp.h restated: dict bytes (LDS of a workgroup), ws_doubles (function of the horizon: doubles of workspace per slot).
     soft: mpc_qp_soft_lds / mpc_qp_soft_ws_doubles, the layout of a call with penalty (the vectors e, nu, c after the hard layout, E, NU, dE, C2 after the hard
-    workspace)."""
+    workspace).  ne (not None): mpc_qp_eq_lds / mpc_qp_eq_ws_doubles, the layout of a call with J= or terminal= (J_k [ne x ld] and three vectors after the hard
+    or soft layout, NUe, REQ [N][ne] and NUT [nt] after the workspace)."""
     nx, nu, nd = int(nx), int(nu), int(nd)
     n = nx + nu
     ld, ldp, lv = (n + 1) | 1, nx | 1, max(n + 1, nd)
     total = nx * ld + nx * ldp + nx * ld + n * ld + nd * ld + 24 * lv + 8
+    if ne is not None:
+        ne, nt = int(ne), int(nt)
+        base = lds_layout(nx, nu, nd, soft)
+        return dict(bytes=base['bytes'] + 8 * ne * (ld + 3), ws_doubles=lambda N: base['ws_doubles'](N) + 2 * N * ne + nt)
     if soft:
         return dict(bytes=8 * (total + 3 * nd), ws_doubles=lambda N: 2 * (N + 1) * n + 6 * N * nd + N * nx + N * nu * (n + 1) + 4 * N * nd)
     return dict(bytes=8 * total, ws_doubles=lambda N: 2 * (N + 1) * n + 6 * N * nd + N * nx + N * nu * (n + 1))
 
 
-def _validate(who, A, B, H, X0, horizon, phase0, D, d, ndcnt, q, Pf, tol, max_iter, steps=1, penalty=None):
-    named = [('A', A), ('B', B), ('H', H), ('X0', X0)] + [(nm, x) for nm, x in (('D', D), ('d', d), ('q', q), ('Pf', Pf), ('penalty', penalty)) if x is not None]
+def _validate(who, A, B, H, X0, horizon, phase0, D, d, ndcnt, q, Pf, tol, max_iter, steps=1, penalty=None, J=None, r=None, necnt=None, terminal=None):
+    if terminal is not None and not (isinstance(terminal, str) and terminal == 'constraint') and not hasattr(terminal, 'shape'):
+        raise ValueError("{}: terminal must be None, 'constraint' or an array [nb, p, nt, nx], got {!r}".format(who, terminal))
+    Tx = terminal if hasattr(terminal, 'shape') else None
+    named = [('A', A), ('B', B), ('H', H), ('X0', X0)] + [(nm, x) for nm, x in (('D', D), ('d', d), ('q', q), ('Pf', Pf), ('penalty', penalty), ('J', J), ('r', r),
+                                                                                 ('terminal', Tx)) if x is not None]
     use_torch = _cl._check_kind(who, named)
     if len(A.shape) != 4 or A.shape[2] != A.shape[3]:
         raise ValueError('{}: A [nb, p, nx, nx] expected, got {}'.format(who, tuple(A.shape)))
@@ -115,15 +129,51 @@ def _validate(who, A, B, H, X0, horizon, phase0, D, d, ndcnt, q, Pf, tol, max_it
         if soft['bytes'] > LDS_BYTES:
             raise NotImplementedError('{}: nx = {}, nu = {} with room for {} soft rows per stage needs {} bytes of LDS (limit {})'.format(
                 who, nx, nu, nd, soft['bytes'], LDS_BYTES))
+    if J is None and (r is not None or necnt is not None):
+        raise ValueError('{}: {} describes the rows of J, which is None'.format(who, 'r' if r is not None else 'necnt'))
+    ne = 0
+    if J is not None:
+        if len(J.shape) != 4 or tuple(J.shape[:2]) != (nb, p) or int(J.shape[3]) != n or int(J.shape[2]) < 1:
+            raise ValueError('{}: J [nb, p, ne, nx + nu] = [{}, {}, ne >= 1, {}] expected, got {}'.format(who, nb, p, n, tuple(J.shape)))
+        ne = int(J.shape[2])
+        if r is not None and tuple(r.shape) != (nb, p, ne):
+            raise ValueError('{}: r {} expected, got {}'.format(who, (nb, p, ne), tuple(r.shape)))
+        if necnt is not None:
+            if not hasattr(necnt, 'shape') or lqr._is_torch(necnt) != use_torch:
+                raise ValueError('{}: necnt must be {} like A, B, H'.format(who, 'a torch tensor' if use_torch else 'a numpy array'))
+            if tuple(necnt.shape) != (nb, p) or 'int32' not in str(necnt.dtype):
+                raise ValueError('{}: necnt int32 {} expected, got {} {}'.format(who, (nb, p), necnt.dtype, tuple(necnt.shape)))
+            if use_torch and (not necnt.is_cuda or necnt.device != A.device):
+                raise ValueError('{}: torch tensors must be tensors of one GPU (necnt: {})'.format(who, necnt.device))
+            lo, hi = (int(necnt.min()), int(necnt.max()))
+            if lo < 0 or hi > ne:
+                raise ValueError('{}: necnt in 0 .. ne = {} expected, got {} .. {}'.format(who, ne, lo, hi))
+    nt = 0 if terminal is None else nx
+    if Tx is not None:
+        if len(Tx.shape) != 4 or tuple(Tx.shape[:2]) != (nb, p) or int(Tx.shape[3]) != nx or not 1 <= int(Tx.shape[2]) <= nx:
+            raise ValueError('{}: terminal [nb, p, nt, nx] = [{}, {}, 1 <= nt <= {}, {}] expected, got {}'.format(who, nb, p, nx, nx, tuple(Tx.shape)))
+        nt = int(Tx.shape[2])
+    if J is not None or terminal is not None:
+        lay = lds_layout(nx, nu, nd, soft=penalty is not None, ne=ne, nt=nt)
+        if lay['bytes'] > LDS_BYTES:
+            raise NotImplementedError('{}: nx = {}, nu = {} with room for {} {}rows and {} equality rows per stage needs {} bytes of LDS (limit {})'.format(
+                who, nx, nu, nd, 'soft ' if penalty is not None else '', ne, lay['bytes'], LDS_BYTES))
     return use_torch, nd, int(horizon), T, k0
 
 
-def _run(who, A, B, H, X0, horizon, steps, phase0, D, d, ndcnt, q, Pf, tol, max_iter, return_traj, return_ol, penalty=None):
-    use_torch, nd, N, T, k0 = _validate(who, A, B, H, X0, horizon, phase0, D, d, ndcnt, q, Pf, tol, max_iter, steps, penalty)
-    A, B, H, X0, D, d, q, Pf, penalty = (lqr._contig(x, use_torch) for x in (A, B, H, X0, D, d, q, Pf, penalty))
+def _run(who, A, B, H, X0, horizon, steps, phase0, D, d, ndcnt, q, Pf, tol, max_iter, return_traj, return_ol, penalty=None, J=None, r=None, necnt=None,
+         terminal=None):
+    use_torch, nd, N, T, k0 = _validate(who, A, B, H, X0, horizon, phase0, D, d, ndcnt, q, Pf, tol, max_iter, steps, penalty, J, r, necnt, terminal)
+    A, B, H, X0, D, d, q, Pf, penalty, J, r = (lqr._contig(x, use_torch) for x in (A, B, H, X0, D, d, q, Pf, penalty, J, r))
     if ndcnt is not None:
         ndcnt = ndcnt.contiguous() if use_torch else np.ascontiguousarray(ndcnt)
-    if penalty is None:
+    if necnt is not None:
+        necnt = necnt.contiguous() if use_torch else np.ascontiguousarray(necnt)
+    if J is not None or terminal is not None:
+        Tx = terminal if isinstance(terminal, str) or terminal is None else lqr._contig(terminal, use_torch)
+        entry = _lib.mpc_qp_eq_batch_device if use_torch else _lib.mpc_qp_eq_batch_host
+        out = entry(A, B, H, q, Pf, D, ndcnt, d, penalty, J, r, necnt, Tx, X0, N, T, k0, float(tol), int(max_iter), bool(return_traj), bool(return_ol))
+    elif penalty is None:
         entry = _lib.mpc_qp_batch_device if use_torch else _lib.mpc_qp_batch_host
         out = entry(A, B, H, q, Pf, D, ndcnt, d, X0, N, T, k0, float(tol), int(max_iter), bool(return_traj), bool(return_ol))
     else:
@@ -140,7 +190,8 @@ def _run(who, A, B, H, X0, horizon, steps, phase0, D, d, ndcnt, q, Pf, tol, max_
     return out
 
 
-def mpc_qp_batch(A, B, H, X0, horizon, phase0=0, D=None, d=None, ndcnt=None, q=None, Pf=None, tol=TOL, max_iter=MAX_ITER, return_traj=True, penalty=None):
+def mpc_qp_batch(A, B, H, X0, horizon, phase0=0, D=None, d=None, ndcnt=None, q=None, Pf=None, tol=TOL, max_iter=MAX_ITER, return_traj=True, penalty=None,
+                 J=None, r=None, necnt=None, terminal=None):
     """One MPC step per (problem, initial deviation): A [nb,p,nx,nx], B [nb,p,nx,nu], H [nb,p,n,n] (used as (H + H') / 2), X0 [nb,ns,nx], fp64, n = nx + nu <= 64;
     the horizon-`horizon` QP from phase `phase0`.  Optional: the rows D [nb,p,nd,n], d [nb,p,nd] (D z <= d; ndcnt int32 [nb,p]: only the first ndcnt rows of a
     stage, None: all nd), q [nb,p,n] (linear cost), Pf [nb,p,nx,nx] (terminal weight 1/2 x_N' Pf[(phase0 + N) mod p] x_N); None: absent / zero.  Without rows
@@ -148,6 +199,11 @@ def mpc_qp_batch(A, B, H, X0, horizon, phase0=0, D=None, d=None, ndcnt=None, q=N
     penalty [nb,p,nd] (fp64): inf a hard row, c > 0 a soft row (D_i z - e_i <= d_i, e_i >= 0, cost c e_i at every stage); None: every row hard, the call as it
     was.  With a penalty the dict gains eps [nb,ns,N,nd] (the open-loop slacks; 0 on hard rows; None with return_traj=False) and nviol [nb,ns] int32 (rows of
     stage 0 with e > nu), hres > 0 tells a violated soft row, and a state outside a soft bound is no longer status 1.
+    J [nb,p,ne,n], r [nb,p,ne] (None: zero), necnt int32 [nb,p] (None: all ne): the equality rows J_k z_j = r_k of every stage.  terminal: 'constraint' (x_N = 0)
+    or Tx [nb,p,nt,nx], 1 <= nt <= nx, indexed by (phase0 + N) mod p like Pf: the rows Tx x_N = 0.  With J or terminal the dict gains nu [nb,ns,N,ne] and
+    nu_term [nb,ns,nt] (the multipliers, free sign; None with return_traj=False) and eres [nb,ns] = max|J z_0 - r| (0 at a stage without rows).  Rows that
+    cannot be met (horizon * nu too short to reach the terminal rows, a row of stage 0 on x_0 alone that x_0 violates) make the instance infeasible: status 1.
+    Without them (J=None, terminal=None) the call is the one it was, bit for bit.
 
     numpy arrays run through the host entry; torch tensors on a GPU through the device entry (torch tensors out, the inputs are not copied).  Both run the same
     kernel and agree bit for bit; the numbers of an instance do not depend on ns or on the other instances of the call.
@@ -157,18 +213,20 @@ def mpc_qp_batch(A, B, H, X0, horizon, phase0=0, D=None, d=None, ndcnt=None, q=N
     (0 converged, 1 max_iter reached -- an infeasible instance ends here --, 2 a stage matrix not positive definite: not convex along the path, 3 non-finite), steps,
     iters_total, iters_max [nb,ns] int32, mu, rp, rd, pivmin [nb,ns], info [nb,ns,8].  An instance with status != 0 returns NaN (nact -1); the others are not
     affected.  ValueError: shapes, dtypes, mixed numpy / torch, horizon < 1, phase0 outside 0 .. p-1, D without d, ndcnt outside 0 .. nd, tol <= 0,
-    max_iter < 1, penalty without D or with an entry <= 0 or NaN; NotImplementedError: n > 64, (nx, nu, nd) beyond the 160 KB LDS layout (lds_layout; with a
-    penalty the soft layout)."""
-    o = _run('mpc_qp_batch', A, B, H, X0, horizon, 1, phase0, D, d, ndcnt, q, Pf, tol, max_iter, False, return_traj, penalty)
+    max_iter < 1, penalty without D or with an entry <= 0 or NaN, r or necnt without J, a terminal that is neither None, 'constraint' nor an array;
+    NotImplementedError: n > 64, (nx, nu, nd) beyond the 160 KB LDS layout (lds_layout; with a penalty the soft layout, with J or terminal lds_layout(ne=))."""
+    o = _run('mpc_qp_batch', A, B, H, X0, horizon, 1, phase0, D, d, ndcnt, q, Pf, tol, max_iter, False, return_traj, penalty, J, r, necnt, terminal)
     out = dict(u0=o['U0'], X=o['Xol'], U=o['Uol'], lam=o['Lam'], nact=o['nact'][..., 0], hres=o['hres'][..., 0], x1=o['XT'], info=o['info'])
     if penalty is not None:
         out.update(eps=o['Eol'], nviol=o['nviol'][..., 0])
+    if J is not None or terminal is not None:
+        out.update(nu=o['Nu'], nu_term=o['NuT'], eres=o['eres'][..., 0])
     out.update({k: o[k] for k in INFO_FIELDS})
     return out
 
 
 def mpc_closed_loop_batch(A, B, H, X0, horizon, steps, phase0=0, D=None, d=None, ndcnt=None, q=None, Pf=None, tol=TOL, max_iter=MAX_ITER, return_traj=True,
-                          penalty=None):
+                          penalty=None, J=None, r=None, necnt=None, terminal=None):
     """The receding-horizon loop: at t = 0 .. steps-1 the QP of mpc_qp_batch from phase (phase0 + t) mod p, cold-started, u_0 applied, x <- A_k x + B_k u_0 (the
     linear plant, as closed_loop_batch does), all steps in one launch.  Arguments as mpc_qp_batch.
 
@@ -176,12 +234,49 @@ def mpc_closed_loop_batch(A, B, H, X0, horizon, steps, phase0=0, D=None, d=None,
     u0 [nb,ns,nu] (the first input of step 0) and the info fields of mpc_qp_batch (steps: steps finished).  An instance that fails at step t (status 1, 2, 3)
     keeps what it logged before: U, hres from t on, X from t + 1 on and XT are NaN, nact from t on and iters beyond t are -1.  X, U and the per-step logs are
     permuted views of time-major arrays.  With penalty (as in mpc_qp_batch) the dict gains nviol [nb,ns,steps] int32 (-1 from a failed step on); hres > 0
-    at a step whose applied stage violates a soft row."""
-    o = _run('mpc_closed_loop_batch', A, B, H, X0, horizon, steps, phase0, D, d, ndcnt, q, Pf, tol, max_iter, return_traj, False, penalty)
+    at a step whose applied stage violates a soft row.  With J or terminal (as in mpc_qp_batch) the dict gains eres [nb,ns,steps] = max|J z_0 - r| of the
+    applied stage (NaN from a failed step on)."""
+    o = _run('mpc_closed_loop_batch', A, B, H, X0, horizon, steps, phase0, D, d, ndcnt, q, Pf, tol, max_iter, return_traj, False, penalty, J, r, necnt, terminal)
     out = dict(X=o['X'], U=o['U'], iters=o['iters'], nact=o['nact'], hres=o['hres'], XT=o['XT'], u0=o['U0'], info=o['info'])
     if penalty is not None:
         out['nviol'] = o['nviol']
+    if J is not None or terminal is not None:
+        out['eres'] = o['eres']
     out.update({k: o[k] for k in INFO_FIELDS})
+    return out
+
+
+def _stack_eq(who, p, nx, n, J, r, terminal):
+    """J, r (single arrays or lists of p, None entries: no rows at that stage) and terminal (None, 'constraint', one matrix [nt,nx] or a list of p) -> dict J,
+    r, necnt, terminal of one problem."""
+    out = dict(J=None, r=None, necnt=None, terminal=None)
+    if J is None and r is not None:
+        raise ValueError('{}: r describes the rows of J, which is None'.format(who))
+    if J is not None:
+        Jl = [None if m is None else np.atleast_2d(_to_array(m)).astype(np.float64) for m in (J if isinstance(J, (list, tuple)) else [J] * p)]
+        rl = [None] * p if r is None else [None if v is None else _to_array(v).astype(np.float64).reshape(-1) for v in (r if isinstance(r, (list, tuple)) else [r] * p)]
+        if len(Jl) != p or len(rl) != p:
+            raise ValueError('{}: J, r must be single arrays or lists of p = {} (None: no rows at that stage)'.format(who, p))
+        cnts = [0 if m is None else m.shape[0] for m in Jl]
+        for k in range(p):
+            if (Jl[k] is not None and Jl[k].shape[1] != n) or (rl[k] is not None and rl[k].shape != (cnts[k],)):
+                raise ValueError('{}: J[{}] (rows, nx + nu = {}) with r[{}] (rows) or None expected'.format(who, k, n, k))
+        ne = max(cnts)
+        if ne:
+            Js = np.zeros((1, p, ne, n)); rs = np.zeros((1, p, ne))
+            for k in range(p):
+                if cnts[k]:
+                    Js[0, k, :cnts[k]] = Jl[k]
+                    if rl[k] is not None:
+                        rs[0, k, :cnts[k]] = rl[k]
+            out.update(J=Js, r=rs, necnt=np.asarray([cnts], np.int32))
+    if isinstance(terminal, str):
+        out['terminal'] = terminal                                          # (checked by the batch call)
+    elif terminal is not None:
+        Tl = [np.atleast_2d(_to_array(m)).astype(np.float64) for m in (terminal if isinstance(terminal, (list, tuple)) else [terminal] * p)]
+        if len(Tl) != p or any(m.shape != Tl[0].shape or m.shape[1] != nx for m in Tl):
+            raise ValueError('{}: terminal must be \'constraint\', one matrix [nt, nx = {}] or a list of p = {} of them'.format(who, nx, p))
+        out['terminal'] = np.ascontiguousarray(np.stack(Tl)[None])
     return out
 
 
@@ -240,36 +335,41 @@ def _stack_one(who, A, B, Q, R, N, x0, D, d, q, Pf, penalty=None):
     return As, Bs, Hs, np.ascontiguousarray(x[None, None]), dict(D=Ds, d=ds, ndcnt=cnt, q=qs, Pf=Pfs, penalty=pens)
 
 
-def mpc_step(A, B, Q, R, N, x0, horizon, phase0=0, D=None, d=None, q=None, Pf=None, tol=TOL, max_iter=MAX_ITER, penalty=None):
+def mpc_step(A, B, Q, R, N, x0, horizon, phase0=0, D=None, d=None, q=None, Pf=None, tol=TOL, max_iter=MAX_ITER, penalty=None, J=None, r=None, terminal=None):
     """One MPC step of one model in the reference's calling style: A, B, Q, R, N (the cross term) single matrices (p = 1) or lists of length p as in horizon_lqr,
     D, d the rows D_k [x; u] <= d_k (single arrays or lists of p; None entries: no rows at that stage), q, Pf likewise.  Returns (u0, X [horizon+1,nx],
     U [horizon,nu], lam [horizon,nd], info dict).  penalty: the weights of the soft rows, one vector (every stage) or a list of p vectors, one entry per row of
-    D_k; np.inf entries and None stages are hard.  With it info gains 'eps' [horizon,nd] (the slacks) and 'nviol'.  RuntimeError when the solve did not converge."""
+    D_k; np.inf entries and None stages are hard.  With it info gains 'eps' [horizon,nd] (the slacks) and 'nviol'.  J, r: the equality rows J_k [x; u] = r_k
+    (single arrays or lists of p, None entries: no rows at that stage; r None: zero); terminal: 'constraint' (x_N = 0), one matrix Tx [nt,nx] or a list of p
+    (Tx x_N = 0).  With them info gains 'nu' [horizon,ne], 'nu_term' [nt] and 'eres'.  RuntimeError when the solve did not converge (an infeasible problem)."""
     who = 'mpc_step'
     As, Bs, Hs, X0, kw = _stack_one(who, A, B, Q, R, N, x0, D, d, q, Pf, penalty)
-    r = mpc_qp_batch(As, Bs, Hs, X0, horizon, phase0, tol=tol, max_iter=max_iter, **kw)
-    st = int(r['status'][0, 0])
+    kw.update(_stack_eq(who, As.shape[1], As.shape[2], As.shape[2] + Bs.shape[3], J, r, terminal))
+    res = mpc_qp_batch(As, Bs, Hs, X0, horizon, phase0, tol=tol, max_iter=max_iter, **kw)
+    st = int(res['status'][0, 0])
     if st != 0:
-        raise RuntimeError('{}: the solve ended with status {} ({}) after {} iterations'.format(who, st, STATUS_NAMES.get(st), int(r['iters_total'][0, 0])))
-    return r['u0'][0, 0], r['X'][0, 0], r['U'][0, 0], r['lam'][0, 0], {k: r[k][0, 0] for k in INFO_FIELDS + ('nact', 'hres') + (('eps', 'nviol') if 'eps' in r else ())}
+        raise RuntimeError('{}: the solve ended with status {} ({}) after {} iterations'.format(who, st, STATUS_NAMES.get(st), int(res['iters_total'][0, 0])))
+    return res['u0'][0, 0], res['X'][0, 0], res['U'][0, 0], res['lam'][0, 0], {k: res[k][0, 0] for k in INFO_FIELDS + ('nact', 'hres') + (('eps', 'nviol') if 'eps' in res else ()) + (('nu', 'nu_term', 'eres') if 'nu' in res else ())}
 
 
-def mpc_closed_loop_sim(A, B, Q, R, N, x0, horizon, steps, phase0=0, D=None, d=None, q=None, Pf=None, tol=TOL, max_iter=MAX_ITER, penalty=None):
+def mpc_closed_loop_sim(A, B, Q, R, N, x0, horizon, steps, phase0=0, D=None, d=None, q=None, Pf=None, tol=TOL, max_iter=MAX_ITER, penalty=None, J=None,
+                        r=None, terminal=None):
     """The reference's closed_loop_sim with the inequality-constrained tracking MPC in the loop and the linear plant, one model in the calling style of mpc_step.
     Returns the reference's log: {'x': steps + 1 states, 'u': steps inputs, 'l': steps stage costs 1/2 z' H_k z + q_k' z, 'h': steps arrays d_k - D_k [x_t; u_t]
     (>= 0 when the rows hold; empty at a stage without rows)} and 'iters', 'nact'.  With penalty (as in mpc_step) 'h' stays d - D z (negative on a violated soft
     row), 'usc' holds the slack of the applied step, max(0, D z - d) on the soft rows and 0 on the hard ones (the reference's usc), and 'nviol' the count of the
-    solver.  RuntimeError when a step did not converge."""
+    solver.  With J, r, terminal (as in mpc_step) the log gains 'eres': max|J_k [x_t; u_t] - r_k| of every step.  RuntimeError when a step did not converge."""
     who = 'mpc_closed_loop_sim'
     As, Bs, Hs, X0, kw = _stack_one(who, A, B, Q, R, N, x0, D, d, q, Pf, penalty)
-    r = mpc_closed_loop_batch(As, Bs, Hs, X0, horizon, steps, phase0, tol=tol, max_iter=max_iter, **kw)
-    st = int(r['status'][0, 0])
+    kw.update(_stack_eq(who, As.shape[1], As.shape[2], As.shape[2] + Bs.shape[3], J, r, terminal))
+    res = mpc_closed_loop_batch(As, Bs, Hs, X0, horizon, steps, phase0, tol=tol, max_iter=max_iter, **kw)
+    st = int(res['status'][0, 0])
     if st != 0:
-        raise RuntimeError('{}: step {} of {} ended with status {} ({})'.format(who, int(r['steps'][0, 0]), int(steps), st, STATUS_NAMES.get(st)))
+        raise RuntimeError('{}: step {} of {} ended with status {} ({})'.format(who, int(res['steps'][0, 0]), int(steps), st, STATUS_NAMES.get(st)))
     T, p = int(steps), As.shape[1]
-    X, U = r['X'][0, 0], r['U'][0, 0]
-    log = {'x': [X[t].copy() for t in range(T + 1)], 'u': [U[t].copy() for t in range(T)], 'l': [], 'h': [], 'iters': [int(v) for v in r['iters'][0, 0]],
-           'nact': [int(v) for v in r['nact'][0, 0]]}
+    X, U = res['X'][0, 0], res['U'][0, 0]
+    log = {'x': [X[t].copy() for t in range(T + 1)], 'u': [U[t].copy() for t in range(T)], 'l': [], 'h': [], 'iters': [int(v) for v in res['iters'][0, 0]],
+           'nact': [int(v) for v in res['nact'][0, 0]]}
     for t in range(T):
         k = (int(phase0) + t) % p
         z = np.concatenate([X[t], U[t]])
@@ -280,7 +380,9 @@ def mpc_closed_loop_sim(A, B, Q, R, N, x0, horizon, steps, phase0=0, D=None, d=N
         if kw['penalty'] is not None:
             log.setdefault('usc', []).append(np.where(np.isfinite(kw['penalty'][0, k, :m]), np.maximum(0.0, -log['h'][-1]), 0.0))
     if kw['penalty'] is not None:
-        log['nviol'] = [int(v) for v in r['nviol'][0, 0]]
+        log['nviol'] = [int(v) for v in res['nviol'][0, 0]]
+    if 'eres' in res:
+        log['eres'] = [float(v) for v in res['eres'][0, 0]]
     return log
 
 
