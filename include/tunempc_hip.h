@@ -398,9 +398,10 @@ int tmpc_closed_loop_batch_device(int nb, int p, int nx, int mb, int nr, int ng,
  *     min  sum_{j<N} (1/2 z_j' H_k z_j + q_k' z_j) + 1/2 x_N' Pf_{k_N} x_N,   z_j = [x_j; u_j],   k = k_j = (k0 + j) mod p,
  *     s.t. x_{j+1} = A_k x_j + B_k u_j,  x_0 given,   D_k z_j <= d_k (first ndcnt_k rows of the stage),   j = 0 .. N-1,
  * solved at the steps t = 0 .. T-1 from the phase (k0 + t) mod p; u_0 is applied and x <- A_k x + B_k u_0 (the linear plant), one launch for the whole batch.
- * Not served (there are no arguments for them): a terminal right-hand side != 0, quadratic slack penalties, warm starts between steps, the nonlinear plant.
+ * Not served (there are no arguments for them): quadratic slack penalties, warm starts between steps, the nonlinear plant, nt > nx.
  * Soft rows (exact L1 slack penalties, the reference's `usc`): the tmpc_mpc_qp_soft_batch_* entries below.  Equality rows J z = r and the terminal
- * constraint Tx x_N = 0 (the reference's g and p_operator): the tmpc_mpc_qp_eq_batch_* entries below.
+ * constraint Tx x_N = 0 (the reference's g and p_operator): the tmpc_mpc_qp_eq_batch_* entries below.  The affine problem (a dynamics offset, a linear
+ * terminal cost, a terminal right-hand side, a plant that is not the model, a disturbance): the tmpc_mpc_qp_aff_batch_* entries below.
  * Method: primal-dual interior point with Mehrotra's predictor-corrector, started infeasible, the Newton system solved by a Riccati pass with a Cholesky
  * factorisation per stage; the stop rule is r_p <= tol, r_d <= tol, mu <= 1e-3 tol max(1, max lam), residuals relative to the scale of the problem (stated
  * in tmpc_mpc_qp.h and in tests/mpc_qp_reference.py).  H is used as (H + H') / 2, likewise Pf.
@@ -475,6 +476,34 @@ int tmpc_mpc_qp_eq_batch_device(int nb, int p, int nx, int mb, int nd, int N, in
                                 int max_iter, double* U0, double* XT, double* info, double* X, double* U, int32_t* iters, int32_t* nact, double* hres,
                                 double* Xol, double* Uol, double* Lam, const double* penalty, double* Eol, int32_t* nviol, int ne, const double* J,
                                 const double* r, const int32_t* necnt, int nt, const double* Tx, double* Nu, double* NuT, double* eres);
+
+/* The same step and loop on the AFFINE problem (the reference's controller in absolute coordinates, an estimated constant disturbance, an SQP subproblem):
+ *     x_{j+1} = A_k x_j + B_k u_j + c_k,   terminal cost 1/2 x_N' Pf x_N + qf_{k_N}' x_N,   Tx_{k_N} x_N = t_{k_N},
+ * and in the loop the plant x_{t+1} = Ap_k x_t + Bp_k u_0 + cp_k + W_t, k = (k0 + t) mod p.  The 43 arguments of the eq entries, then, each optional (NULL):
+ *   offset [nb][p][nx]         c, indexed by the phase like A;
+ *   qf [nb][p][nx]             indexed by k_N like Pf (legal without Pf);
+ *   terminal_rhs [nb][p][nt]   t, indexed by k_N like Tx (nx entries for nt = -1: x_N = t);
+ *   Ap [nb][p][nx][nx], Bp [nb][p][nx][mb]   the plant (both or neither; NULL: the model A, B);   cp [nb][p][nx]: its offset (NULL: the model's offset);
+ *   W [nb][ns][T][nx]          the disturbance of every step, unknown to the controller.
+ * XT is the plant's state after T steps; with T = 1 and no plant it is A x_0 + B u_0 + c.  hres, eres, nact, nviol stay functions of the applied z_0 of the
+ * model's QP.  The iteration is the one of the eq entries with r_dyn = [A B] z + c - x+, pi_N = Pf x_N + qf + Tx' nu_T and the terminal residual Tx x_N - t
+ * (tmpc_mpc_qp.h; tests/mpc_qp_affine_reference.py); the stop rule takes max|Tx x_N - t| / max(1, max|x|), and |c|, |t| enter no scale.  The kernels are
+ * AFF instantiations of the two EQ kernels with their LDS layout and workspace; a call without rows runs them with ne = nt = 0.  With all seven NULL the eq
+ * entry runs (the same bits).  A non-finite entry of the new arrays ends that instance with status 3 at the step that meets it (W_t, Ap, Bp, cp: at step
+ * t + 1, X[t + 1] holds the non-finite state); a t that cannot be reached ends with status 1.
+ * TMPC_E_ARG, besides the above: terminal_rhs with nt = 0, Ap without Bp or Bp without Ap. */
+int tmpc_mpc_qp_aff_batch_host(int nb, int p, int nx, int mb, int nd, int N, int ns, int T, int k0, const double* A, const double* B, const double* H,
+                               const double* q, const double* Pf, const double* D, const int32_t* ndcnt, const double* d, const double* X0, double tol,
+                               int max_iter, double* U0, double* XT, double* info, double* X, double* U, int32_t* iters, int32_t* nact, double* hres,
+                               double* Xol, double* Uol, double* Lam, const double* penalty, double* Eol, int32_t* nviol, int ne, const double* J,
+                               const double* r, const int32_t* necnt, int nt, const double* Tx, double* Nu, double* NuT, double* eres, const double* offset,
+                               const double* qf, const double* terminal_rhs, const double* Ap, const double* Bp, const double* cp, const double* W);
+int tmpc_mpc_qp_aff_batch_device(int nb, int p, int nx, int mb, int nd, int N, int ns, int T, int k0, const double* A, const double* B, const double* H,
+                                 const double* q, const double* Pf, const double* D, const int32_t* ndcnt, const double* d, const double* X0, double tol,
+                                 int max_iter, double* U0, double* XT, double* info, double* X, double* U, int32_t* iters, int32_t* nact, double* hres,
+                                 double* Xol, double* Uol, double* Lam, const double* penalty, double* Eol, int32_t* nviol, int ne, const double* J,
+                                 const double* r, const int32_t* necnt, int nt, const double* Tx, double* Nu, double* NuT, double* eres, const double* offset,
+                                 const double* qf, const double* terminal_rhs, const double* Ap, const double* Bp, const double* cp, const double* W);
 
 /* Accumulated hipEvent timings since the last call (ms) when TMPC_FLAG_PROFILE is set, 16 doubles:
  * out[0] stage_pre+ctrl, [1] schur assembly, [2] block factorisation (all kernels of tmpc_cr.h's factor phase), [3] predictor

@@ -27,6 +27,7 @@ EXPORTS = [
     'tmpc_periodic_lqr_ctg_batch_host', 'tmpc_periodic_lqr_ctg_batch_device', 'tmpc_horizon_lqr_batch_host', 'tmpc_horizon_lqr_batch_device',
     'tmpc_closed_loop_batch_host', 'tmpc_closed_loop_batch_device', 'tmpc_mpc_qp_batch_host', 'tmpc_mpc_qp_batch_device',
     'tmpc_mpc_qp_soft_batch_host', 'tmpc_mpc_qp_soft_batch_device', 'tmpc_mpc_qp_eq_batch_host', 'tmpc_mpc_qp_eq_batch_device',
+    'tmpc_mpc_qp_aff_batch_host', 'tmpc_mpc_qp_aff_batch_device',
     'tmpc_last_error', 'tmpc_version',
 ]
 # ... and in include/tunempc_hip_debug.h (unit-test / diagnostic entries)
@@ -159,6 +160,10 @@ def load_library():
     lib.tmpc_mpc_qp_eq_batch_host.argtypes = lib.tmpc_mpc_qp_soft_batch_host.argtypes + [C.c_int, dp, dp, ip, C.c_int, dp, dp, dp, dp]
     lib.tmpc_mpc_qp_eq_batch_device.restype = C.c_int
     lib.tmpc_mpc_qp_eq_batch_device.argtypes = lib.tmpc_mpc_qp_soft_batch_device.argtypes + [C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, vp]
+    lib.tmpc_mpc_qp_aff_batch_host.restype = C.c_int
+    lib.tmpc_mpc_qp_aff_batch_host.argtypes = lib.tmpc_mpc_qp_eq_batch_host.argtypes + [dp] * 7
+    lib.tmpc_mpc_qp_aff_batch_device.restype = C.c_int
+    lib.tmpc_mpc_qp_aff_batch_device.argtypes = lib.tmpc_mpc_qp_eq_batch_device.argtypes + [vp] * 7
     lib.tmpc_get_profile.restype = C.c_int
     lib.tmpc_get_profile.argtypes = [vp, dp]
     lib.tmpc_get_trace.restype = C.c_int
@@ -996,11 +1001,14 @@ def _mpc_qp_eq_terminal(Tx, nx):
     return int(Tx.shape[2]), Tx, int(Tx.shape[2])
 
 
-def mpc_qp_eq_batch_host(A, B, H, q, Pf, D, ndcnt, d, penalty, J, r, necnt, Tx, X0, N, T, k0, tol, max_iter, return_traj, return_ol):
+def mpc_qp_eq_batch_host(A, B, H, q, Pf, D, ndcnt, d, penalty, J, r, necnt, Tx, X0, N, T, k0, tol, max_iter, return_traj, return_ol, aff=None):
     """tmpc_mpc_qp_eq_batch_host on validated, contiguous numpy arrays (penalty, J [nb,p,ne,n], r, necnt int32 None or arrays; Tx None, 'constraint' or
     [nb,p,nt,nx]) -> the dict of mpc_qp_soft_batch_host (Eol None and no nviol without penalty) with Nu [nb,ns,N,ne], NuT [nb,ns,nt] (None without return_ol)
-    and eres [nb,ns,T]."""
+    and eres [nb,ns,T].  aff (mpc_qp_aff_batch_host): the seven arrays offset, qf, terminal_rhs, Ap, Bp, cp, W or None each -> tmpc_mpc_qp_aff_batch_host."""
     lib = load_library()
+    entry, name, tail = lib.tmpc_mpc_qp_eq_batch_host, 'tmpc_mpc_qp_eq_batch_host', ()
+    if aff is not None:
+        entry, name, tail = lib.tmpc_mpc_qp_aff_batch_host, 'tmpc_mpc_qp_aff_batch_host', tuple(_dptr(a) for a in aff)
     nb, p, nx, mb = B.shape
     ns, T, N = X0.shape[1], int(T), int(N)
     nd = 0 if D is None else D.shape[2]
@@ -1018,14 +1026,14 @@ def mpc_qp_eq_batch_host(A, B, H, q, Pf, D, ndcnt, d, penalty, J, r, necnt, Tx, 
     NuT = np.empty((nb, ns, ntr)) if return_ol else None
     U0 = np.empty((nb, ns, mb)); XT = np.empty((nb, ns, nx)); info = np.zeros((nb, ns, MPC_QP_INFO_STRIDE))
     opt = lambda a: _dptr(a) if a is not None and a.size else None
-    rc = lib.tmpc_mpc_qp_eq_batch_host(nb, p, nx, mb, nd, N, ns, T, int(k0), _dptr(A), _dptr(B), _dptr(H), _dptr(q), _dptr(Pf), _dptr(D) if nd else None,
-                                       _iptr(ndcnt) if nd else None, _dptr(d) if nd else None, _dptr(X0), float(tol), int(max_iter), _dptr(U0), _dptr(XT),
-                                       _dptr(info), _dptr(X), _dptr(U), _iptr(iters), _iptr(nact), _dptr(hres), _dptr(Xol), _dptr(Uol), opt(Lam), _dptr(penalty),
-                                       opt(Eol), _iptr(nviol), ne, _dptr(J) if ne else None, _dptr(r) if ne else None, _iptr(necnt) if ne else None, nt, _dptr(Txa),
-                                       opt(Nu), opt(NuT), _dptr(eres))
+    rc = entry(nb, p, nx, mb, nd, N, ns, T, int(k0), _dptr(A), _dptr(B), _dptr(H), _dptr(q), _dptr(Pf), _dptr(D) if nd else None,
+               _iptr(ndcnt) if nd else None, _dptr(d) if nd else None, _dptr(X0), float(tol), int(max_iter), _dptr(U0), _dptr(XT),
+               _dptr(info), _dptr(X), _dptr(U), _iptr(iters), _iptr(nact), _dptr(hres), _dptr(Xol), _dptr(Uol), opt(Lam), _dptr(penalty),
+               opt(Eol), _iptr(nviol), ne, _dptr(J) if ne else None, _dptr(r) if ne else None, _iptr(necnt) if ne else None, nt, _dptr(Txa),
+               opt(Nu), opt(NuT), _dptr(eres), *tail)
     if rc == -1:
         raise ValueError(lib.tmpc_last_error().decode())
-    _check_lqr(lib, rc, 'tmpc_mpc_qp_eq_batch_host')
+    _check_lqr(lib, rc, name)
     out = _mpc_qp_views(U0, XT, info, X, U, iters, nact, hres, Xol, Uol, Lam, lambda a: a.transpose(0, 2, 1, 3), lambda a: a.transpose(0, 2, 1))
     out.update(Nu=Nu, NuT=NuT, eres=eres.transpose(0, 2, 1))
     if penalty is not None:
@@ -1033,10 +1041,12 @@ def mpc_qp_eq_batch_host(A, B, H, q, Pf, D, ndcnt, d, penalty, J, r, necnt, Tx, 
     return out
 
 
-def mpc_qp_eq_batch_device(A, B, H, q, Pf, D, ndcnt, d, penalty, J, r, necnt, Tx, X0, N, T, k0, tol, max_iter, return_traj, return_ol):
-    """tmpc_mpc_qp_eq_batch_device on validated, contiguous torch tensors of one GPU -> the dict of mpc_qp_eq_batch_host with torch tensors."""
+def mpc_qp_eq_batch_device(A, B, H, q, Pf, D, ndcnt, d, penalty, J, r, necnt, Tx, X0, N, T, k0, tol, max_iter, return_traj, return_ol, aff=None):
+    """tmpc_mpc_qp_eq_batch_device on validated, contiguous torch tensors of one GPU -> the dict of mpc_qp_eq_batch_host with torch tensors.  aff as there:
+    tmpc_mpc_qp_aff_batch_device."""
     import torch
     lib = load_library()
+    entry, name = (lib.tmpc_mpc_qp_eq_batch_device, 'tmpc_mpc_qp_eq_batch_device') if aff is None else (lib.tmpc_mpc_qp_aff_batch_device, 'tmpc_mpc_qp_aff_batch_device')
     nb, p, nx, mb = B.shape
     ns, T, N = X0.shape[1], int(T), int(N)
     nd = 0 if D is None else D.shape[2]
@@ -1059,18 +1069,30 @@ def mpc_qp_eq_batch_device(A, B, H, q, Pf, D, ndcnt, d, penalty, J, r, necnt, Tx
     ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
     with torch.cuda.device(dev):
         torch.cuda.current_stream(dev).synchronize()      # the entry runs on the null stream: the inputs must be complete
-        rc = lib.tmpc_mpc_qp_eq_batch_device(nb, p, nx, mb, nd, N, ns, T, int(k0), ptr(A), ptr(B), ptr(H), ptr(q), ptr(Pf), ptr(D) if nd else None,
-                                             ptr(ndcnt) if nd else None, ptr(d) if nd else None, ptr(X0), float(tol), int(max_iter), ptr(U0), ptr(XT), ptr(info),
-                                             ptr(X), ptr(U), ptr(iters), ptr(nact), ptr(hres), ptr(Xol), ptr(Uol), ptr(Lam), ptr(penalty), ptr(Eol), ptr(nviol), ne,
-                                             ptr(J) if ne else None, ptr(r) if ne else None, ptr(necnt) if ne else None, nt, ptr(Txa), ptr(Nu), ptr(NuT), ptr(eres))
+        rc = entry(nb, p, nx, mb, nd, N, ns, T, int(k0), ptr(A), ptr(B), ptr(H), ptr(q), ptr(Pf), ptr(D) if nd else None,
+                   ptr(ndcnt) if nd else None, ptr(d) if nd else None, ptr(X0), float(tol), int(max_iter), ptr(U0), ptr(XT), ptr(info),
+                   ptr(X), ptr(U), ptr(iters), ptr(nact), ptr(hres), ptr(Xol), ptr(Uol), ptr(Lam), ptr(penalty), ptr(Eol), ptr(nviol), ne,
+                   ptr(J) if ne else None, ptr(r) if ne else None, ptr(necnt) if ne else None, nt, ptr(Txa), ptr(Nu), ptr(NuT), ptr(eres),
+                   *(() if aff is None else tuple(ptr(a) for a in aff)))
     if rc == -1:
         raise ValueError(lib.tmpc_last_error().decode())
-    _check_lqr(lib, rc, 'tmpc_mpc_qp_eq_batch_device')
+    _check_lqr(lib, rc, name)
     out = _mpc_qp_views(U0, XT, info, X, U, iters, nact, hres, Xol, Uol, Lam, lambda a: a.permute(0, 2, 1, 3), lambda a: a.permute(0, 2, 1))
     out.update(Nu=Nu, NuT=NuT, eres=eres.permute(0, 2, 1))
     if penalty is not None:
         out.update(Eol=Eol, nviol=nviol.permute(0, 2, 1))
     return out
+
+
+def mpc_qp_aff_batch_host(A, B, H, q, Pf, D, ndcnt, d, penalty, J, r, necnt, Tx, aff, X0, N, T, k0, tol, max_iter, return_traj, return_ol):
+    """tmpc_mpc_qp_aff_batch_host on validated, contiguous numpy arrays: the arguments of mpc_qp_eq_batch_host and aff = (offset, qf, terminal_rhs, Ap, Bp, cp,
+    W), None or an array each -> the dict of mpc_qp_eq_batch_host."""
+    return mpc_qp_eq_batch_host(A, B, H, q, Pf, D, ndcnt, d, penalty, J, r, necnt, Tx, X0, N, T, k0, tol, max_iter, return_traj, return_ol, aff=tuple(aff))
+
+
+def mpc_qp_aff_batch_device(A, B, H, q, Pf, D, ndcnt, d, penalty, J, r, necnt, Tx, aff, X0, N, T, k0, tol, max_iter, return_traj, return_ol):
+    """tmpc_mpc_qp_aff_batch_device on validated, contiguous torch tensors of one GPU -> the dict of mpc_qp_aff_batch_host with torch tensors."""
+    return mpc_qp_eq_batch_device(A, B, H, q, Pf, D, ndcnt, d, penalty, J, r, necnt, Tx, X0, N, T, k0, tol, max_iter, return_traj, return_ol, aff=tuple(aff))
 
 
 def cr_schedule(p):

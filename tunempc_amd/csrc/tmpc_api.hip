@@ -2223,9 +2223,11 @@ static thread_local EigScratch g_mpc_qp_ws;           // workspace slots of both
 static int mpc_qp_launch(int nb, int p, int nx, int mb, int nd, int N, int ns, int T, int k0, const double* A, const double* B, const double* H, const double* q,
                          const double* Pf, const double* D, const int32_t* ndcnt, const double* d, const double* X0, double tol, int max_iter, double* U0,
                          double* XT, double* info, double* X, double* U, int32_t* iters, int32_t* nact, double* hres, double* Xol, double* Uol, double* Lam,
-                         const double* penalty = nullptr, double* Eol = nullptr, int32_t* nviol = nullptr, const MpcQpEqArgs* eq = nullptr) {
+                         const double* penalty = nullptr, double* Eol = nullptr, int32_t* nviol = nullptr, const MpcQpEqArgs* eq = nullptr,
+                         const MpcQpAff* aff = nullptr) {
   // penalty: the SOFT instantiation with its longer LDS layout and workspace slots; without it the hard kernel (Eol, nviol are not passed then)
   // eq: the EQ instantiations (equality rows and / or terminal rows), their layout after the hard or soft one
+  // aff (only with eq): the AFF instantiations of the two EQ kernels, the same layouts
   const MpcQpEqArgs none;
   const MpcQpEqArgs& e = eq ? *eq : none;
   const size_t lds_bytes = (size_t)(eq ? mpc_qp_eq_lds(nx, mb, nd, e.ne, penalty != nullptr).total
@@ -2236,13 +2238,15 @@ static int mpc_qp_launch(int nb, int p, int nx, int mb, int nd, int N, int ns, i
   if (slots * per > MQ_WS_CAP_BYTES) slots = MQ_WS_CAP_BYTES / per;
   if (slots < 1) slots = 1;
   HIPCHK(g_mpc_qp_ws.reserve((size_t)(slots * per)));
-  auto kern = eq ? (penalty ? k_mpc_qp<true, true> : k_mpc_qp<false, true>) : (penalty ? k_mpc_qp<true, false> : k_mpc_qp<false, false>);
+  auto kern = eq ? (penalty ? k_mpc_qp<true, true, false> : k_mpc_qp<false, true, false>) : (penalty ? k_mpc_qp<true, false, false> : k_mpc_qp<false, false, false>);
+  if (eq && aff) kern = penalty ? k_mpc_qp<true, true, true> : k_mpc_qp<false, true, true>;
+  const MpcQpAff no_aff = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   HIPCHK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LQR_LDS_BYTES));
   int lcw = 0;
   while ((1 << lcw) < nx + mb) ++lcw;
   hipLaunchKernelGGL(kern, dim3((unsigned)slots), dim3(LQR_NT), lds_bytes, 0, p, nx, mb, nd, lcw, N, ns, T, k0, ninst, A, B, H, q, Pf, D, (const int*)ndcnt, d,
                      X0, tol, max_iter, (double*)g_mpc_qp_ws.p, U0, XT, info, X, U, (int*)iters, (int*)nact, hres, Xol, Uol, Lam, penalty, Eol, (int*)nviol,
-                     e.ne, e.J, e.r, (const int*)e.necnt, e.nt, e.Tx, e.Nu, e.NuT, e.eres);
+                     e.ne, e.J, e.r, (const int*)e.necnt, e.nt, e.Tx, e.Nu, e.NuT, e.eres, aff ? *aff : no_aff);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(0));
   return TMPC_OK;
@@ -2448,17 +2452,34 @@ static int mpc_qp_eq_check(const char* who, int nx, int mb, int nd, int N, bool 
   return TMPC_OK;
 }
 
-int tmpc_mpc_qp_eq_batch_device(int nb, int p, int nx, int mb, int nd, int N, int ns, int T, int k0, const double* A, const double* B, const double* H,
-                                const double* q, const double* Pf, const double* D, const int32_t* ndcnt, const double* d, const double* X0, double tol,
-                                int max_iter, double* U0, double* XT, double* info, double* X, double* U, int32_t* iters, int32_t* nact, double* hres,
-                                double* Xol, double* Uol, double* Lam, const double* penalty, double* Eol, int32_t* nviol, int ne, const double* J,
-                                const double* r, const int32_t* necnt, int nt, const double* Tx, double* Nu, double* NuT, double* eres) {
-  const char* who = "tmpc_mpc_qp_eq_batch_device";
+// The arguments of the AFF instantiations (tmpc_mpc_qp.h): terminal_rhs needs terminal rows, Ap and Bp come together.  aff null or all seven null: no check.
+static bool mpc_qp_aff_any(const MpcQpAff* a) { return a && (a->c || a->qf || a->t || a->Ap || a->Bp || a->cp || a->W); }
+static int mpc_qp_aff_check(const char* who, int nt, const MpcQpAff* a) {
+  if (!mpc_qp_aff_any(a)) return TMPC_OK;
+  if (a->t && nt == 0) {
+    snprintf(g_err, sizeof(g_err), "%s: bad argument (terminal_rhs describes the terminal rows; got nt = 0)", who);
+    return TMPC_E_ARG;
+  }
+  if ((a->Ap != nullptr) != (a->Bp != nullptr)) {
+    snprintf(g_err, sizeof(g_err), "%s: bad argument (the plant's Ap and Bp come together; got %s without %s)", who, a->Ap ? "Ap" : "Bp", a->Ap ? "Bp" : "Ap");
+    return TMPC_E_ARG;
+  }
+  return TMPC_OK;
+}
+
+// Both eq entries and both aff entries: aff null or all seven null is the eq entry, statement by statement.
+static int mpc_qp_eq_device(const char* who, int nb, int p, int nx, int mb, int nd, int N, int ns, int T, int k0, const double* A, const double* B, const double* H,
+                            const double* q, const double* Pf, const double* D, const int32_t* ndcnt, const double* d, const double* X0, double tol,
+                            int max_iter, double* U0, double* XT, double* info, double* X, double* U, int32_t* iters, int32_t* nact, double* hres,
+                            double* Xol, double* Uol, double* Lam, const double* penalty, double* Eol, int32_t* nviol, int ne, const double* J,
+                            const double* r, const int32_t* necnt, int nt, const double* Tx, double* Nu, double* NuT, double* eres, const MpcQpAff* aff) {
   int rc = mpc_qp_check(who, nb, p, nx, mb, nd, N, ns, T, k0, A, B, H, D, ndcnt, d, X0, tol, max_iter, U0, XT, info);
   if (rc == TMPC_OK) rc = mpc_qp_soft_check(who, nx, mb, nd, N, penalty);
   if (rc == TMPC_OK) rc = mpc_qp_eq_check(who, nx, mb, nd, N, penalty != nullptr, ne, J, r, necnt, nt, Tx);
+  if (rc == TMPC_OK) rc = mpc_qp_aff_check(who, nt, aff);
   if (rc != TMPC_OK) return rc;
-  if (ne == 0 && nt == 0) {
+  if (!mpc_qp_aff_any(aff)) aff = nullptr;
+  if (ne == 0 && nt == 0 && !aff) {
     if (eres) HIPCHK(hipMemsetAsync(eres, 0, (size_t)nb * T * ns * 8, 0));
     return tmpc_mpc_qp_soft_batch_device(nb, p, nx, mb, nd, N, ns, T, k0, A, B, H, q, Pf, D, ndcnt, d, X0, tol, max_iter, U0, XT, info, X, U, iters, nact, hres,
                                          Xol, Uol, Lam, penalty, Eol, nviol);
@@ -2470,23 +2491,45 @@ int tmpc_mpc_qp_eq_batch_device(int nb, int p, int nx, int mb, int nd, int N, in
   MpcQpEqArgs e;
   e.ne = ne; e.J = J; e.r = r; e.necnt = necnt; e.nt = nt < 0 ? nx : nt; e.Tx = Tx; e.Nu = Nu; e.NuT = NuT; e.eres = eres;
   return mpc_qp_launch(nb, p, nx, mb, nd, N, ns, T, k0, A, B, H, q, Pf, D, ndcnt, d, X0, tol, max_iter, U0, XT, info, X, U, iters, nact, hres, Xol, Uol, Lam,
-                       penalty, penalty ? Eol : nullptr, penalty ? nviol : nullptr, &e);
+                       penalty, penalty ? Eol : nullptr, penalty ? nviol : nullptr, &e, aff);
+}
+
+int tmpc_mpc_qp_eq_batch_device(int nb, int p, int nx, int mb, int nd, int N, int ns, int T, int k0, const double* A, const double* B, const double* H,
+                                const double* q, const double* Pf, const double* D, const int32_t* ndcnt, const double* d, const double* X0, double tol,
+                                int max_iter, double* U0, double* XT, double* info, double* X, double* U, int32_t* iters, int32_t* nact, double* hres,
+                                double* Xol, double* Uol, double* Lam, const double* penalty, double* Eol, int32_t* nviol, int ne, const double* J,
+                                const double* r, const int32_t* necnt, int nt, const double* Tx, double* Nu, double* NuT, double* eres) {
+  return mpc_qp_eq_device("tmpc_mpc_qp_eq_batch_device", nb, p, nx, mb, nd, N, ns, T, k0, A, B, H, q, Pf, D, ndcnt, d, X0, tol, max_iter, U0, XT, info, X, U, iters,
+                          nact, hres, Xol, Uol, Lam, penalty, Eol, nviol, ne, J, r, necnt, nt, Tx, Nu, NuT, eres, nullptr);
+}
+
+int tmpc_mpc_qp_aff_batch_device(int nb, int p, int nx, int mb, int nd, int N, int ns, int T, int k0, const double* A, const double* B, const double* H,
+                                 const double* q, const double* Pf, const double* D, const int32_t* ndcnt, const double* d, const double* X0, double tol,
+                                 int max_iter, double* U0, double* XT, double* info, double* X, double* U, int32_t* iters, int32_t* nact, double* hres,
+                                 double* Xol, double* Uol, double* Lam, const double* penalty, double* Eol, int32_t* nviol, int ne, const double* J,
+                                 const double* r, const int32_t* necnt, int nt, const double* Tx, double* Nu, double* NuT, double* eres, const double* offset,
+                                 const double* qf, const double* terminal_rhs, const double* Ap, const double* Bp, const double* cp, const double* W) {
+  const MpcQpAff aff = {offset, qf, terminal_rhs, Ap, Bp, cp, W};
+  return mpc_qp_eq_device("tmpc_mpc_qp_aff_batch_device", nb, p, nx, mb, nd, N, ns, T, k0, A, B, H, q, Pf, D, ndcnt, d, X0, tol, max_iter, U0, XT, info, X, U, iters,
+                          nact, hres, Xol, Uol, Lam, penalty, Eol, nviol, ne, J, r, necnt, nt, Tx, Nu, NuT, eres, &aff);
 }
 
 static thread_local EigScratch g_mpc_qp_eq_scratch;      // device images of the host entry with equality rows
 
-int tmpc_mpc_qp_eq_batch_host(int nb, int p, int nx, int mb, int nd, int N, int ns, int T, int k0, const double* A, const double* B, const double* H,
-                              const double* q, const double* Pf, const double* D, const int32_t* ndcnt, const double* d, const double* X0, double tol,
-                              int max_iter, double* U0, double* XT, double* info, double* X, double* U, int32_t* iters, int32_t* nact, double* hres,
-                              double* Xol, double* Uol, double* Lam, const double* penalty, double* Eol, int32_t* nviol, int ne, const double* J,
-                              const double* r, const int32_t* necnt, int nt, const double* Tx, double* Nu, double* NuT, double* eres) {
-  const char* who = "tmpc_mpc_qp_eq_batch_host";
+// (aff: HOST pointers here)
+static int mpc_qp_eq_host(const char* who, int nb, int p, int nx, int mb, int nd, int N, int ns, int T, int k0, const double* A, const double* B, const double* H,
+                          const double* q, const double* Pf, const double* D, const int32_t* ndcnt, const double* d, const double* X0, double tol,
+                          int max_iter, double* U0, double* XT, double* info, double* X, double* U, int32_t* iters, int32_t* nact, double* hres,
+                          double* Xol, double* Uol, double* Lam, const double* penalty, double* Eol, int32_t* nviol, int ne, const double* J,
+                          const double* r, const int32_t* necnt, int nt, const double* Tx, double* Nu, double* NuT, double* eres, const MpcQpAff* aff) {
   int rc = mpc_qp_check(who, nb, p, nx, mb, nd, N, ns, T, k0, A, B, H, D, ndcnt, d, X0, tol, max_iter, U0, XT, info);
   if (rc == TMPC_OK) rc = mpc_qp_soft_check(who, nx, mb, nd, N, penalty);
   if (rc == TMPC_OK) rc = mpc_qp_eq_check(who, nx, mb, nd, N, penalty != nullptr, ne, J, r, necnt, nt, Tx);
+  if (rc == TMPC_OK) rc = mpc_qp_aff_check(who, nt, aff);
   if (rc != TMPC_OK) return rc;
+  if (!mpc_qp_aff_any(aff)) aff = nullptr;
   const size_t st = (size_t)nb * p, sn = (size_t)nb * ns, n = (size_t)nx + mb, cS = sn * T;
-  if (ne == 0 && nt == 0) {
+  if (ne == 0 && nt == 0 && !aff) {
     rc = tmpc_mpc_qp_soft_batch_host(nb, p, nx, mb, nd, N, ns, T, k0, A, B, H, q, Pf, D, ndcnt, d, X0, tol, max_iter, U0, XT, info, X, U, iters, nact, hres, Xol,
                                      Uol, Lam, penalty, Eol, nviol);
     if (rc != TMPC_OK) return rc;
@@ -2518,6 +2561,10 @@ int tmpc_mpc_qp_eq_batch_host(int nb, int p, int nx, int mb, int nd, int N, int 
   const int oUo = add(nullptr, Uol, sn * N * mb * 8), oL = add(nullptr, Lam, sn * N * nd * 8), oE = add(nullptr, penalty ? Eol : nullptr, sn * N * nd * 8);
   const int onv = add(nullptr, penalty ? nviol : nullptr, cS * sizeof(int32_t)), oNu = add(nullptr, Nu, sn * N * ne * 8), oNT = add(nullptr, NuT, sn * ntk * 8);
   const int oer = add(nullptr, eres, cS * 8);
+  const int ic = add(aff ? aff->c : nullptr, nullptr, st * nx * 8), iqf = add(aff ? aff->qf : nullptr, nullptr, st * nx * 8);
+  const int itr = add(aff ? aff->t : nullptr, nullptr, st * ntk * 8), iAp = add(aff ? aff->Ap : nullptr, nullptr, st * nx * nx * 8);
+  const int iBp = add(aff ? aff->Bp : nullptr, nullptr, st * nx * mb * 8), icp = add(aff ? aff->cp : nullptr, nullptr, st * nx * 8);
+  const int iW = add(aff ? aff->W : nullptr, nullptr, cS * nx * 8);
   HIPCHK(g_mpc_qp_eq_scratch.reserve(total + 8));
   char* base = (char*)g_mpc_qp_eq_scratch.p;
   auto dev = [&](int i) -> void* { return im[i].bytes ? base + im[i].off : nullptr; };
@@ -2525,11 +2572,13 @@ int tmpc_mpc_qp_eq_batch_host(int nb, int p, int nx, int mb, int nd, int N, int 
   MpcQpEqArgs e;
   e.ne = ne; e.J = (const double*)dev(iJ); e.r = (const double*)dev(ir); e.necnt = (const int32_t*)dev(iec); e.nt = ntk; e.Tx = (const double*)dev(iTx);
   e.Nu = (double*)dev(oNu); e.NuT = (double*)dev(oNT); e.eres = (double*)dev(oer);
+  const MpcQpAff daff = {(const double*)dev(ic), (const double*)dev(iqf), (const double*)dev(itr), (const double*)dev(iAp), (const double*)dev(iBp),
+                         (const double*)dev(icp), (const double*)dev(iW)};
   const int rl = mpc_qp_launch(nb, p, nx, mb, nd, N, ns, T, k0, (const double*)dev(iA), (const double*)dev(iB), (const double*)dev(iH), (const double*)dev(iq),
                                (const double*)dev(iPf), (const double*)dev(iD), (const int32_t*)dev(icnt), (const double*)dev(id), (const double*)dev(i0), tol,
                                max_iter, (double*)dev(oU0), (double*)dev(oXT), (double*)dev(oI), (double*)dev(oX), (double*)dev(oU), (int32_t*)dev(oit),
                                (int32_t*)dev(ona), (double*)dev(oh), (double*)dev(oXo), (double*)dev(oUo), (double*)dev(oL), (const double*)dev(ipen),
-                               (double*)dev(oE), (int32_t*)dev(onv), &e);
+                               (double*)dev(oE), (int32_t*)dev(onv), &e, aff ? &daff : nullptr);
   if (rl != TMPC_OK) return rl;
   for (int i = 0; i < (int)im.size(); ++i) if (im[i].out) HIPCHK(hipMemcpy(im[i].out, dev(i), im[i].bytes, hipMemcpyDeviceToHost));
   if (!penalty) {
@@ -2537,6 +2586,28 @@ int tmpc_mpc_qp_eq_batch_host(int nb, int p, int nx, int mb, int nd, int N, int 
     if (nviol) for (size_t i = 0; i < cS; ++i) nviol[i] = 0;
   }
   return TMPC_OK;
+}
+
+int tmpc_mpc_qp_eq_batch_host(int nb, int p, int nx, int mb, int nd, int N, int ns, int T, int k0, const double* A, const double* B, const double* H,
+                              const double* q, const double* Pf, const double* D, const int32_t* ndcnt, const double* d, const double* X0, double tol,
+                              int max_iter, double* U0, double* XT, double* info, double* X, double* U, int32_t* iters, int32_t* nact, double* hres,
+                              double* Xol, double* Uol, double* Lam, const double* penalty, double* Eol, int32_t* nviol, int ne, const double* J,
+                              const double* r, const int32_t* necnt, int nt, const double* Tx, double* Nu, double* NuT, double* eres) {
+  return mpc_qp_eq_host("tmpc_mpc_qp_eq_batch_host", nb, p, nx, mb, nd, N, ns, T, k0, A, B, H, q, Pf, D, ndcnt, d, X0, tol, max_iter, U0, XT, info, X, U, iters, nact,
+                        hres, Xol, Uol, Lam, penalty, Eol, nviol, ne, J, r, necnt, nt, Tx, Nu, NuT, eres, nullptr);
+}
+
+// The affine problem (tmpc_mpc_qp.h, the AFF instantiations): the 43 arguments of the eq entries, then offset, qf, terminal_rhs, Ap, Bp, cp, W.  All seven
+// NULL: the eq entry.
+int tmpc_mpc_qp_aff_batch_host(int nb, int p, int nx, int mb, int nd, int N, int ns, int T, int k0, const double* A, const double* B, const double* H,
+                               const double* q, const double* Pf, const double* D, const int32_t* ndcnt, const double* d, const double* X0, double tol,
+                               int max_iter, double* U0, double* XT, double* info, double* X, double* U, int32_t* iters, int32_t* nact, double* hres,
+                               double* Xol, double* Uol, double* Lam, const double* penalty, double* Eol, int32_t* nviol, int ne, const double* J,
+                               const double* r, const int32_t* necnt, int nt, const double* Tx, double* Nu, double* NuT, double* eres, const double* offset,
+                               const double* qf, const double* terminal_rhs, const double* Ap, const double* Bp, const double* cp, const double* W) {
+  const MpcQpAff aff = {offset, qf, terminal_rhs, Ap, Bp, cp, W};
+  return mpc_qp_eq_host("tmpc_mpc_qp_aff_batch_host", nb, p, nx, mb, nd, N, ns, T, k0, A, B, H, q, Pf, D, ndcnt, d, X0, tol, max_iter, U0, XT, info, X, U, iters, nact,
+                        hres, Xol, Uol, Lam, penalty, Eol, nviol, ne, J, r, necnt, nt, Tx, Nu, NuT, eres, &aff);
 }
 
 int tmpc_tracking_reference_host(tmpc_handle* h, int nstage, const double* Hc, const double* q, const double* wref,

@@ -3,8 +3,9 @@
 //   min  sum_{j<N} (1/2 z_j' H_k z_j + q_k' z_j) + 1/2 x_N' Pf_{k_N} x_N,   z_j = [x_j; u_j],   k = k_j = (k0 + j) mod p,
 //   s.t. x_{j+1} = A_k x_j + B_k u_j,  x_0 given,   D_k z_j <= d_k (first ndcnt_k rows),   j = 0 .. N-1,
 //        and, in the EQ instantiations,   J_k z_j = r_k (first necnt_k rows),  j = 0 .. N-1,   Tx_{k_N} x_N = 0 (nt rows; Tx absent: the identity, x_N = 0),
-// solved T times in a row: step t starts at phase (k0 + t) mod p, applies u_0 and moves x <- A_k x + B_k u_0 on the linear plant.
-// Not served: a terminal right-hand side != 0, quadratic slack penalties, warm starts between the steps, the nonlinear plant.
+// solved T times in a row: step t starts at phase (k0 + t) mod p, applies u_0 and moves x <- A_k x + B_k u_0 on the linear plant.  The AFF instantiations
+// (below) add the dynamics offset c_k, the terminal cost qf' x_N, the terminal right-hand side t and a plant that is not the model.
+// Not served: quadratic slack penalties, warm starts between the steps, the nonlinear plant, nt > nx.
 //
 // Method: a primal-dual interior-point method with Mehrotra's predictor-corrector, started infeasible (z = 0 but x_0, s_i = max(d_i, 1), lam_i = 1).  The
 // multipliers of the dynamics are not variables: they are the adjoint of the iterate, pi_N = Pf x_N, [pi_j; r_u] = H z_j + q + D' lam_j + [A B]' pi_{j+1}, so
@@ -68,6 +69,20 @@
 // inequality rows.  eres = max|J z_0 - r| of the applied stage (0 at a stage without rows).  LDS: J_k [ne x ld] and the vectors nu, J z - r, r after the hard or
 // soft layout (mpc_qp_eq_lds); workspace: NUe, REQ [N][ne] and NUT [nt] after the hard or soft workspace (mpc_qp_eq_ws_doubles); nt <= nx (Tx x_N and dnu_T
 // share the last vector slot of the hard layout).  With EQ = false both instantiations are what they were, statement by statement.
+//
+// The affine problem (the AFF instantiations; they are EQ instantiations, with or without SOFT, and a call without rows runs them with ne = nt = 0):
+//   x_{j+1} = A_k x_j + B_k u_j + c_k,   terminal cost 1/2 x_N' Pf x_N + qf_{k_N}' x_N,   Tx_{k_N} x_N = t_{k_N},
+// and in the loop the plant x_{t+1} = Ap_k x_t + Bp_k u_0 + cp_k + W_t (Ap, Bp absent: the model; cp absent: c; W unknown to the controller).  The
+// iteration needs no new rule (tests/mpc_qp_affine_reference.py runs the EQ reference on the dense problem with c, t, qf in its vectors):
+//   r_dyn = [A B] z_j + c_k - x_{j+1} in pass 1; the start (z = 0 but x_0), the forward sweep and the step rule are unchanged;
+//   pi_N = Pf x_N + qf + Tx' nu_T,   p_N = Pf x_N + qf + Tx' (nu_T + (1 / rho)(Tx x_N - t)),   dnu_T = (1 / rho)(Tx dx_N + Tx x_N - t);
+//   stop       max|Tx x_N - t| / max(1, max|x|): the scale of today; |c| and |t| enter no scale;
+//   plant      A_p, B_p are fetched where E_k is fetched for x <- E [x; u_0], then cp_k + W[b][si][t] is added; hres, eres, nact, nviol stay functions of
+//              the applied z_0 of the model's QP.
+// c_k, qf, t, cp, W are read from global memory where they are used (as Tx is): no LDS and no workspace of their own, the layouts are those of EQ.  A
+// non-finite entry ends the instance with status 3 at the step that meets it (c, qf, t: the stop test of that step; Ap, Bp, cp, W_t: x_{t+1} is
+// non-finite and the stop test of step t + 1 sees it); a t that cannot be reached is status 1.  With AFF = false the four instantiations are what they
+// were, statement by statement: every statement of AFF stands behind `if (AFF)` or is a value selected by it at compile time.
 #pragma once
 #include "tmpc_closed_loop.h"
 
@@ -135,6 +150,10 @@ __host__ __device__ inline long long mpc_qp_eq_ws_doubles(int nx, int mb, int nd
   return (soft ? mpc_qp_soft_ws_doubles(nx, mb, nd, N) : mpc_qp_ws_doubles(nx, mb, nd, N)) + 2LL * N * ne + nt;
 }
 
+// The arguments of the AFF instantiations, each or null: c [nb][p][nx], qf [nb][p][nx], t [nb][p][nt], Ap [nb][p][nx][nx] and Bp [nb][p][nx][mb] (both or
+// neither), cp [nb][p][nx] (null: c), W [nb][ns][T][nx].
+struct MpcQpAff { const double* c; const double* qf; const double* t; const double* Ap; const double* Bp; const double* cp; const double* W; };
+
 __device__ __forceinline__ double mq_dot(const double* __restrict__ a, const double* __restrict__ b, int len) {
   double acc = 0.0;
   for (int c = 0; c < len; ++c) acc = fma(a[c], b[c], acc);
@@ -174,8 +193,8 @@ __device__ __forceinline__ void mq_fetch(double* El, double* Hl, double* Dl, int
 // [nb][T][ns]; ws: gridDim.x slots of mpc_qp_soft_ws_doubles, LDS of mpc_qp_soft_lds.  Without SOFT the three are not read or written.
 // EQ: J [nb][p][ne][n] (null when ne = 0), req [nb][p][ne] or null (zero), necnt [nb][p] or null (all ne rows; clamped to 0 .. ne), Tx [nb][p][nt][nx] or null
 // (nt = nx: the identity), nt <= nx, and each or null Nu [nb][ns][N][ne], NuT [nb][ns][nt], eres [nb][T][ns]; ws: slots of mpc_qp_eq_ws_doubles, LDS of
-// mpc_qp_eq_lds.  Without EQ none of these is read or written.
-template <bool SOFT, bool EQ>
+// mpc_qp_eq_lds.  Without EQ none of these is read or written.  AFF: aff (MpcQpAff above); without AFF it is not read.
+template <bool SOFT, bool EQ, bool AFF>
 __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd, int lcw, int N, int ns, int T, int k0, long long ninst,
                                                    const double* __restrict__ Ag, const double* __restrict__ Bg, const double* __restrict__ Hg,
                                                    const double* __restrict__ qg, const double* __restrict__ Pfg, const double* __restrict__ Dg,
@@ -186,7 +205,8 @@ __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd
                                                    double* __restrict__ Lamg, const double* __restrict__ peng, double* __restrict__ Eolg,
                                                    int* __restrict__ nviolg, int ne, const double* __restrict__ Jg, const double* __restrict__ reqg,
                                                    const int* __restrict__ necntg, int nt, const double* __restrict__ Txg, double* __restrict__ Nug,
-                                                   double* __restrict__ NuTg, double* __restrict__ eresg) {
+                                                   double* __restrict__ NuTg, double* __restrict__ eresg, MpcQpAff aff) {
+  static_assert(EQ || !AFF, "the AFF instantiations are EQ instantiations");
   extern __shared__ __attribute__((aligned(16))) double lds[];
   const int n = nx + mb;
   const MpcQpLds Ly = mpc_qp_lds(nx, mb, nd);
@@ -226,6 +246,12 @@ __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd
     const int* necnt = EQ && necntg ? necntg + b * p : nullptr;
     const double* Tx = EQ && Txg ? Txg + b * p * nt * nx : nullptr;
     auto erows_of = [&](int k) { return ne > 0 ? (necnt ? max(0, min(ne, necnt[k])) : ne) : 0; };
+    // (AFF) the offsets of the model and of the plant, the terminal vectors, the plant's matrices (absent: the model's) and the disturbance of this instance
+    const double* cof = AFF && aff.c ? aff.c + b * p * nx : nullptr; const double* qfv = AFF && aff.qf ? aff.qf + b * p * nx : nullptr;
+    const double* trh = AFF && aff.t ? aff.t + b * p * nt : nullptr;
+    const double* Ap = AFF && aff.Ap ? aff.Ap + b * p * nx * nx : A; const double* Bp = AFF && aff.Bp ? aff.Bp + b * p * nx * mb : B;
+    const double* cpl = AFF ? (aff.cp ? aff.cp + b * p * nx : cof) : nullptr;
+    const double* Wd = AFF && aff.W ? aff.W + (b * ns + si) * T * nx : nullptr;
 
     if (tid < nx) {
       const double v = X0g[(b * ns + si) * nx + tid];
@@ -286,7 +312,8 @@ __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd
           __syncthreads();
           double a_rp = 0.0, a_dyn = 0.0, a_x = 0.0, a_rd = 0.0, a_g = 0.0, a_lam = 0.0;
           if (tid < nx) {
-            const double v = mq_dot(Pl + tid * ldp, xn, nx);
+            double v = mq_dot(Pl + tid * ldp, xn, nx);
+            if (AFF) if (qfv) v += qfv[kN * nx + tid];
             pin[tid] = v; pv[tid] = v;
             a_x = cl_absmax(a_x, xn[tid]);
           }
@@ -296,6 +323,7 @@ __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd
             if (tid < nt) {
               double acc = 0.0;
               for (int c = 0; c < nx; ++c) acc = fma(tx_at(tid, c), xn[c], acc);
+              if (AFF) if (trh) acc -= trh[kN * nt + tid];
               tv[tid] = acc;
             }
             __syncthreads();
@@ -342,7 +370,8 @@ __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd
                 a_rp = cl_absmax(a_rp, r / fmax(1.0, fabs(ddv[e]))); a_lam = cl_absmax(a_lam, lam);
               } else if (e < m + nx) {
                 const int r = e - m;
-                const double v = mq_dot(El + r * ld, zv, n) - xn[r];
+                double v = mq_dot(El + r * ld, zv, n) - xn[r];
+                if (AFF) if (cof) v = (mq_dot(El + r * ld, zv, n) + cof[k * nx + r]) - xn[r];
                 rdynv[r] = v; RDYN[(size_t)j * nx + r] = v;
                 a_dyn = cl_absmax(a_dyn, v); a_x = cl_absmax(a_x, zv[r]);
               } else {
@@ -596,7 +625,8 @@ __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd
       const bool ok = status == MQ_OK && done == t;
       if (ok) {
         const int m = rows_of(k0s);
-        mq_fetch(El, nullptr, Dl, ld, A + (size_t)k0s * nx * nx, B + (size_t)k0s * nx * mb, nullptr, D ? D + (size_t)k0s * nd * n : nullptr, nx, mb, m, tx, ty, rs);
+        mq_fetch(El, nullptr, Dl, ld, (AFF ? Ap : A) + (size_t)k0s * nx * nx, (AFF ? Bp : B) + (size_t)k0s * nx * mb, nullptr, D ? D + (size_t)k0s * nd * n : nullptr, nx, mb,
+                 m, tx, ty, rs);
         if (tid < n) zv[tid] = Z[tid];
         const int me0 = EQ ? erows_of(k0s) : 0;
         if (EQ) if (tx < n) for (int i = ty; i < me0; i += rs) Jl[i * ld + tx] = J[((size_t)k0s * ne + i) * n + tx];
@@ -630,6 +660,10 @@ __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd
         }
         double xnew = 0.0;
         if (tid < nx) xnew = mq_dot(El + tid * ld, zv, n);
+        if (AFF) if (tid < nx) {                                             // the plant's offset and the disturbance of this step
+          if (cpl) xnew += cpl[k0s * nx + tid];
+          if (Wd) xnew += Wd[(size_t)t * nx + tid];
+        }
         if (tid >= 64 && tid < 64 + mb) {
           const double u = zv[nx + tid - 64];
           if (t == 0) U0g[(b * ns + si) * mb + tid - 64] = u;

@@ -3,9 +3,10 @@ a bound (the reference's pmpc.py with h(x, u) >= 0 at every stage, as closed_loo
 
 lqr.py and closed_loop.py serve the laws of a FIXED active set.  This module solves, per (problem, initial deviation x_0) and k_j = (phase0 + j) mod p,
 
-    min  sum_{j<N} (1/2 z_j' H_k z_j + q_k' z_j) + 1/2 x_N' Pf_{k_N} x_N,   z_j = [x_j; u_j],
-    s.t. x_{j+1} = A_k x_j + B_k u_j,   D_k z_j <= d_k (first ndcnt_k rows of the stage),   j = 0 .. N-1,
-         J_k z_j = r_k (first necnt_k rows of the stage),   Tx_{k_N} x_N = 0,  k_N = (phase0 + N) mod p   (J=, r=, necnt=, terminal=),
+    min  sum_{j<N} (1/2 z_j' H_k z_j + q_k' z_j) + 1/2 x_N' Pf_{k_N} x_N + qf_{k_N}' x_N,   z_j = [x_j; u_j],
+    s.t. x_{j+1} = A_k x_j + B_k u_j + c_k,   D_k z_j <= d_k (first ndcnt_k rows of the stage),   j = 0 .. N-1,
+         J_k z_j = r_k (first necnt_k rows of the stage),   Tx_{k_N} x_N = t_{k_N},  k_N = (phase0 + N) mod p   (J=, r=, necnt=, terminal=),
+    (c, qf, t zero unless offset=, qf=, terminal_rhs= are given: the homogeneous problem in deviation coordinates),
 
 where a row may be SOFT (`penalty`, the reference's preprocessing.add_mpc_slacks: D_i z - e_i <= d_i, e_i >= 0 at the cost c_i e_i, an exact L1 penalty: the
 hard solution as long as c_i exceeds the row's multiplier, a violated row instead of an infeasible problem otherwise), the equality rows are the reference's
@@ -19,12 +20,19 @@ per instance, the whole interior-point loop and all steps of the closed loop in 
     mpc_step(A, B, Q, R, N, x0, horizon, ...)                                      one model in the reference's calling style
     mpc_closed_loop_sim(A, B, Q, R, N, x0, horizon, steps, ...)                    -> the reference's log {'x', 'u', 'l', 'h'} (and 'usc' with penalty=)
     slack_penalty(lam_h, active_set, slack_flag, factor)                           the reference's rule for the weights of the soft rows
+    about_reference(A, B, H, xref, uref, ...)                                      a deviation problem and a periodic reference -> the absolute-coordinate kwargs
+
+The affine problem (offset=, qf=, terminal_rhs=; in the loop plant=, disturbance=) is the reference's controller in ABSOLUTE coordinates -- its cost
+(w - wref)' H (w - wref) + q' w, its terminal row p_operator(x_N - x_ref) = 0, x0 the plant state --, the model x+ = A x + B u + c of a linearisation that is
+not taken on a trajectory of the model or of an estimated constant disturbance, and the loop on a plant that is not the prediction model:
+x_{t+1} = Ap_k x_t + Bp_k u_0 + cp_k + W_t.  It runs on AFF instantiations of the two kernels that serve J= and terminal= (with no rows at all when there
+are none); without any of the five arguments every call is the one it was.
 
 An equality row is a hard row without a slack: a multiplier of free sign at the constant barrier weight 1e12 (csrc/tmpc_mpc_qp.h states the rules).  An
 instance whose rows cannot be met -- horizon * nu too short to reach Tx x_N = 0, a row of stage 0 on x_0 alone that x_0 violates (the reference drops state-only
 h rows at stage 0 for the same reason) -- is infeasible and ends with status 1, like contradictory inequality rows.
 
-Not served: a terminal right-hand side != 0, quadratic slack penalties, warm starts between the steps, the nonlinear plant; there are no arguments for them.  Conventions as in lqr.py / closed_loop.py.  There is no CPU path: the solve runs in the HIP library or the call raises."""
+Not served: quadratic slack penalties, warm starts between the steps, the nonlinear plant, more than nx terminal rows; there are no arguments for them.  Conventions as in lqr.py / closed_loop.py.  There is no CPU path: the solve runs in the HIP library or the call raises."""
 import numpy as np
 
 from . import _lib
@@ -161,15 +169,50 @@ def _validate(who, A, B, H, X0, horizon, phase0, D, d, ndcnt, q, Pf, tol, max_it
     return use_torch, nd, int(horizon), T, k0
 
 
+def _validate_affine(who, use_torch, A, B, X0, T, terminal, offset, qf, terminal_rhs, plant, disturbance):
+    """The arguments of the affine problem, after _validate -> (offset, qf, terminal_rhs, Ap, Bp, cp, W), None or an array each."""
+    nb, p, nx, _ = (int(v) for v in A.shape)
+    nu, ns = int(B.shape[3]), int(X0.shape[1])
+    if plant is not None:
+        if not isinstance(plant, (tuple, list)) or len(plant) not in (2, 3):
+            raise ValueError('{}: plant must be (Ap, Bp) or (Ap, Bp, cp), got {!r}'.format(who, type(plant).__name__ if not isinstance(plant, (tuple, list)) else len(plant)))
+        if plant[0] is None or plant[1] is None:
+            raise ValueError('{}: plant (Ap, Bp[, cp]): Ap and Bp come together, neither may be None'.format(who))
+    Ap, Bp, cp = (tuple(plant) + (None,))[:3] if plant is not None else (None, None, None)
+    named = [(nm, x) for nm, x in (('offset', offset), ('qf', qf), ('terminal_rhs', terminal_rhs), ('plant[0]', Ap), ('plant[1]', Bp), ('plant[2]', cp),
+                                   ('disturbance', disturbance)) if x is not None]
+    if not named:
+        return None
+    _cl._check_kind(who, [('A', A)] + named)
+    if terminal_rhs is not None and terminal is None:
+        raise ValueError('{}: terminal_rhs describes the rows of terminal, which is None'.format(who))
+    nt = 0 if terminal is None else (nx if isinstance(terminal, str) else int(terminal.shape[2]))
+    for nm, x, shape in (('offset', offset, (nb, p, nx)), ('qf', qf, (nb, p, nx)), ('terminal_rhs', terminal_rhs, (nb, p, nt)), ('plant[0]', Ap, (nb, p, nx, nx)),
+                         ('plant[1]', Bp, (nb, p, nx, nu)), ('plant[2]', cp, (nb, p, nx)), ('disturbance', disturbance, (nb, ns, T, nx))):
+        if x is not None and tuple(x.shape) != shape:
+            raise ValueError('{}: {} {} expected, got {}'.format(who, nm, shape, tuple(x.shape)))
+    return tuple(lqr._contig(x, use_torch) for x in (offset, qf, terminal_rhs, Ap, Bp, cp, disturbance))
+
+
 def _run(who, A, B, H, X0, horizon, steps, phase0, D, d, ndcnt, q, Pf, tol, max_iter, return_traj, return_ol, penalty=None, J=None, r=None, necnt=None,
-         terminal=None):
+         terminal=None, offset=None, qf=None, terminal_rhs=None, plant=None, disturbance=None):
     use_torch, nd, N, T, k0 = _validate(who, A, B, H, X0, horizon, phase0, D, d, ndcnt, q, Pf, tol, max_iter, steps, penalty, J, r, necnt, terminal)
+    aff = _validate_affine(who, use_torch, A, B, X0, T, terminal, offset, qf, terminal_rhs, plant, disturbance)
+    if aff is not None and J is None and terminal is None:                  # the AFF kernels are EQ kernels: their layout with no rows
+        lay = lds_layout(A.shape[2], B.shape[3], nd, soft=penalty is not None, ne=0, nt=0)
+        if lay['bytes'] > LDS_BYTES:
+            raise NotImplementedError('{}: nx = {}, nu = {} with room for {} rows per stage needs {} bytes of LDS (limit {})'.format(
+                who, A.shape[2], B.shape[3], nd, lay['bytes'], LDS_BYTES))
     A, B, H, X0, D, d, q, Pf, penalty, J, r = (lqr._contig(x, use_torch) for x in (A, B, H, X0, D, d, q, Pf, penalty, J, r))
     if ndcnt is not None:
         ndcnt = ndcnt.contiguous() if use_torch else np.ascontiguousarray(ndcnt)
     if necnt is not None:
         necnt = necnt.contiguous() if use_torch else np.ascontiguousarray(necnt)
-    if J is not None or terminal is not None:
+    if aff is not None:
+        Tx = terminal if isinstance(terminal, str) or terminal is None else lqr._contig(terminal, use_torch)
+        entry = _lib.mpc_qp_aff_batch_device if use_torch else _lib.mpc_qp_aff_batch_host
+        out = entry(A, B, H, q, Pf, D, ndcnt, d, penalty, J, r, necnt, Tx, aff, X0, N, T, k0, float(tol), int(max_iter), bool(return_traj), bool(return_ol))
+    elif J is not None or terminal is not None:
         Tx = terminal if isinstance(terminal, str) or terminal is None else lqr._contig(terminal, use_torch)
         entry = _lib.mpc_qp_eq_batch_device if use_torch else _lib.mpc_qp_eq_batch_host
         out = entry(A, B, H, q, Pf, D, ndcnt, d, penalty, J, r, necnt, Tx, X0, N, T, k0, float(tol), int(max_iter), bool(return_traj), bool(return_ol))
@@ -190,8 +233,8 @@ def _run(who, A, B, H, X0, horizon, steps, phase0, D, d, ndcnt, q, Pf, tol, max_
     return out
 
 
-def mpc_qp_batch(A, B, H, X0, horizon, phase0=0, D=None, d=None, ndcnt=None, q=None, Pf=None, tol=TOL, max_iter=MAX_ITER, return_traj=True, penalty=None,
-                 J=None, r=None, necnt=None, terminal=None):
+def mpc_qp_batch(A, B, H, X0, horizon, phase0=0, D=None, d=None, ndcnt=None, q=None, Pf=None, tol=TOL, max_iter=MAX_ITER, return_traj=True, offset=None,
+                 qf=None, terminal_rhs=None, penalty=None, J=None, r=None, necnt=None, terminal=None):
     """One MPC step per (problem, initial deviation): A [nb,p,nx,nx], B [nb,p,nx,nu], H [nb,p,n,n] (used as (H + H') / 2), X0 [nb,ns,nx], fp64, n = nx + nu <= 64;
     the horizon-`horizon` QP from phase `phase0`.  Optional: the rows D [nb,p,nd,n], d [nb,p,nd] (D z <= d; ndcnt int32 [nb,p]: only the first ndcnt rows of a
     stage, None: all nd), q [nb,p,n] (linear cost), Pf [nb,p,nx,nx] (terminal weight 1/2 x_N' Pf[(phase0 + N) mod p] x_N); None: absent / zero.  Without rows
@@ -204,6 +247,13 @@ def mpc_qp_batch(A, B, H, X0, horizon, phase0=0, D=None, d=None, ndcnt=None, q=N
     nu_term [nb,ns,nt] (the multipliers, free sign; None with return_traj=False) and eres [nb,ns] = max|J z_0 - r| (0 at a stage without rows).  Rows that
     cannot be met (horizon * nu too short to reach the terminal rows, a row of stage 0 on x_0 alone that x_0 violates) make the instance infeasible: status 1.
     Without them (J=None, terminal=None) the call is the one it was, bit for bit.
+    offset [nb,p,nx]: the dynamics are x_{j+1} = A_k x_j + B_k u_j + offset_k (indexed by the phase like A); qf [nb,p,nx]: the terminal cost gains
+    qf[(phase0 + N) mod p]' x_N (legal without Pf); terminal_rhs [nb,p,nt] ([nb,p,nx] with terminal='constraint': x_N = t): the terminal rows read
+    Tx x_N = terminal_rhs[(phase0 + N) mod p]; it needs terminal=.  With any of the three the dict also holds nu, nu_term (empty without rows) and eres, x1
+    is A x_0 + B u_0 + offset, a non-finite entry that the step meets makes the instance status 3 and a terminal_rhs that cannot be reached status 1.
+    Without them the call is the one it was, bit for bit.  about_reference builds the three from a periodic reference.  In the signatures of the four calls the
+    three (and plant, disturbance) stand between return_traj / max_iter and penalty: what comes before them is where it was, and penalty, J, r, necnt, terminal
+    stay the last parameters, so every argument from penalty on is to be passed by keyword.
 
     numpy arrays run through the host entry; torch tensors on a GPU through the device entry (torch tensors out, the inputs are not copied).  Both run the same
     kernel and agree bit for bit; the numbers of an instance do not depend on ns or on the other instances of the call.
@@ -213,20 +263,21 @@ def mpc_qp_batch(A, B, H, X0, horizon, phase0=0, D=None, d=None, ndcnt=None, q=N
     (0 converged, 1 max_iter reached -- an infeasible instance ends here --, 2 a stage matrix not positive definite: not convex along the path, 3 non-finite), steps,
     iters_total, iters_max [nb,ns] int32, mu, rp, rd, pivmin [nb,ns], info [nb,ns,8].  An instance with status != 0 returns NaN (nact -1); the others are not
     affected.  ValueError: shapes, dtypes, mixed numpy / torch, horizon < 1, phase0 outside 0 .. p-1, D without d, ndcnt outside 0 .. nd, tol <= 0,
-    max_iter < 1, penalty without D or with an entry <= 0 or NaN, r or necnt without J, a terminal that is neither None, 'constraint' nor an array;
-    NotImplementedError: n > 64, (nx, nu, nd) beyond the 160 KB LDS layout (lds_layout; with a penalty the soft layout, with J or terminal lds_layout(ne=))."""
-    o = _run('mpc_qp_batch', A, B, H, X0, horizon, 1, phase0, D, d, ndcnt, q, Pf, tol, max_iter, False, return_traj, penalty, J, r, necnt, terminal)
+    max_iter < 1, penalty without D or with an entry <= 0 or NaN, r or necnt without J, a terminal that is neither None, 'constraint' nor an array,
+    terminal_rhs without terminal; NotImplementedError: n > 64, (nx, nu, nd) beyond the 160 KB LDS layout (lds_layout; with a penalty the soft layout, with J or terminal lds_layout(ne=))."""
+    o = _run('mpc_qp_batch', A, B, H, X0, horizon, 1, phase0, D, d, ndcnt, q, Pf, tol, max_iter, False, return_traj, penalty, J, r, necnt, terminal, offset, qf,
+             terminal_rhs)
     out = dict(u0=o['U0'], X=o['Xol'], U=o['Uol'], lam=o['Lam'], nact=o['nact'][..., 0], hres=o['hres'][..., 0], x1=o['XT'], info=o['info'])
     if penalty is not None:
         out.update(eps=o['Eol'], nviol=o['nviol'][..., 0])
-    if J is not None or terminal is not None:
+    if 'eres' in o:
         out.update(nu=o['Nu'], nu_term=o['NuT'], eres=o['eres'][..., 0])
     out.update({k: o[k] for k in INFO_FIELDS})
     return out
 
 
 def mpc_closed_loop_batch(A, B, H, X0, horizon, steps, phase0=0, D=None, d=None, ndcnt=None, q=None, Pf=None, tol=TOL, max_iter=MAX_ITER, return_traj=True,
-                          penalty=None, J=None, r=None, necnt=None, terminal=None):
+                          offset=None, qf=None, terminal_rhs=None, plant=None, disturbance=None, penalty=None, J=None, r=None, necnt=None, terminal=None):
     """The receding-horizon loop: at t = 0 .. steps-1 the QP of mpc_qp_batch from phase (phase0 + t) mod p, cold-started, u_0 applied, x <- A_k x + B_k u_0 (the
     linear plant, as closed_loop_batch does), all steps in one launch.  Arguments as mpc_qp_batch.
 
@@ -235,12 +286,18 @@ def mpc_closed_loop_batch(A, B, H, X0, horizon, steps, phase0=0, D=None, d=None,
     keeps what it logged before: U, hres from t on, X from t + 1 on and XT are NaN, nact from t on and iters beyond t are -1.  X, U and the per-step logs are
     permuted views of time-major arrays.  With penalty (as in mpc_qp_batch) the dict gains nviol [nb,ns,steps] int32 (-1 from a failed step on); hres > 0
     at a step whose applied stage violates a soft row.  With J or terminal (as in mpc_qp_batch) the dict gains eres [nb,ns,steps] = max|J z_0 - r| of the
-    applied stage (NaN from a failed step on)."""
-    o = _run('mpc_closed_loop_batch', A, B, H, X0, horizon, steps, phase0, D, d, ndcnt, q, Pf, tol, max_iter, return_traj, False, penalty, J, r, necnt, terminal)
+    applied stage (NaN from a failed step on).
+    offset, qf, terminal_rhs as in mpc_qp_batch.  plant = (Ap, Bp) or (Ap, Bp, cp) with the shapes of A, B, offset: the plant step is
+    x_{t+1} = Ap_k x_t + Bp_k u_0 + cp_k + W_t, k = (phase0 + t) mod p (default: the model; a cp left out is the model's offset); disturbance W
+    [nb,ns,steps,nx], which the controller does not know about.  hres, eres, nact, nviol stay figures of the applied stage of the model's QP.  A non-finite
+    W_t (or plant entry) makes x_{t+1} non-finite: the instance ends with status 3 at step t + 1, X[t + 1] holds that state.  With any of the five the dict
+    also holds eres.  ValueError: shapes, mixed numpy / torch, terminal_rhs without terminal, a plant that is not a tuple of 2 or 3."""
+    o = _run('mpc_closed_loop_batch', A, B, H, X0, horizon, steps, phase0, D, d, ndcnt, q, Pf, tol, max_iter, return_traj, False, penalty, J, r, necnt, terminal,
+             offset, qf, terminal_rhs, plant, disturbance)
     out = dict(X=o['X'], U=o['U'], iters=o['iters'], nact=o['nact'], hres=o['hres'], XT=o['XT'], u0=o['U0'], info=o['info'])
     if penalty is not None:
         out['nviol'] = o['nviol']
-    if J is not None or terminal is not None:
+    if 'eres' in o:
         out['eres'] = o['eres']
     out.update({k: o[k] for k in INFO_FIELDS})
     return out
@@ -277,6 +334,44 @@ def _stack_eq(who, p, nx, n, J, r, terminal):
         if len(Tl) != p or any(m.shape != Tl[0].shape or m.shape[1] != nx for m in Tl):
             raise ValueError('{}: terminal must be \'constraint\', one matrix [nt, nx = {}] or a list of p = {} of them'.format(who, nx, p))
         out['terminal'] = np.ascontiguousarray(np.stack(Tl)[None])
+    return out
+
+
+def _stack_affine(who, p, nx, nu, terminal, offset, qf, terminal_rhs, plant=None, disturbance=None, steps=None):
+    """offset, qf, terminal_rhs (single vectors or lists of p), plant ((Ap, Bp[, cp]), each a single array or a list of p), disturbance [steps, nx] -> the
+    keyword arguments of the batch calls for one problem and one state (only those that are given)."""
+    out = {}
+
+    def vecs(name, v, m):
+        vl = [_to_array(x).astype(np.float64).reshape(-1) for x in (v if isinstance(v, (list, tuple)) else [v] * p)]
+        if len(vl) != p or any(x.shape != (m,) for x in vl):
+            raise ValueError('{}: {} must be one vector of {} entries or a list of p = {} of them'.format(who, name, m, p))
+        return np.ascontiguousarray(np.stack(vl)[None])
+
+    def mats(name, v, rows, cols):
+        ml = [np.atleast_2d(_to_array(x)).astype(np.float64) for x in (v if isinstance(v, (list, tuple)) else [v] * p)]
+        if len(ml) != p or any(x.shape != (rows, cols) for x in ml):
+            raise ValueError('{}: {} must be one matrix [{}, {}] or a list of p = {} of them'.format(who, name, rows, cols, p))
+        return np.ascontiguousarray(np.stack(ml)[None])
+    if offset is not None:
+        out['offset'] = vecs('offset', offset, nx)
+    if qf is not None:
+        out['qf'] = vecs('qf', qf, nx)
+    if terminal_rhs is not None:
+        if terminal is None:
+            raise ValueError('{}: terminal_rhs describes the rows of terminal, which is None'.format(who))
+        nt = nx if isinstance(terminal, str) else int(terminal.shape[2])
+        out['terminal_rhs'] = vecs('terminal_rhs', terminal_rhs, nt)
+    if plant is not None:
+        if not isinstance(plant, tuple) or len(plant) not in (2, 3):
+            raise ValueError('{}: plant must be a tuple (Ap, Bp) or (Ap, Bp, cp), got {!r}'.format(who, type(plant).__name__ if not isinstance(plant, tuple) else len(plant)))
+        pl = (mats('plant[0]', plant[0], nx, nx), mats('plant[1]', plant[1], nx, nu))
+        out['plant'] = pl + ((vecs('plant[2]', plant[2], nx),) if len(plant) == 3 and plant[2] is not None else ())
+    if disturbance is not None:
+        W = np.atleast_2d(_to_array(disturbance)).astype(np.float64)
+        if W.shape != (int(steps), nx):
+            raise ValueError('{}: disturbance [steps, nx] = [{}, {}] expected, got {}'.format(who, int(steps), nx, W.shape))
+        out['disturbance'] = np.ascontiguousarray(W[None, None])
     return out
 
 
@@ -335,16 +430,19 @@ def _stack_one(who, A, B, Q, R, N, x0, D, d, q, Pf, penalty=None):
     return As, Bs, Hs, np.ascontiguousarray(x[None, None]), dict(D=Ds, d=ds, ndcnt=cnt, q=qs, Pf=Pfs, penalty=pens)
 
 
-def mpc_step(A, B, Q, R, N, x0, horizon, phase0=0, D=None, d=None, q=None, Pf=None, tol=TOL, max_iter=MAX_ITER, penalty=None, J=None, r=None, terminal=None):
+def mpc_step(A, B, Q, R, N, x0, horizon, phase0=0, D=None, d=None, q=None, Pf=None, tol=TOL, max_iter=MAX_ITER, offset=None, qf=None, terminal_rhs=None, penalty=None,
+             J=None, r=None, terminal=None):
     """One MPC step of one model in the reference's calling style: A, B, Q, R, N (the cross term) single matrices (p = 1) or lists of length p as in horizon_lqr,
     D, d the rows D_k [x; u] <= d_k (single arrays or lists of p; None entries: no rows at that stage), q, Pf likewise.  Returns (u0, X [horizon+1,nx],
     U [horizon,nu], lam [horizon,nd], info dict).  penalty: the weights of the soft rows, one vector (every stage) or a list of p vectors, one entry per row of
     D_k; np.inf entries and None stages are hard.  With it info gains 'eps' [horizon,nd] (the slacks) and 'nviol'.  J, r: the equality rows J_k [x; u] = r_k
     (single arrays or lists of p, None entries: no rows at that stage; r None: zero); terminal: 'constraint' (x_N = 0), one matrix Tx [nt,nx] or a list of p
-    (Tx x_N = 0).  With them info gains 'nu' [horizon,ne], 'nu_term' [nt] and 'eres'.  RuntimeError when the solve did not converge (an infeasible problem)."""
+    (Tx x_N = 0).  With them info gains 'nu' [horizon,ne], 'nu_term' [nt] and 'eres'.  offset, qf, terminal_rhs: the vectors of the affine problem
+    (mpc_qp_batch), one vector each or a list of p.  RuntimeError when the solve did not converge (an infeasible problem)."""
     who = 'mpc_step'
     As, Bs, Hs, X0, kw = _stack_one(who, A, B, Q, R, N, x0, D, d, q, Pf, penalty)
     kw.update(_stack_eq(who, As.shape[1], As.shape[2], As.shape[2] + Bs.shape[3], J, r, terminal))
+    kw.update(_stack_affine(who, As.shape[1], As.shape[2], Bs.shape[3], kw['terminal'], offset, qf, terminal_rhs))
     res = mpc_qp_batch(As, Bs, Hs, X0, horizon, phase0, tol=tol, max_iter=max_iter, **kw)
     st = int(res['status'][0, 0])
     if st != 0:
@@ -352,16 +450,19 @@ def mpc_step(A, B, Q, R, N, x0, horizon, phase0=0, D=None, d=None, q=None, Pf=No
     return res['u0'][0, 0], res['X'][0, 0], res['U'][0, 0], res['lam'][0, 0], {k: res[k][0, 0] for k in INFO_FIELDS + ('nact', 'hres') + (('eps', 'nviol') if 'eps' in res else ()) + (('nu', 'nu_term', 'eres') if 'nu' in res else ())}
 
 
-def mpc_closed_loop_sim(A, B, Q, R, N, x0, horizon, steps, phase0=0, D=None, d=None, q=None, Pf=None, tol=TOL, max_iter=MAX_ITER, penalty=None, J=None,
-                        r=None, terminal=None):
+def mpc_closed_loop_sim(A, B, Q, R, N, x0, horizon, steps, phase0=0, D=None, d=None, q=None, Pf=None, tol=TOL, max_iter=MAX_ITER, offset=None, qf=None,
+                        terminal_rhs=None, plant=None, disturbance=None, penalty=None, J=None, r=None, terminal=None):
     """The reference's closed_loop_sim with the inequality-constrained tracking MPC in the loop and the linear plant, one model in the calling style of mpc_step.
     Returns the reference's log: {'x': steps + 1 states, 'u': steps inputs, 'l': steps stage costs 1/2 z' H_k z + q_k' z, 'h': steps arrays d_k - D_k [x_t; u_t]
     (>= 0 when the rows hold; empty at a stage without rows)} and 'iters', 'nact'.  With penalty (as in mpc_step) 'h' stays d - D z (negative on a violated soft
     row), 'usc' holds the slack of the applied step, max(0, D z - d) on the soft rows and 0 on the hard ones (the reference's usc), and 'nviol' the count of the
-    solver.  With J, r, terminal (as in mpc_step) the log gains 'eres': max|J_k [x_t; u_t] - r_k| of every step.  RuntimeError when a step did not converge."""
+    solver.  With J, r, terminal (as in mpc_step) the log gains 'eres': max|J_k [x_t; u_t] - r_k| of every step.  offset, qf, terminal_rhs as in mpc_step; plant = (Ap, Bp) or (Ap, Bp, cp), each a single
+    array or a list of p, and disturbance [steps, nx]: the plant of the loop, x_{t+1} = Ap_k x_t + Bp_k u_t + cp_k + W_t (mpc_closed_loop_batch).
+    RuntimeError when a step did not converge."""
     who = 'mpc_closed_loop_sim'
     As, Bs, Hs, X0, kw = _stack_one(who, A, B, Q, R, N, x0, D, d, q, Pf, penalty)
     kw.update(_stack_eq(who, As.shape[1], As.shape[2], As.shape[2] + Bs.shape[3], J, r, terminal))
+    kw.update(_stack_affine(who, As.shape[1], As.shape[2], Bs.shape[3], kw['terminal'], offset, qf, terminal_rhs, plant, disturbance, steps))
     res = mpc_closed_loop_batch(As, Bs, Hs, X0, horizon, steps, phase0, tol=tol, max_iter=max_iter, **kw)
     st = int(res['status'][0, 0])
     if st != 0:
@@ -384,6 +485,63 @@ def mpc_closed_loop_sim(A, B, Q, R, N, x0, horizon, steps, phase0=0, D=None, d=N
     if 'eres' in res:
         log['eres'] = [float(v) for v in res['eres'][0, 0]]
     return log
+
+
+def about_reference(A, B, H, xref, uref, q=None, Pf=None, D=None, d=None, J=None, r=None, terminal=None):
+    """A problem in DEVIATION coordinates (the arguments of mpc_qp_batch: A [nb,p,nx,nx], B [nb,p,nx,nu], H [nb,p,n,n], q [nb,p,n], Pf [nb,p,nx,nx], D, d, J, r,
+    terminal as there) and a p-periodic reference xref [nb,p,nx], uref [nb,p,nu] -> the keyword arguments of the same problem in ABSOLUTE coordinates
+    w = dw + wref, wref_k = [xref_k; uref_k], H used as (H + H') / 2, likewise Pf:
+        offset_k = xref_{(k+1) % p} - A_k xref_k - B_k uref_k       (zero when the reference is a trajectory of the model),
+        q_k - H_k wref_k,   d_k + D_k wref_k,   r_k + J_k wref_k,   qf_k = -Pf_k xref_k,   terminal_rhs_k = Tx_k xref_k  (xref_k for terminal='constraint').
+    Returns a dict with offset, q, and, where the argument is given, Pf, qf, D, d, J, r, terminal, terminal_rhs: pass it as **kwargs next to A, B, H and the
+    ABSOLUTE X0 (and ndcnt, necnt, penalty, which do not change).  The solution is the deviation solution plus the reference with the same multipliers; the
+    cost differs by a constant.  Host-side numpy or torch (all arguments of one kind), no kernel."""
+    who = 'about_reference'
+    Tx = terminal if hasattr(terminal, 'shape') else None
+    if terminal is not None and Tx is None and not (isinstance(terminal, str) and terminal == 'constraint'):
+        raise ValueError("{}: terminal must be None, 'constraint' or an array [nb, p, nt, nx], got {!r}".format(who, terminal))
+    named = [('A', A), ('B', B), ('H', H), ('xref', xref), ('uref', uref)] + [(nm, x) for nm, x in (('q', q), ('Pf', Pf), ('D', D), ('d', d), ('J', J), ('r', r),
+                                                                                                      ('terminal', Tx)) if x is not None]
+    use_torch = [lqr._is_torch(x) for _, x in named]
+    if any(use_torch) != all(use_torch) or not all(hasattr(x, 'shape') for _, x in named):
+        raise ValueError('{}: all arguments numpy arrays or all torch tensors expected'.format(who))
+    if len(A.shape) != 4 or A.shape[2] != A.shape[3] or len(B.shape) != 4 or tuple(B.shape[:3]) != tuple(A.shape[:3]):
+        raise ValueError('{}: A [nb, p, nx, nx], B [nb, p, nx, nu] expected, got {}, {}'.format(who, tuple(A.shape), tuple(B.shape)))
+    nb, p, nx, _ = (int(v) for v in A.shape)
+    nu = int(B.shape[3])
+    n = nx + nu
+    if (D is None) != (d is None):
+        raise ValueError('{}: D and d come together (the rows D z <= d)'.format(who))
+    if J is None and r is not None:
+        raise ValueError('{}: r describes the rows of J, which is None'.format(who))
+    for nm, x, shape in (('H', H, (nb, p, n, n)), ('xref', xref, (nb, p, nx)), ('uref', uref, (nb, p, nu)), ('q', q, (nb, p, n)), ('Pf', Pf, (nb, p, nx, nx)),
+                         ('D', D, (nb, p, None, n)), ('J', J, (nb, p, None, n)), ('terminal', Tx, (nb, p, None, nx))):
+        if x is not None and (len(x.shape) != len(shape) or any(b is not None and int(a) != b for a, b in zip(x.shape, shape))):
+            raise ValueError('{}: {} {} expected, got {}'.format(who, nm, tuple('any' if v is None else v for v in shape), tuple(x.shape)))
+    if D is not None and tuple(d.shape) != tuple(D.shape[:3]):
+        raise ValueError('{}: d {} expected, got {}'.format(who, tuple(D.shape[:3]), tuple(d.shape)))
+    if r is not None and tuple(r.shape) != tuple(J.shape[:3]):
+        raise ValueError('{}: r {} expected, got {}'.format(who, tuple(J.shape[:3]), tuple(r.shape)))
+    if use_torch[0]:
+        import torch
+        cat, roll = (lambda a, b: torch.cat([a, b], dim=-1)), (lambda x: torch.roll(x, -1, dims=1))
+    else:
+        cat, roll = (lambda a, b: np.concatenate([a, b], axis=-1)), (lambda x: np.roll(x, -1, axis=1))
+    mv = lambda M, v: (M @ v[..., None])[..., 0]
+    tr = lambda M: M.transpose(-1, -2) if use_torch[0] else np.swapaxes(M, -1, -2)
+    w = cat(xref, uref)
+    out = dict(offset=roll(xref) - mv(A, xref) - mv(B, uref))
+    Hw = 0.5 * (mv(H, w) + mv(tr(H), w))
+    out['q'] = -Hw if q is None else q - Hw
+    if Pf is not None:
+        out.update(Pf=Pf, qf=-0.5 * (mv(Pf, xref) + mv(tr(Pf), xref)))
+    if D is not None:
+        out.update(D=D, d=d + mv(D, w))
+    if J is not None:
+        out.update(J=J, r=mv(J, w) if r is None else r + mv(J, w))
+    if terminal is not None:
+        out.update(terminal=terminal, terminal_rhs=xref + 0.0 if Tx is None else mv(Tx, xref))
+    return out
 
 
 def slack_penalty(lam_h, active_set=None, slack_flag='active', factor=1e3):
