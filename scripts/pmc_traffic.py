@@ -35,8 +35,8 @@ def sources_sha():
 def main():
     kernels = sys.argv[3:] if len(sys.argv) > 3 else ['k_cr_trsm_dma(', 'k_cr_update_dma(', 'k_cr_update_dma_f32(']
     out = {
-        "source": "rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE TCC_HIT_sum TCC_MISS_sum (separate passes) on "
-                  "`python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-extra`; per-kernel summary in profiles/r6_final_pmc.txt",
+        "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE TCC_HIT_sum TCC_MISS_sum (separate passes, counters only) on "
+                  "`python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-extra`; per-kernel summary in profiles/r8_final_pmc.txt",
         "fetch_correction": "x2: gfx950 FETCH_SIZE counts 128-byte requests as 64 B (MI355X_MICROARCH.md, HBM section)",
         "sources_sha": sources_sha(),
         "note": "average over all launches of a kernel (7 levels per factorisation phase, shrinking active sets)",

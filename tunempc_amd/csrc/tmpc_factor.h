@@ -41,12 +41,6 @@ typedef const double2_t __attribute__((address_space(1)))* gcptr2;
     const double2_t u1_ = (ok) ? ((gcptr2)(p))[1] : (double2_t){0.0, 0.0};              \
     dst[(off) + 0] = u0_[0]; dst[(off) + 1] = u0_[1]; dst[(off) + 2] = u1_[0]; dst[(off) + 3] = u1_[1]; \
   }
-// the same piece of a float32 matrix (one 16-byte load), widened to double
-#define TMPC_LD4F(dst, off, p, ok)                                                      \
-  {                                                                                     \
-    const float4_t u_ = (ok) ? *(const float4_t __attribute__((address_space(1)))*)(p) : (float4_t){0.f, 0.f, 0.f, 0.f}; \
-    dst[(off) + 0] = (double)u_[0]; dst[(off) + 1] = (double)u_[1]; dst[(off) + 2] = (double)u_[2]; dst[(off) + 3] = (double)u_[3]; \
-  }
 typedef double __attribute__((address_space(1)))* gptr;
 // WM x WN waves per workgroup (blockDim.x = 64 WM WN), FA fragments of 16 rows per wave: a wave owns (16 FA) x 32 of C, the
 // workgroup tile is TM x TN = (16 FA WM) x (32 WN).  Two shapes are used: <2,2,2> = 64 x 64 with 256 threads (two workgroups per
@@ -534,14 +528,108 @@ __device__ __forceinline__ int wg_block_column(double* Dk, double* R1, double* R
 constexpr int NCP = 4;      // rows of the LDS vectors (>= max NC = 3)
 constexpr int GKV = 16, GLDV = GKV + 1;   // K slab of the skinny GEMM
 
+// The same product with a float32 copy of M (the O blocks of an iteration whose updates run in single precision, tmpc_cr.h).  The copy halves the bytes of the
+// blocks it covers, but streamed through the fp64 geometry (64 x 16 slabs, one 16-byte load per thread and step: 4 KB between two barriers, 16 KB in flight per
+// workgroup) those bytes moved at 3.2 TB/s (transposed) / 4.2 TB/s against the fp64 form's 6.0 and bought 8 ms of the 116 ms the same blocks take in fp64
+// (profiles/r8_subst_f32_before.txt); in the form below they move at 5.2 / 5.5 TB/s (profiles/r8_subst_f32_after.txt, NOTEBOOK.md section 13).  Here the K slab
+// is GKF = 32 deep: a thread loads 8 floats per step (non-transposed: 32 contiguous bytes of a row, a quarter-wave = one 128-byte line; transposed: 4 consecutive i of the k
+// rows lrow and 16 + lrow), four sets of 8 floats are in flight (8 KB per step, 32 KB per workgroup, as in the fp64 form), the slab is staged in LDS as float
+// (64 x GLDF floats inside the 64 x GLDV doubles of As) and widened on the fragment read.  The 8 MFMAs of a step run on one accumulator with k ascending -- the order of
+// two steps of the 16-deep form, and the widening is exact: the results are those of the 16-deep form bit for bit.
+// cols is a multiple of 16: the last step may be a half slab.  Only its four MFMAs run (X ends at cols), and in the transposed form the k rows >= cols are not fetched
+// (they are the next block's).  Non-transposed, the row stride ldm covers the whole last slab (ldm >= cols rounded up to GKF); what stands there is not used.
+constexpr int GKF = 32, GLDF = GKF + 1;
+static_assert(64 * GLDF * sizeof(float) <= 64 * GLDV * sizeof(double), "the float32 slab lives in the As region of the fp64 form");
+template <bool TRANS>
+__device__ __forceinline__ void wg_gemv32f(double* Y, int yld, const double* X, int xld, const float* M, int ldm,
+                                           int rows, int cols, bool accumulate, double sgn, double* As, int nc) {
+  float* Af = (float*)As;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int fr = lane & 15, fk = lane >> 4;
+  const int nks = (cols + GKF - 1) / GKF;
+  // The loads go through a raw buffer resource that ends with the matrix (TRANS: after the part of k row cols - 1 that is read; else after row rows - 1): the whole
+  // byte offset is the per-thread VGPR offset, which the hardware checks against that end, so rows beyond the matrix read as zeros without predicates or 64-bit addresses.
+  const unsigned mbytes = TRANS ? ((unsigned)(cols - 1) * (unsigned)ldm + (unsigned)rows) * 4u : (unsigned)rows * (unsigned)ldm * 4u;
+  const __amdgpu_buffer_rsrc_t mrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)M, 0, (int)mbytes, 0x00020000);
+  const unsigned kstep = (TRANS ? (unsigned)GKF * (unsigned)ldm : (unsigned)GKF) * 4u;   // bytes from slab to slab
+  const unsigned piece = (TRANS ? 16u * (unsigned)ldm : 4u) * 4u;                         // ... and from a thread's first piece to its second
+  typedef unsigned int u4_t __attribute__((ext_vector_type(4)));
+  for (int m0 = 0; m0 < rows; m0 += 64) {
+    double4_t acc = (double4_t){0.0, 0.0, 0.0, 0.0};
+    // slab loader: two 16-byte pieces per thread and step
+    const int lrow = TRANS ? (tid >> 4) : (tid >> 2);            // TRANS: k index (0..15, and 16 + that) ; else row (0..63)
+    const int lcol = TRANS ? ((tid & 15) * 4) : ((tid & 3) * 8); // TRANS: first i ; else first k
+    // (TRANS: the columns i >= rows of a k row inside the matrix lie inside the resource: such a thread's offset starts far behind every matrix)
+    const unsigned vo = TRANS ? ((m0 + lcol < rows) ? ((unsigned)lrow * (unsigned)ldm + (unsigned)(m0 + lcol)) * 4u : 0x40000000u)
+                              : ((unsigned)(m0 + lrow) * (unsigned)ldm + (unsigned)lcol) * 4u;
+    float ra[8], rb[8], rc[8], rd[8];
+#define TMPC_GEMV_LD(RG, KS)                                                                                      \
+    {                                                                                                             \
+      const unsigned o_ = vo + (unsigned)(KS) * kstep;                                                            \
+      const float4_t u0_ = __builtin_bit_cast(float4_t, __builtin_amdgcn_raw_buffer_load_b128(mrsrc, (int)o_, 0, 0));           \
+      const float4_t u1_ = __builtin_bit_cast(float4_t, __builtin_amdgcn_raw_buffer_load_b128(mrsrc, (int)(o_ + piece), 0, 0)); \
+      _Pragma("unroll") for (int q = 0; q < 4; ++q) { RG[q] = u0_[q]; RG[4 + q] = u1_[q]; }                     \
+    }
+    TMPC_GEMV_LD(ra, 0)
+    if (nks > 1) TMPC_GEMV_LD(rb, 1)
+    if (nks > 2) TMPC_GEMV_LD(rc, 2)
+    if (nks > 3) TMPC_GEMV_LD(rd, 3)
+#define TMPC_GEMV_MFMA4(KK0)                                                                                      \
+        _Pragma("unroll") for (int kk = (KK0); kk < (KK0) + 4; ++kk) {                                           \
+          const double a = (double)Af[(16 * wv + fr) * GLDF + kk * 4 + fk];                                       \
+          const double bq = X[(fr & (NCP - 1)) * xld + k0 + kk * 4 + fk];                                         \
+          acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, bq, acc, 0, 0, 0);                                        \
+        }
+#define TMPC_GEMV_SLAB(RG, KS)                                                                                  \
+    {                                                                                                             \
+      __syncthreads();                                                                                            \
+      if (TRANS) {                                                                                                \
+        _Pragma("unroll") for (int q = 0; q < 4; ++q) { Af[(lcol + q) * GLDF + lrow] = RG[q]; Af[(lcol + q) * GLDF + 16 + lrow] = RG[4 + q]; } \
+      } else {                                                                                                    \
+        _Pragma("unroll") for (int q = 0; q < 8; ++q) Af[lrow * GLDF + lcol + q] = RG[q];                       \
+      }                                                                                                           \
+      __syncthreads();                                                                                            \
+      if ((KS) + 4 < nks) TMPC_GEMV_LD(RG, (KS) + 4)                                                              \
+      if (m0 + 16 * wv < rows) {                                                                                  \
+        const int k0 = (KS) * GKF;                                                                                \
+        TMPC_GEMV_MFMA4(0)                                                                                        \
+        if (k0 + 16 < cols) { TMPC_GEMV_MFMA4(4) }                                                                \
+      }                                                                                                           \
+    }
+    for (int ks = 0; ks < nks; ks += 4) {
+      TMPC_GEMV_SLAB(ra, ks)
+      if (ks + 1 < nks) TMPC_GEMV_SLAB(rb, ks + 1)
+      if (ks + 2 < nks) TMPC_GEMV_SLAB(rc, ks + 2)
+      if (ks + 3 < nks) TMPC_GEMV_SLAB(rd, ks + 3)
+    }
+#undef TMPC_GEMV_SLAB
+#undef TMPC_GEMV_MFMA4
+#undef TMPC_GEMV_LD
+    if (m0 + 16 * wv < rows && fr < nc) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int i = m0 + 16 * wv + fk + 4 * r;
+        if (i < rows) {
+          double* yp = Y + fr * yld + i;
+          *yp = (accumulate ? *yp : 0.0) + sgn * acc[r];
+        }
+      }
+    }
+  }
+  __syncthreads();
+}
+
 // LOWER: M is a lower-triangular tile (an inverted diagonal tile): the 4-element pieces above the diagonal are zeros in memory and are
 // not fetched (3/8 of the tile: the substitutions are bound by the bytes they stream)
-// MT = float: M is a float32 copy of the matrix (the O blocks of an iteration whose updates run in single precision, tmpc_cr.h: half the bytes of a sweep that is
-// bound by them); its entries are widened on the way into LDS, products and sums stay fp64.
+// MT = float: M is a float32 copy of the matrix: wg_gemv32f above (products and sums stay fp64).
 template <bool TRANS, bool LOWER = false, typename MT = double>
 __device__ __forceinline__ void wg_gemv16(double* Y, int yld, const double* X, int xld, const MT* M, int ldm,
                                           int rows, int cols, bool accumulate, double sgn, double* As, int nc) {
-  constexpr bool F32 = sizeof(MT) == 4;
+  if constexpr (sizeof(MT) == 4) {
+    static_assert(!LOWER, "the float32 form has no triangular variant");
+    wg_gemv32f<TRANS>(Y, yld, X, xld, M, ldm, rows, cols, accumulate, sgn, As, nc);
+    return;
+  }
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int fr = lane & 15, fk = lane >> 4;
   const int nks = cols / GKV;
@@ -558,7 +646,7 @@ __device__ __forceinline__ void wg_gemv16(double* Y, int yld, const double* X, i
     // bytes in flight (512 workgroups x 8 KB with a single prefetch: 4.4 TB/s; two in flight: 5.2)
     double rb[4], rc[4], rd[4];
 #define TMPC_GEMV_OK(KS) (ok && (!LOWER || (TRANS ? (m0 + lcol <= GKV * (KS) + lrow) : (GKV * (KS) + lcol <= m0 + lrow))))
-#define TMPC_GEMV_LD(RG, P, OK) { if (F32) TMPC_LD4F(RG, 0, P, OK) else TMPC_LD4(RG, 0, P, OK) }
+#define TMPC_GEMV_LD(RG, P, OK) TMPC_LD4(RG, 0, P, OK)
     TMPC_GEMV_LD(ra, src, TMPC_GEMV_OK(0))
     if (nks > 1) { const MT* s1 = src + kstep; TMPC_GEMV_LD(rb, s1, TMPC_GEMV_OK(1)) }
     if (nks > 2) { const MT* s1 = src + 2 * kstep; TMPC_GEMV_LD(rc, s1, TMPC_GEMV_OK(2)) }
