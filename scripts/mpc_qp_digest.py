@@ -1,7 +1,11 @@
 """sha256 of the raw outputs (u0, X, U, lam, info) of the fixed cases of tests/mpc_qp_reference.py through mpc_qp_batch and mpc_closed_loop_batch WITHOUT penalty,
 host and device entry, for comparing two builds of the library bit for bit -- the hard path of csrc/tmpc_mpc_qp.h must not move when the kernel grows:
 
-    python scripts/mpc_qp_digest.py [--tree path/to/another/checkout]      (the package and its built library are taken from that tree; the cases from this one)
+    python scripts/mpc_qp_digest.py [--all] [--tree path/to/another/checkout]      (the package and its built library are taken from that tree; the cases from this one)
+
+--all adds the fixed cases of tests/mpc_qp_soft_reference.py (every variant, with its penalty), tests/mpc_qp_eq_reference.py (with J, r, necnt, terminal, penalty)
+and tests/mpc_qp_affine_reference.py (with offset, qf, terminal_rhs, and the loop with a plant and a disturbance), EVERY key of the returned dicts hashed: the
+soft, eq and aff entries next to the hard ones, for a change of the host code around the kernel.
 """
 import argparse
 import hashlib
@@ -14,6 +18,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ap = argparse.ArgumentParser()
 ap.add_argument('--tree', default=ROOT)
+ap.add_argument('--all', action='store_true')
 args = ap.parse_args()
 sys.path.insert(0, os.path.abspath(args.tree))
 sys.path.insert(1, os.path.join(ROOT, 'tests'))
@@ -49,4 +54,35 @@ for case in mq.CASES + [lambda: mq.case_mixed_small(2)]:
         line.append(dig(mpc_qp.mpc_closed_loop_batch(*a, T, c['k0'], **kw), ('u0', 'X', 'U', 'iters', 'nact', 'hres', 'info')))
     total.update(' '.join(line).encode())
     print('%-24s N %d  step host %s  loop host %s  step device %s  loop device %s' % (getattr(case, '__name__', 'case_mixed_small_N2'), c['N'], *line), flush=True)
+
+
+def batches():
+    """(name, batch dict: A, B, H, X0, N, k0 and the keyword arguments of mpc_qp_batch, None where absent; plant, disturbance for the loop alone)."""
+    import mpc_qp_affine_reference as af
+    import mpc_qp_eq_reference as eq
+    import mpc_qp_soft_reference as sq
+    for (case, f, hard_first), name in zip(sq.VARIANTS, sq.VARIANT_IDS):
+        yield 'soft ' + name, sq.batch_of(sq.instances(case, f, hard_first))
+    for c in [case() for case in eq.VALUE_CASES] + [eq.case_dependent_row()] + [eq.case_lqr(w) for w in eq.LQR_CASES]:
+        yield 'eq ' + c['name'], eq.batch_of(c)
+    for case in af.VALUE_CASES:
+        c = case()
+        yield 'aff ' + c['name'], af.batch_of(c)
+    c, plant, W = af.loop_plant()
+    yield 'aff loop_plant', dict(af.batch_of(c), plant=plant, disturbance=W)
+
+
+if args.all:
+    for name, bt in batches():
+        line = []
+        for entry in ('host', 'device'):
+            f = (lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()) if entry == 'device' else np.ascontiguousarray
+            conv = lambda v: v if v is None or isinstance(v, str) else (tuple(f(x) for x in v) if isinstance(v, tuple) else f(v))
+            kw = {k: conv(v) for k, v in bt.items() if k not in ('A', 'B', 'H', 'X0', 'N', 'k0') and v is not None}
+            loop_only = {k: kw.pop(k) for k in ('plant', 'disturbance') if k in kw}
+            a = (f(bt['A']), f(bt['B']), f(bt['H']), f(bt['X0']), bt['N'])
+            for o in (mpc_qp.mpc_qp_batch(*a, bt['k0'], **kw), mpc_qp.mpc_closed_loop_batch(*a, T, bt['k0'], **kw, **loop_only)):
+                line.append(dig(o, sorted(k for k, v in o.items() if v is not None)))
+        total.update(' '.join(line).encode())
+        print('%-40s N %d  step host %s  loop host %s  step device %s  loop device %s' % (name, bt['N'], *line), flush=True)
 print('all', total.hexdigest())

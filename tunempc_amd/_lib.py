@@ -874,122 +874,65 @@ def closed_loop_batch_device(A, B, K, X0, H, Hc, J, ncnt, ng, Hn, T, k0, return_
     return _closed_loop_views(X, U, l, lc, rowres, subres, sums, XT, info, lambda a: a.permute(0, 2, 1, 3), lambda a: a.permute(0, 2, 1))
 
 
-def _mpc_qp_views(U0, XT, info, X, U, iters, nact, hres, Xol, Uol, Lam, tr4, tr3):
-    """The outputs of the MPC QP entries (logs time-major in memory) in the layout of mpc_closed_loop_batch: permuted views, nothing is copied."""
-    return dict(U0=U0, XT=XT, info=info, X=None if X is None else tr4(X), U=None if U is None else tr4(U), iters=tr3(iters), nact=tr3(nact), hres=tr3(hres),
-                Xol=Xol, Uol=Uol, Lam=Lam)
+class _HostArrays:
+    """The array kind of the host entries for _mpc_qp_call: numpy allocation, the pointer of an optional array, the axis permutation, the call."""
+    entry = 'host'
+
+    def __init__(self, like):
+        pass
+
+    def f64(self, *sh):
+        return np.empty(sh)
+
+    def i32(self, *sh):
+        return np.empty(sh, np.int32)
+
+    def zeros(self, *sh):
+        return np.zeros(sh)
+
+    @staticmethod
+    def ptr(a):
+        if a is None or not a.size:
+            return None
+        return _iptr(a) if a.dtype == np.int32 else _dptr(a)
+
+    @staticmethod
+    def permute(a, *axes):
+        return a.transpose(*axes)
+
+    def call(self, fn, args):
+        return fn(*args)
 
 
-def mpc_qp_batch_host(A, B, H, q, Pf, D, ndcnt, d, X0, N, T, k0, tol, max_iter, return_traj, return_ol):
-    """tmpc_mpc_qp_batch_host on validated, contiguous numpy arrays (fp64; q, Pf, D, d None or arrays; ndcnt int32 or None) -> dict U0 [nb,ns,nu], XT [nb,ns,nx],
-    info [nb,ns,8], X [nb,ns,T+1,nx], U [nb,ns,T,nu] (None without return_traj), iters, nact int32 [nb,ns,T], hres [nb,ns,T], Xol [nb,ns,N+1,nx], Uol [nb,ns,N,nu],
-    Lam [nb,ns,N,nd] (None without return_ol).  The library stores the logs time-major: they are permuted views."""
-    lib = load_library()
-    nb, p, nx, mb = B.shape
-    ns, T, N = X0.shape[1], int(T), int(N)
-    nd = 0 if D is None else D.shape[2]
-    X = np.empty((nb, T + 1, ns, nx)) if return_traj else None
-    U = np.empty((nb, T, ns, mb)) if return_traj else None
-    iters = np.empty((nb, T, ns), np.int32); nact = np.empty((nb, T, ns), np.int32); hres = np.empty((nb, T, ns))
-    Xol = np.empty((nb, ns, N + 1, nx)) if return_ol else None
-    Uol = np.empty((nb, ns, N, mb)) if return_ol else None
-    Lam = np.empty((nb, ns, N, nd)) if return_ol else None
-    U0 = np.empty((nb, ns, mb)); XT = np.empty((nb, ns, nx)); info = np.zeros((nb, ns, MPC_QP_INFO_STRIDE))
-    rc = lib.tmpc_mpc_qp_batch_host(nb, p, nx, mb, nd, N, ns, T, int(k0), _dptr(A), _dptr(B), _dptr(H), _dptr(q), _dptr(Pf), _dptr(D) if nd else None,
-                                    _iptr(ndcnt) if nd else None, _dptr(d) if nd else None, _dptr(X0), float(tol), int(max_iter), _dptr(U0), _dptr(XT), _dptr(info),
-                                    _dptr(X), _dptr(U), _iptr(iters), _iptr(nact), _dptr(hres), _dptr(Xol), _dptr(Uol), _dptr(Lam))
-    if rc == -1:      # TMPC_E_ARG: the library's message names the argument
-        raise ValueError(lib.tmpc_last_error().decode())
-    _check_lqr(lib, rc, 'tmpc_mpc_qp_batch_host')
-    return _mpc_qp_views(U0, XT, info, X, U, iters, nact, hres, Xol, Uol, Lam, lambda a: a.transpose(0, 2, 1, 3), lambda a: a.transpose(0, 2, 1))
+class _DeviceArrays:
+    """The same for the device entries: torch tensors on the GPU of `like`."""
+    entry = 'device'
 
+    def __init__(self, like):
+        import torch
+        self.torch, self.dev = torch, like.device
 
-def mpc_qp_batch_device(A, B, H, q, Pf, D, ndcnt, d, X0, N, T, k0, tol, max_iter, return_traj, return_ol):
-    """tmpc_mpc_qp_batch_device on validated, contiguous torch tensors of one GPU (fp64; ndcnt int32 or None) -> the dict of mpc_qp_batch_host with torch
-    tensors; the inputs never leave HBM."""
-    import torch
-    lib = load_library()
-    nb, p, nx, mb = B.shape
-    ns, T, N = X0.shape[1], int(T), int(N)
-    nd = 0 if D is None else D.shape[2]
-    dev = A.device
-    f64 = lambda *sh: torch.empty(sh, dtype=torch.float64, device=dev)
-    i32 = lambda *sh: torch.empty(sh, dtype=torch.int32, device=dev)
-    X = f64(nb, T + 1, ns, nx) if return_traj else None
-    U = f64(nb, T, ns, mb) if return_traj else None
-    iters = i32(nb, T, ns); nact = i32(nb, T, ns); hres = f64(nb, T, ns)
-    Xol = f64(nb, ns, N + 1, nx) if return_ol else None
-    Uol = f64(nb, ns, N, mb) if return_ol else None
-    Lam = f64(nb, ns, N, nd) if return_ol else None
-    U0 = f64(nb, ns, mb); XT = f64(nb, ns, nx); info = torch.zeros((nb, ns, MPC_QP_INFO_STRIDE), dtype=torch.float64, device=dev)
-    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
-    with torch.cuda.device(dev):
-        torch.cuda.current_stream(dev).synchronize()      # the entry runs on the null stream: the inputs must be complete
-        rc = lib.tmpc_mpc_qp_batch_device(nb, p, nx, mb, nd, N, ns, T, int(k0), ptr(A), ptr(B), ptr(H), ptr(q), ptr(Pf), ptr(D) if nd else None,
-                                          ptr(ndcnt) if nd else None, ptr(d) if nd else None, ptr(X0), float(tol), int(max_iter), ptr(U0), ptr(XT), ptr(info),
-                                          ptr(X), ptr(U), ptr(iters), ptr(nact), ptr(hres), ptr(Xol), ptr(Uol), ptr(Lam))
-    if rc == -1:
-        raise ValueError(lib.tmpc_last_error().decode())
-    _check_lqr(lib, rc, 'tmpc_mpc_qp_batch_device')
-    return _mpc_qp_views(U0, XT, info, X, U, iters, nact, hres, Xol, Uol, Lam, lambda a: a.permute(0, 2, 1, 3), lambda a: a.permute(0, 2, 1))
+    def f64(self, *sh):
+        return self.torch.empty(sh, dtype=self.torch.float64, device=self.dev)
 
+    def i32(self, *sh):
+        return self.torch.empty(sh, dtype=self.torch.int32, device=self.dev)
 
-def mpc_qp_soft_batch_host(A, B, H, q, Pf, D, ndcnt, d, penalty, X0, N, T, k0, tol, max_iter, return_traj, return_ol):
-    """tmpc_mpc_qp_soft_batch_host on validated, contiguous numpy arrays (penalty fp64 [nb,p,nd]) -> the dict of mpc_qp_batch_host with Eol [nb,ns,N,nd] (None
-    without return_ol) and nviol int32 [nb,ns,T]."""
-    lib = load_library()
-    nb, p, nx, mb = B.shape
-    ns, T, N = X0.shape[1], int(T), int(N)
-    nd = D.shape[2]
-    X = np.empty((nb, T + 1, ns, nx)) if return_traj else None
-    U = np.empty((nb, T, ns, mb)) if return_traj else None
-    iters = np.empty((nb, T, ns), np.int32); nact = np.empty((nb, T, ns), np.int32); nviol = np.empty((nb, T, ns), np.int32); hres = np.empty((nb, T, ns))
-    Xol = np.empty((nb, ns, N + 1, nx)) if return_ol else None
-    Uol = np.empty((nb, ns, N, mb)) if return_ol else None
-    Lam = np.empty((nb, ns, N, nd)) if return_ol else None
-    Eol = np.empty((nb, ns, N, nd)) if return_ol else None
-    U0 = np.empty((nb, ns, mb)); XT = np.empty((nb, ns, nx)); info = np.zeros((nb, ns, MPC_QP_INFO_STRIDE))
-    rc = lib.tmpc_mpc_qp_soft_batch_host(nb, p, nx, mb, nd, N, ns, T, int(k0), _dptr(A), _dptr(B), _dptr(H), _dptr(q), _dptr(Pf), _dptr(D), _iptr(ndcnt), _dptr(d),
-                                         _dptr(X0), float(tol), int(max_iter), _dptr(U0), _dptr(XT), _dptr(info), _dptr(X), _dptr(U), _iptr(iters), _iptr(nact),
-                                         _dptr(hres), _dptr(Xol), _dptr(Uol), _dptr(Lam), _dptr(penalty), _dptr(Eol), _iptr(nviol))
-    if rc == -1:
-        raise ValueError(lib.tmpc_last_error().decode())
-    _check_lqr(lib, rc, 'tmpc_mpc_qp_soft_batch_host')
-    out = _mpc_qp_views(U0, XT, info, X, U, iters, nact, hres, Xol, Uol, Lam, lambda a: a.transpose(0, 2, 1, 3), lambda a: a.transpose(0, 2, 1))
-    out.update(Eol=Eol, nviol=nviol.transpose(0, 2, 1))
-    return out
+    def zeros(self, *sh):
+        return self.torch.zeros(sh, dtype=self.torch.float64, device=self.dev)
 
+    @staticmethod
+    def ptr(t):
+        return C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
 
-def mpc_qp_soft_batch_device(A, B, H, q, Pf, D, ndcnt, d, penalty, X0, N, T, k0, tol, max_iter, return_traj, return_ol):
-    """tmpc_mpc_qp_soft_batch_device on validated, contiguous torch tensors of one GPU -> the dict of mpc_qp_soft_batch_host with torch tensors."""
-    import torch
-    lib = load_library()
-    nb, p, nx, mb = B.shape
-    ns, T, N = X0.shape[1], int(T), int(N)
-    nd = D.shape[2]
-    dev = A.device
-    f64 = lambda *sh: torch.empty(sh, dtype=torch.float64, device=dev)
-    i32 = lambda *sh: torch.empty(sh, dtype=torch.int32, device=dev)
-    X = f64(nb, T + 1, ns, nx) if return_traj else None
-    U = f64(nb, T, ns, mb) if return_traj else None
-    iters = i32(nb, T, ns); nact = i32(nb, T, ns); nviol = i32(nb, T, ns); hres = f64(nb, T, ns)
-    Xol = f64(nb, ns, N + 1, nx) if return_ol else None
-    Uol = f64(nb, ns, N, mb) if return_ol else None
-    Lam = f64(nb, ns, N, nd) if return_ol else None
-    Eol = f64(nb, ns, N, nd) if return_ol else None
-    U0 = f64(nb, ns, mb); XT = f64(nb, ns, nx); info = torch.zeros((nb, ns, MPC_QP_INFO_STRIDE), dtype=torch.float64, device=dev)
-    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
-    with torch.cuda.device(dev):
-        torch.cuda.current_stream(dev).synchronize()      # the entry runs on the null stream: the inputs must be complete
-        rc = lib.tmpc_mpc_qp_soft_batch_device(nb, p, nx, mb, nd, N, ns, T, int(k0), ptr(A), ptr(B), ptr(H), ptr(q), ptr(Pf), ptr(D), ptr(ndcnt), ptr(d), ptr(X0),
-                                               float(tol), int(max_iter), ptr(U0), ptr(XT), ptr(info), ptr(X), ptr(U), ptr(iters), ptr(nact), ptr(hres), ptr(Xol),
-                                               ptr(Uol), ptr(Lam), ptr(penalty), ptr(Eol), ptr(nviol))
-    if rc == -1:
-        raise ValueError(lib.tmpc_last_error().decode())
-    _check_lqr(lib, rc, 'tmpc_mpc_qp_soft_batch_device')
-    out = _mpc_qp_views(U0, XT, info, X, U, iters, nact, hres, Xol, Uol, Lam, lambda a: a.permute(0, 2, 1, 3), lambda a: a.permute(0, 2, 1))
-    out.update(Eol=Eol, nviol=nviol.permute(0, 2, 1))
-    return out
+    @staticmethod
+    def permute(t, *axes):
+        return t.permute(*axes)
+
+    def call(self, fn, args):
+        with self.torch.cuda.device(self.dev):
+            self.torch.cuda.current_stream(self.dev).synchronize()      # the entry runs on the null stream: the inputs must be complete
+            return fn(*args)
 
 
 def _mpc_qp_eq_terminal(Tx, nx):
@@ -1001,87 +944,93 @@ def _mpc_qp_eq_terminal(Tx, nx):
     return int(Tx.shape[2]), Tx, int(Tx.shape[2])
 
 
-def mpc_qp_eq_batch_host(A, B, H, q, Pf, D, ndcnt, d, penalty, J, r, necnt, Tx, X0, N, T, k0, tol, max_iter, return_traj, return_ol, aff=None):
-    """tmpc_mpc_qp_eq_batch_host on validated, contiguous numpy arrays (penalty, J [nb,p,ne,n], r, necnt int32 None or arrays; Tx None, 'constraint' or
-    [nb,p,nt,nx]) -> the dict of mpc_qp_soft_batch_host (Eol None and no nviol without penalty) with Nu [nb,ns,N,ne], NuT [nb,ns,nt] (None without return_ol)
-    and eres [nb,ns,T].  aff (mpc_qp_aff_batch_host): the seven arrays offset, qf, terminal_rhs, Ap, Bp, cp, W or None each -> tmpc_mpc_qp_aff_batch_host."""
+_MPC_QP_LEVELS = {'hard': '', 'soft': 'soft_', 'eq': 'eq_', 'aff': 'aff_'}
+
+
+def _mpc_qp_call(level, kind, A, B, H, q, Pf, D, ndcnt, d, X0, N, T, k0, tol, max_iter, return_traj, return_ol, penalty=None, J=None, r=None, necnt=None,
+                 Tx=None, aff=None):
+    """The eight MPC QP entries: tmpc_mpc_qp_<level>batch_<host or device> of the level 'hard', 'soft', 'eq' or 'aff' on validated, contiguous arrays of `kind`
+    (_HostArrays: numpy, _DeviceArrays: torch tensors of one GPU).  Allocates the outputs, passes the 31 common arguments and the tails of the level (soft:
+    penalty, Eol, nviol; eq: the rows and Nu, NuT, eres; aff: the seven arrays), an absent or empty array as NULL, and returns the dict of the level.  The
+    library stores the logs time-major: X, U and the per-step logs are permuted views, nothing is copied."""
     lib = load_library()
-    entry, name, tail = lib.tmpc_mpc_qp_eq_batch_host, 'tmpc_mpc_qp_eq_batch_host', ()
-    if aff is not None:
-        entry, name, tail = lib.tmpc_mpc_qp_aff_batch_host, 'tmpc_mpc_qp_aff_batch_host', tuple(_dptr(a) for a in aff)
+    xp = kind(A)
+    name = 'tmpc_mpc_qp_%sbatch_%s' % (_MPC_QP_LEVELS[level], xp.entry)
     nb, p, nx, mb = B.shape
     ns, T, N = X0.shape[1], int(T), int(N)
     nd = 0 if D is None else D.shape[2]
     ne = 0 if J is None else J.shape[2]
     nt, Txa, ntr = _mpc_qp_eq_terminal(Tx, nx)
-    X = np.empty((nb, T + 1, ns, nx)) if return_traj else None
-    U = np.empty((nb, T, ns, mb)) if return_traj else None
-    iters = np.empty((nb, T, ns), np.int32); nact = np.empty((nb, T, ns), np.int32); hres = np.empty((nb, T, ns)); eres = np.empty((nb, T, ns))
-    nviol = np.empty((nb, T, ns), np.int32) if penalty is not None else None
-    Xol = np.empty((nb, ns, N + 1, nx)) if return_ol else None
-    Uol = np.empty((nb, ns, N, mb)) if return_ol else None
-    Lam = np.empty((nb, ns, N, nd)) if return_ol else None
-    Eol = np.empty((nb, ns, N, nd)) if return_ol and penalty is not None else None
-    Nu = np.empty((nb, ns, N, ne)) if return_ol else None
-    NuT = np.empty((nb, ns, ntr)) if return_ol else None
-    U0 = np.empty((nb, ns, mb)); XT = np.empty((nb, ns, nx)); info = np.zeros((nb, ns, MPC_QP_INFO_STRIDE))
-    opt = lambda a: _dptr(a) if a is not None and a.size else None
-    rc = entry(nb, p, nx, mb, nd, N, ns, T, int(k0), _dptr(A), _dptr(B), _dptr(H), _dptr(q), _dptr(Pf), _dptr(D) if nd else None,
-               _iptr(ndcnt) if nd else None, _dptr(d) if nd else None, _dptr(X0), float(tol), int(max_iter), _dptr(U0), _dptr(XT),
-               _dptr(info), _dptr(X), _dptr(U), _iptr(iters), _iptr(nact), _dptr(hres), _dptr(Xol), _dptr(Uol), opt(Lam), _dptr(penalty),
-               opt(Eol), _iptr(nviol), ne, _dptr(J) if ne else None, _dptr(r) if ne else None, _iptr(necnt) if ne else None, nt, _dptr(Txa),
-               opt(Nu), opt(NuT), _dptr(eres), *tail)
-    if rc == -1:
+    eq = level in ('eq', 'aff')
+    soft = level == 'soft' or (eq and penalty is not None)                  # (the eq level without penalty passes Eol = nviol = NULL)
+    traj = lambda *sh: xp.f64(*sh) if return_traj else None
+    ol = lambda *sh: xp.f64(*sh) if return_ol else None
+    X, U = traj(nb, T + 1, ns, nx), traj(nb, T, ns, mb)
+    iters, nact, hres = xp.i32(nb, T, ns), xp.i32(nb, T, ns), xp.f64(nb, T, ns)
+    Xol, Uol, Lam = ol(nb, ns, N + 1, nx), ol(nb, ns, N, mb), ol(nb, ns, N, nd)
+    U0, XT, info = xp.f64(nb, ns, mb), xp.f64(nb, ns, nx), xp.zeros(nb, ns, MPC_QP_INFO_STRIDE)
+    Eol, nviol = (ol(nb, ns, N, nd), xp.i32(nb, T, ns)) if soft else (None, None)
+    Nu, NuT, eres = (ol(nb, ns, N, ne), ol(nb, ns, ntr), xp.f64(nb, T, ns)) if eq else (None, None, None)
+    ptr = xp.ptr
+    rows = lambda a, cap: ptr(a) if cap else None
+    args = [nb, p, nx, mb, nd, N, ns, T, int(k0), ptr(A), ptr(B), ptr(H), ptr(q), ptr(Pf), rows(D, nd), rows(ndcnt, nd), rows(d, nd), ptr(X0), float(tol),
+            int(max_iter)] + [ptr(a) for a in (U0, XT, info, X, U, iters, nact, hres, Xol, Uol, Lam)]
+    if level != 'hard':
+        args += [ptr(penalty), ptr(Eol), ptr(nviol)]
+    if eq:
+        args += [ne, rows(J, ne), rows(r, ne), rows(necnt, ne), nt, ptr(Txa), ptr(Nu), ptr(NuT), ptr(eres)]
+    if level == 'aff':
+        args += [ptr(a) for a in aff]
+    rc = xp.call(getattr(lib, name), args)
+    if rc == -1:      # TMPC_E_ARG: the library's message names the argument
         raise ValueError(lib.tmpc_last_error().decode())
     _check_lqr(lib, rc, name)
-    out = _mpc_qp_views(U0, XT, info, X, U, iters, nact, hres, Xol, Uol, Lam, lambda a: a.transpose(0, 2, 1, 3), lambda a: a.transpose(0, 2, 1))
-    out.update(Nu=Nu, NuT=NuT, eres=eres.transpose(0, 2, 1))
-    if penalty is not None:
-        out.update(Eol=Eol, nviol=nviol.transpose(0, 2, 1))
+    tr4, tr3 = (lambda a: None if a is None else xp.permute(a, 0, 2, 1, 3)), (lambda a: xp.permute(a, 0, 2, 1))
+    out = dict(U0=U0, XT=XT, info=info, X=tr4(X), U=tr4(U), iters=tr3(iters), nact=tr3(nact), hres=tr3(hres), Xol=Xol, Uol=Uol, Lam=Lam)
+    if eq:
+        out.update(Nu=Nu, NuT=NuT, eres=tr3(eres))
+    if soft:
+        out.update(Eol=Eol, nviol=tr3(nviol))
     return out
+
+
+def mpc_qp_batch_host(A, B, H, q, Pf, D, ndcnt, d, X0, N, T, k0, tol, max_iter, return_traj, return_ol):
+    """tmpc_mpc_qp_batch_host on validated, contiguous numpy arrays (fp64; q, Pf, D, d None or arrays; ndcnt int32 or None) -> dict U0 [nb,ns,nu], XT [nb,ns,nx],
+    info [nb,ns,8], X [nb,ns,T+1,nx], U [nb,ns,T,nu] (None without return_traj), iters, nact int32 [nb,ns,T], hres [nb,ns,T], Xol [nb,ns,N+1,nx], Uol [nb,ns,N,nu],
+    Lam [nb,ns,N,nd] (None without return_ol)."""
+    return _mpc_qp_call('hard', _HostArrays, A, B, H, q, Pf, D, ndcnt, d, X0, N, T, k0, tol, max_iter, return_traj, return_ol)
+
+
+def mpc_qp_batch_device(A, B, H, q, Pf, D, ndcnt, d, X0, N, T, k0, tol, max_iter, return_traj, return_ol):
+    """tmpc_mpc_qp_batch_device on validated, contiguous torch tensors of one GPU (fp64; ndcnt int32 or None) -> the dict of mpc_qp_batch_host with torch
+    tensors; the inputs never leave HBM."""
+    return _mpc_qp_call('hard', _DeviceArrays, A, B, H, q, Pf, D, ndcnt, d, X0, N, T, k0, tol, max_iter, return_traj, return_ol)
+
+
+def mpc_qp_soft_batch_host(A, B, H, q, Pf, D, ndcnt, d, penalty, X0, N, T, k0, tol, max_iter, return_traj, return_ol):
+    """tmpc_mpc_qp_soft_batch_host on validated, contiguous numpy arrays (penalty fp64 [nb,p,nd]) -> the dict of mpc_qp_batch_host with Eol [nb,ns,N,nd] (None
+    without return_ol) and nviol int32 [nb,ns,T]."""
+    return _mpc_qp_call('soft', _HostArrays, A, B, H, q, Pf, D, ndcnt, d, X0, N, T, k0, tol, max_iter, return_traj, return_ol, penalty)
+
+
+def mpc_qp_soft_batch_device(A, B, H, q, Pf, D, ndcnt, d, penalty, X0, N, T, k0, tol, max_iter, return_traj, return_ol):
+    """tmpc_mpc_qp_soft_batch_device on validated, contiguous torch tensors of one GPU -> the dict of mpc_qp_soft_batch_host with torch tensors."""
+    return _mpc_qp_call('soft', _DeviceArrays, A, B, H, q, Pf, D, ndcnt, d, X0, N, T, k0, tol, max_iter, return_traj, return_ol, penalty)
+
+
+def mpc_qp_eq_batch_host(A, B, H, q, Pf, D, ndcnt, d, penalty, J, r, necnt, Tx, X0, N, T, k0, tol, max_iter, return_traj, return_ol, aff=None):
+    """tmpc_mpc_qp_eq_batch_host on validated, contiguous numpy arrays (penalty, J [nb,p,ne,n], r, necnt int32 None or arrays; Tx None, 'constraint' or
+    [nb,p,nt,nx]) -> the dict of mpc_qp_soft_batch_host (Eol None and no nviol without penalty) with Nu [nb,ns,N,ne], NuT [nb,ns,nt] (None without return_ol)
+    and eres [nb,ns,T].  aff (mpc_qp_aff_batch_host): the seven arrays offset, qf, terminal_rhs, Ap, Bp, cp, W or None each -> tmpc_mpc_qp_aff_batch_host."""
+    return _mpc_qp_call('eq' if aff is None else 'aff', _HostArrays, A, B, H, q, Pf, D, ndcnt, d, X0, N, T, k0, tol, max_iter, return_traj, return_ol, penalty, J,
+                        r, necnt, Tx, aff)
 
 
 def mpc_qp_eq_batch_device(A, B, H, q, Pf, D, ndcnt, d, penalty, J, r, necnt, Tx, X0, N, T, k0, tol, max_iter, return_traj, return_ol, aff=None):
     """tmpc_mpc_qp_eq_batch_device on validated, contiguous torch tensors of one GPU -> the dict of mpc_qp_eq_batch_host with torch tensors.  aff as there:
     tmpc_mpc_qp_aff_batch_device."""
-    import torch
-    lib = load_library()
-    entry, name = (lib.tmpc_mpc_qp_eq_batch_device, 'tmpc_mpc_qp_eq_batch_device') if aff is None else (lib.tmpc_mpc_qp_aff_batch_device, 'tmpc_mpc_qp_aff_batch_device')
-    nb, p, nx, mb = B.shape
-    ns, T, N = X0.shape[1], int(T), int(N)
-    nd = 0 if D is None else D.shape[2]
-    ne = 0 if J is None else J.shape[2]
-    nt, Txa, ntr = _mpc_qp_eq_terminal(Tx, nx)
-    dev = A.device
-    f64 = lambda *sh: torch.empty(sh, dtype=torch.float64, device=dev)
-    i32 = lambda *sh: torch.empty(sh, dtype=torch.int32, device=dev)
-    X = f64(nb, T + 1, ns, nx) if return_traj else None
-    U = f64(nb, T, ns, mb) if return_traj else None
-    iters = i32(nb, T, ns); nact = i32(nb, T, ns); hres = f64(nb, T, ns); eres = f64(nb, T, ns)
-    nviol = i32(nb, T, ns) if penalty is not None else None
-    Xol = f64(nb, ns, N + 1, nx) if return_ol else None
-    Uol = f64(nb, ns, N, mb) if return_ol else None
-    Lam = f64(nb, ns, N, nd) if return_ol else None
-    Eol = f64(nb, ns, N, nd) if return_ol and penalty is not None else None
-    Nu = f64(nb, ns, N, ne) if return_ol else None
-    NuT = f64(nb, ns, ntr) if return_ol else None
-    U0 = f64(nb, ns, mb); XT = f64(nb, ns, nx); info = torch.zeros((nb, ns, MPC_QP_INFO_STRIDE), dtype=torch.float64, device=dev)
-    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
-    with torch.cuda.device(dev):
-        torch.cuda.current_stream(dev).synchronize()      # the entry runs on the null stream: the inputs must be complete
-        rc = entry(nb, p, nx, mb, nd, N, ns, T, int(k0), ptr(A), ptr(B), ptr(H), ptr(q), ptr(Pf), ptr(D) if nd else None,
-                   ptr(ndcnt) if nd else None, ptr(d) if nd else None, ptr(X0), float(tol), int(max_iter), ptr(U0), ptr(XT), ptr(info),
-                   ptr(X), ptr(U), ptr(iters), ptr(nact), ptr(hres), ptr(Xol), ptr(Uol), ptr(Lam), ptr(penalty), ptr(Eol), ptr(nviol), ne,
-                   ptr(J) if ne else None, ptr(r) if ne else None, ptr(necnt) if ne else None, nt, ptr(Txa), ptr(Nu), ptr(NuT), ptr(eres),
-                   *(() if aff is None else tuple(ptr(a) for a in aff)))
-    if rc == -1:
-        raise ValueError(lib.tmpc_last_error().decode())
-    _check_lqr(lib, rc, name)
-    out = _mpc_qp_views(U0, XT, info, X, U, iters, nact, hres, Xol, Uol, Lam, lambda a: a.permute(0, 2, 1, 3), lambda a: a.permute(0, 2, 1))
-    out.update(Nu=Nu, NuT=NuT, eres=eres.permute(0, 2, 1))
-    if penalty is not None:
-        out.update(Eol=Eol, nviol=nviol.permute(0, 2, 1))
-    return out
+    return _mpc_qp_call('eq' if aff is None else 'aff', _DeviceArrays, A, B, H, q, Pf, D, ndcnt, d, X0, N, T, k0, tol, max_iter, return_traj, return_ol, penalty,
+                        J, r, necnt, Tx, aff)
 
 
 def mpc_qp_aff_batch_host(A, B, H, q, Pf, D, ndcnt, d, penalty, J, r, necnt, Tx, aff, X0, N, T, k0, tol, max_iter, return_traj, return_ol):

@@ -2172,13 +2172,54 @@ int tmpc_closed_loop_batch_host(int nb, int p, int nx, int mb, int nr, int ng, i
 
 // The inequality-constrained MPC step and closed loop (tmpc_mpc_qp.h): one workgroup per instance (problem, initial state), min(instances, MQ_SLOTS) workgroups
 // loop over the instances, each with its slot of the workspace.
+// The eight entries (hard, soft, eq, aff; host and device) differ in their argument lists only.  An entry writes its arguments into an MpcQpCall (what it has no
+// argument for stays null / zero) and hands the record to mpc_qp_host or mpc_qp_device.  Either checks it once under the entry's name (mpc_qp_validate), reads
+// the kernel off it with its LDS and workspace sizes (mpc_qp_kind), zeroes the outputs that this kernel does not write (mpc_qp_zero_unwritten) and launches
+// (mpc_qp_launch); the host path stages every array of the record through one device buffer.  No entry calls another.
 static_assert(MQ_INFO == TMPC_MPC_QP_INFO, "tunempc_hip.h: info stride of the MPC QP entries");
 constexpr long long MQ_WS_CAP_BYTES = 1LL << 30;      // the workspace of a launch: fewer slots beyond this (one slot at the least)
 
-static int mpc_qp_check(const char* who, int nb, int p, int nx, int mb, int nd, int N, int ns, int T, int k0, const void* A, const void* B, const void* H,
-                        const void* D, const void* ndcnt, const void* d, const void* X0, double tol, int max_iter, const void* U0, const void* XT,
-                        const void* info) {
-  if (nb < 1 || p < 1 || nx < 1 || mb < 1 || N < 1 || ns < 1 || T < 1 || nd < 0 || !A || !B || !H || !X0 || !U0 || !XT || !info) {
+// One call: the arguments of the aff entries (the longest list) in their order; nt as the caller gave it (-1: x_N = 0 without Tx, nx rows).  The pointers are
+// the caller's, host or device by the path; mpc_qp_host launches a copy that holds the device images.
+struct MpcQpCall {
+  const char* who;
+  int nb, p, nx, mb, nd, N, ns, T, k0;
+  const double* A; const double* B; const double* H; const double* q; const double* Pf; const double* D; const int32_t* ndcnt; const double* d; const double* X0;
+  double tol; int max_iter;
+  double* U0; double* XT; double* info; double* X; double* U; int32_t* iters; int32_t* nact; double* hres; double* Xol; double* Uol; double* Lam;
+  const double* penalty = nullptr; double* Eol = nullptr; int32_t* nviol = nullptr;                                                    // the soft entries
+  int ne = 0; const double* J = nullptr; const double* r = nullptr; const int32_t* necnt = nullptr; int nt = 0; const double* Tx = nullptr;      // the eq entries
+  double* Nu = nullptr; double* NuT = nullptr; double* eres = nullptr;
+  MpcQpAff aff = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};                                                      // the aff entries
+  int ntk() const { return nt < 0 ? nx : nt; }      // terminal rows of the kernel
+};
+#define MPC_QP_ARGS31 nb, p, nx, mb, nd, N, ns, T, k0, A, B, H, q, Pf, D, ndcnt, d, X0, tol, max_iter, U0, XT, info, X, U, iters, nact, hres, Xol, Uol, Lam
+
+// The kernel of a call: SOFT with a penalty; EQ with equality rows, terminal rows or an affine array; AFF (an instantiation of the two EQ kernels only) with an
+// affine array.  Sizes in doubles: the LDS of the hard layout, of the soft layout (the hard one without penalty) and of the kernel that runs -- the layouts
+// nest, the three LDS tests of mpc_qp_validate tell which part no longer fits --, and the workspace per slot.  Row capacities enter the LDS sizes clamped to
+// 65536 (no 32-bit overflow before they are refused; a call that passes the checks is far below).
+struct MpcQpKind { bool soft, eq, aff; long long lds_hard, lds_soft, lds, ws; };
+static bool mpc_qp_aff_any(const MpcQpAff& a) { return a.c || a.qf || a.t || a.Ap || a.Bp || a.cp || a.W; }
+static MpcQpKind mpc_qp_kind(const MpcQpCall& c) {
+  MpcQpKind k;
+  k.soft = c.penalty != nullptr;
+  k.aff = mpc_qp_aff_any(c.aff);
+  k.eq = c.ne > 0 || c.nt != 0 || k.aff;
+  const int nd = c.nd < 65536 ? c.nd : 65536, ne = c.ne < 65536 ? c.ne : 65536;
+  k.lds = k.lds_soft = k.lds_hard = mpc_qp_lds(c.nx, c.mb, nd).total;
+  k.ws = mpc_qp_ws_doubles(c.nx, c.mb, c.nd, c.N);
+  if (k.soft) { k.lds = k.lds_soft = mpc_qp_soft_lds(c.nx, c.mb, nd).total; k.ws = mpc_qp_soft_ws_doubles(c.nx, c.mb, c.nd, c.N); }
+  if (k.eq) { k.lds = mpc_qp_eq_lds(c.nx, c.mb, nd, ne, k.soft).total; k.ws = mpc_qp_eq_ws_doubles(c.nx, c.mb, c.nd, c.N, c.ne, c.ntk(), k.soft); }
+  return k;
+}
+
+// Every check that needs no device, in the order base, soft, eq, aff, under the name of the entry that was called; *kind on success.  The eq and aff parts
+// run for every entry: with ne = 0, nt = 0 and none of their pointers (all that the hard and soft entries can state) they cannot fail.
+static int mpc_qp_validate(const MpcQpCall& c, MpcQpKind* kind) {
+  const char* who = c.who;
+  const int nb = c.nb, p = c.p, nx = c.nx, mb = c.mb, nd = c.nd, N = c.N, ns = c.ns, T = c.T, k0 = c.k0, ne = c.ne, nt = c.nt;
+  if (nb < 1 || p < 1 || nx < 1 || mb < 1 || N < 1 || ns < 1 || T < 1 || nd < 0 || !c.A || !c.B || !c.H || !c.X0 || !c.U0 || !c.XT || !c.info) {
     snprintf(g_err, sizeof(g_err), "%s: bad argument (nb, p, nx, nu, N, ns, T >= 1, nd >= 0, non-null A, B, H, X0, U0, XT, info; got N = %d, ns = %d, T = %d, "
              "nd = %d)", who, N, ns, T, nd);
     return TMPC_E_ARG;
@@ -2187,143 +2228,72 @@ static int mpc_qp_check(const char* who, int nb, int p, int nx, int mb, int nd, 
     snprintf(g_err, sizeof(g_err), "%s: bad argument (starting phase k0 in 0 .. p - 1 = %d; got %d)", who, p - 1, k0);
     return TMPC_E_ARG;
   }
-  if (((nd > 0) != (D != nullptr)) || ((nd > 0) != (d != nullptr)) || (ndcnt && !D)) {
+  if (((nd > 0) != (c.D != nullptr)) || ((nd > 0) != (c.d != nullptr)) || (c.ndcnt && !c.D)) {
     snprintf(g_err, sizeof(g_err), "%s: bad argument (D and d non-null exactly when nd > 0, the row capacity per stage; ndcnt only with D; got nd = %d)", who, nd);
     return TMPC_E_ARG;
   }
-  if (!(tol > 0.0) || max_iter < 1) {
-    snprintf(g_err, sizeof(g_err), "%s: bad argument (tol > 0, max_iter >= 1; got tol = %g, max_iter = %d)", who, tol, max_iter);
+  if (!(c.tol > 0.0) || c.max_iter < 1) {
+    snprintf(g_err, sizeof(g_err), "%s: bad argument (tol > 0, max_iter >= 1; got tol = %g, max_iter = %d)", who, c.tol, c.max_iter);
     return TMPC_E_ARG;
   }
   if (nx + mb > LQR_NMAX) {
     snprintf(g_err, sizeof(g_err), "%s: the MPC step handles stage blocks up to nx + nu = %d (got %d)", who, LQR_NMAX, nx + mb);
     return TMPC_E_UNSUPPORTED;
   }
-  const MpcQpLds L = mpc_qp_lds(nx, mb, nd < 65536 ? nd : 65536);
-  const long long bytes = (long long)L.total * (long long)sizeof(double);
-  if (bytes > LQR_LDS_BYTES) {
-    snprintf(g_err, sizeof(g_err), "%s: nx = %d, nu = %d with room for %d rows per stage needs %lld bytes of LDS (limit %d)", who, nx, mb, nd, bytes, LQR_LDS_BYTES);
+  const MpcQpKind k = mpc_qp_kind(c);
+  if (k.lds_hard * 8 > LQR_LDS_BYTES) {
+    snprintf(g_err, sizeof(g_err), "%s: nx = %d, nu = %d with room for %d rows per stage needs %lld bytes of LDS (limit %d)", who, nx, mb, nd, k.lds_hard * 8,
+             LQR_LDS_BYTES);
     return TMPC_E_UNSUPPORTED;
   }
   if ((long long)(N + 1) * (nx + mb) > 0x7fffffffLL / 4 || (long long)N * (nd > mb * (nx + mb + 1) ? nd : mb * (nx + mb + 1)) > 0x7fffffffLL / 4) {
     snprintf(g_err, sizeof(g_err), "%s: horizon N = %d too long for this stage shape (32-bit indices inside a slot)", who, N);
     return TMPC_E_UNSUPPORTED;
   }
-  return TMPC_OK;
-}
-
-// The arguments of the EQ instantiations (tmpc_mpc_qp.h): device pointers; nt counts the terminal rows (Tx null: the identity, nt = nx).
-struct MpcQpEqArgs {
-  int ne = 0; const double* J = nullptr; const double* r = nullptr; const int32_t* necnt = nullptr; int nt = 0; const double* Tx = nullptr;
-  double* Nu = nullptr; double* NuT = nullptr; double* eres = nullptr;
-};
-
-static thread_local EigScratch g_mpc_qp_ws;           // workspace slots of both entries, kept between calls and grown on demand
-
-static int mpc_qp_launch(int nb, int p, int nx, int mb, int nd, int N, int ns, int T, int k0, const double* A, const double* B, const double* H, const double* q,
-                         const double* Pf, const double* D, const int32_t* ndcnt, const double* d, const double* X0, double tol, int max_iter, double* U0,
-                         double* XT, double* info, double* X, double* U, int32_t* iters, int32_t* nact, double* hres, double* Xol, double* Uol, double* Lam,
-                         const double* penalty = nullptr, double* Eol = nullptr, int32_t* nviol = nullptr, const MpcQpEqArgs* eq = nullptr,
-                         const MpcQpAff* aff = nullptr) {
-  // penalty: the SOFT instantiation with its longer LDS layout and workspace slots; without it the hard kernel (Eol, nviol are not passed then)
-  // eq: the EQ instantiations (equality rows and / or terminal rows), their layout after the hard or soft one
-  // aff (only with eq): the AFF instantiations of the two EQ kernels, the same layouts
-  const MpcQpEqArgs none;
-  const MpcQpEqArgs& e = eq ? *eq : none;
-  const size_t lds_bytes = (size_t)(eq ? mpc_qp_eq_lds(nx, mb, nd, e.ne, penalty != nullptr).total
-                                       : (penalty ? mpc_qp_soft_lds(nx, mb, nd).total : mpc_qp_lds(nx, mb, nd).total)) * sizeof(double);
-  const long long ninst = (long long)nb * ns, per = (eq ? mpc_qp_eq_ws_doubles(nx, mb, nd, N, e.ne, e.nt, penalty != nullptr)
-                                                        : (penalty ? mpc_qp_soft_ws_doubles(nx, mb, nd, N) : mpc_qp_ws_doubles(nx, mb, nd, N))) * 8;
-  long long slots = ninst < MQ_SLOTS ? ninst : MQ_SLOTS;
-  if (slots * per > MQ_WS_CAP_BYTES) slots = MQ_WS_CAP_BYTES / per;
-  if (slots < 1) slots = 1;
-  HIPCHK(g_mpc_qp_ws.reserve((size_t)(slots * per)));
-  auto kern = eq ? (penalty ? k_mpc_qp<true, true, false> : k_mpc_qp<false, true, false>) : (penalty ? k_mpc_qp<true, false, false> : k_mpc_qp<false, false, false>);
-  if (eq && aff) kern = penalty ? k_mpc_qp<true, true, true> : k_mpc_qp<false, true, true>;
-  const MpcQpAff no_aff = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  HIPCHK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LQR_LDS_BYTES));
-  int lcw = 0;
-  while ((1 << lcw) < nx + mb) ++lcw;
-  hipLaunchKernelGGL(kern, dim3((unsigned)slots), dim3(LQR_NT), lds_bytes, 0, p, nx, mb, nd, lcw, N, ns, T, k0, ninst, A, B, H, q, Pf, D, (const int*)ndcnt, d,
-                     X0, tol, max_iter, (double*)g_mpc_qp_ws.p, U0, XT, info, X, U, (int*)iters, (int*)nact, hres, Xol, Uol, Lam, penalty, Eol, (int*)nviol,
-                     e.ne, e.J, e.r, (const int*)e.necnt, e.nt, e.Tx, e.Nu, e.NuT, e.eres, aff ? *aff : no_aff);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(0));
-  return TMPC_OK;
-}
-
-int tmpc_mpc_qp_batch_device(int nb, int p, int nx, int mb, int nd, int N, int ns, int T, int k0, const double* A, const double* B, const double* H,
-                             const double* q, const double* Pf, const double* D, const int32_t* ndcnt, const double* d, const double* X0, double tol,
-                             int max_iter, double* U0, double* XT, double* info, double* X, double* U, int32_t* iters, int32_t* nact, double* hres, double* Xol,
-                             double* Uol, double* Lam) {
-  const int rc = mpc_qp_check("tmpc_mpc_qp_batch_device", nb, p, nx, mb, nd, N, ns, T, k0, A, B, H, D, ndcnt, d, X0, tol, max_iter, U0, XT, info);
-  if (rc != TMPC_OK) return rc;
-  return mpc_qp_launch(nb, p, nx, mb, nd, N, ns, T, k0, A, B, H, q, Pf, D, ndcnt, d, X0, tol, max_iter, U0, XT, info, X, U, iters, nact, hres, Xol, Uol, Lam);
-}
-
-static thread_local EigScratch g_mpc_qp_scratch;      // device images of the host entry
-
-int tmpc_mpc_qp_batch_host(int nb, int p, int nx, int mb, int nd, int N, int ns, int T, int k0, const double* A, const double* B, const double* H,
-                           const double* q, const double* Pf, const double* D, const int32_t* ndcnt, const double* d, const double* X0, double tol, int max_iter,
-                           double* U0, double* XT, double* info, double* X, double* U, int32_t* iters, int32_t* nact, double* hres, double* Xol, double* Uol,
-                           double* Lam) {
-  const char* who = "tmpc_mpc_qp_batch_host";
-  const int rc = mpc_qp_check(who, nb, p, nx, mb, nd, N, ns, T, k0, A, B, H, D, ndcnt, d, X0, tol, max_iter, U0, XT, info);
-  if (rc != TMPC_OK) return rc;
-  const size_t n = (size_t)nx + mb, st = (size_t)nb * p, sn = (size_t)nb * ns;
-  if (ndcnt) for (size_t i = 0; i < st; ++i) if (ndcnt[i] < 0 || ndcnt[i] > nd) {
-    snprintf(g_err, sizeof(g_err), "%s: ndcnt[%zu][%zu] = %d outside 0 .. nd = %d", who, i / p, i % p, (int)ndcnt[i], nd);
-    return TMPC_E_ARG;
-  }
-  // inputs A | B | H | q | Pf | D | d | X0, outputs U0 | XT | info | X | U | hres | Xol | Uol | Lam, then the int32 arrays ndcnt | iters | nact
-  const size_t cA = st * nx * nx, cB = st * nx * mb, cH = st * n * n, cq = q ? st * n : 0, cPf = Pf ? cA : 0, cD = st * nd * n, cd = st * nd, c0 = sn * nx;
-  const size_t cU0 = sn * mb, cI = sn * MQ_INFO, cS = sn * T, cX = X ? sn * (T + 1) * nx : 0, cU = U ? sn * T * mb : 0, ch = hres ? cS : 0;
-  const size_t cXo = Xol ? sn * (N + 1) * nx : 0, cUo = Uol ? sn * N * mb : 0, cL = Lam ? sn * N * nd : 0;
-  const size_t cN = ndcnt ? (st + 1) / 2 : 0, cit = iters ? (cS + 1) / 2 : 0, cna = nact ? (cS + 1) / 2 : 0;       // int32, counted in doubles
-  HIPCHK(g_mpc_qp_scratch.reserve((cA + cB + cH + cq + cPf + cD + cd + 2 * c0 + cU0 + cI + cX + cU + ch + cXo + cUo + cL + cN + cit + cna + 1) * 8));
-  double* dA = (double*)g_mpc_qp_scratch.p; double* dB = dA + cA; double* dH = dB + cB; double* dq = dH + cH; double* dPf = dq + cq; double* dD = dPf + cPf;
-  double* dd = dD + cD; double* d0 = dd + cd; double* dU0 = d0 + c0; double* dXT = dU0 + cU0; double* dI = dXT + c0; double* dX = dI + cI; double* dU = dX + cX;
-  double* dh = dU + cU; double* dXo = dh + ch; double* dUo = dXo + cXo; double* dL = dUo + cUo;
-  int32_t* dN = (int32_t*)(dL + cL); int32_t* dit = (int32_t*)((double*)dN + cN); int32_t* dna = (int32_t*)((double*)dit + cit);
-  HIPCHK(hipMemcpy(dA, A, cA * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dB, B, cB * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dH, H, cH * 8, hipMemcpyHostToDevice));
-  if (q) HIPCHK(hipMemcpy(dq, q, cq * 8, hipMemcpyHostToDevice));
-  if (Pf) HIPCHK(hipMemcpy(dPf, Pf, cPf * 8, hipMemcpyHostToDevice));
-  if (D) HIPCHK(hipMemcpy(dD, D, cD * 8, hipMemcpyHostToDevice));
-  if (d) HIPCHK(hipMemcpy(dd, d, cd * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(d0, X0, c0 * 8, hipMemcpyHostToDevice));
-  if (ndcnt) HIPCHK(hipMemcpy(dN, ndcnt, st * sizeof(int32_t), hipMemcpyHostToDevice));
-  const int rl = mpc_qp_launch(nb, p, nx, mb, nd, N, ns, T, k0, dA, dB, dH, q ? dq : nullptr, Pf ? dPf : nullptr, D ? dD : nullptr, ndcnt ? dN : nullptr,
-                               d ? dd : nullptr, d0, tol, max_iter, dU0, dXT, dI, X ? dX : nullptr, U ? dU : nullptr, iters ? dit : nullptr,
-                               nact ? dna : nullptr, hres ? dh : nullptr, Xol ? dXo : nullptr, Uol ? dUo : nullptr, Lam ? dL : nullptr);
-  if (rl != TMPC_OK) return rl;
-  HIPCHK(hipMemcpy(U0, dU0, cU0 * 8, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(XT, dXT, c0 * 8, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(info, dI, cI * 8, hipMemcpyDeviceToHost));
-  if (X) HIPCHK(hipMemcpy(X, dX, cX * 8, hipMemcpyDeviceToHost));
-  if (U) HIPCHK(hipMemcpy(U, dU, cU * 8, hipMemcpyDeviceToHost));
-  if (hres) HIPCHK(hipMemcpy(hres, dh, cS * 8, hipMemcpyDeviceToHost));
-  if (Xol) HIPCHK(hipMemcpy(Xol, dXo, cXo * 8, hipMemcpyDeviceToHost));
-  if (Uol) HIPCHK(hipMemcpy(Uol, dUo, cUo * 8, hipMemcpyDeviceToHost));
-  if (Lam && cL) HIPCHK(hipMemcpy(Lam, dL, cL * 8, hipMemcpyDeviceToHost));
-  if (iters) HIPCHK(hipMemcpy(iters, dit, cS * sizeof(int32_t), hipMemcpyDeviceToHost));
-  if (nact) HIPCHK(hipMemcpy(nact, dna, cS * sizeof(int32_t), hipMemcpyDeviceToHost));
-  return TMPC_OK;
-}
-
-// The same entries with soft rows (tmpc_mpc_qp.h, the SOFT instantiation).  penalty NULL: the hard kernel, Eol and nviol zero.
-static int mpc_qp_soft_check(const char* who, int nx, int mb, int nd, int N, const void* penalty) {
-  if (!penalty) return TMPC_OK;
-  if (nd < 1) {
+  // soft rows
+  if (k.soft && nd < 1) {
     snprintf(g_err, sizeof(g_err), "%s: bad argument (penalty describes the rows of D; got nd = %d)", who, nd);
     return TMPC_E_ARG;
   }
-  const long long bytes = (long long)mpc_qp_soft_lds(nx, mb, nd).total * (long long)sizeof(double);
-  if (bytes > LQR_LDS_BYTES) {
-    snprintf(g_err, sizeof(g_err), "%s: nx = %d, nu = %d with room for %d soft rows per stage needs %lld bytes of LDS (limit %d)", who, nx, mb, nd, bytes, LQR_LDS_BYTES);
+  if (k.lds_soft * 8 > LQR_LDS_BYTES) {
+    snprintf(g_err, sizeof(g_err), "%s: nx = %d, nu = %d with room for %d soft rows per stage needs %lld bytes of LDS (limit %d)", who, nx, mb, nd, k.lds_soft * 8,
+             LQR_LDS_BYTES);
     return TMPC_E_UNSUPPORTED;
   }
+  // equality rows and terminal rows
+  if (ne < 0 || ((ne > 0) != (c.J != nullptr)) || ((c.r || c.necnt) && !c.J)) {
+    snprintf(g_err, sizeof(g_err), "%s: bad argument (J non-null exactly when ne > 0, the equality-row capacity per stage; r and necnt only with J; got ne = %d)",
+             who, ne);
+    return TMPC_E_ARG;
+  }
+  if (nt < -1 || (nt == -1 && c.Tx) || (nt > 0 && !c.Tx) || (nt == 0 && c.Tx)) {
+    snprintf(g_err, sizeof(g_err), "%s: bad argument (nt = -1: x_N = 0 without Tx; nt = 0: no terminal rows, Tx null; nt > 0: Tx [nb][p][nt][nx]; got nt = %d)",
+             who, nt);
+    return TMPC_E_ARG;
+  }
+  if (nt > nx) {
+    snprintf(g_err, sizeof(g_err), "%s: at most nx = %d terminal rows (got nt = %d)", who, nx, nt);
+    return TMPC_E_UNSUPPORTED;
+  }
+  if (k.lds * 8 > LQR_LDS_BYTES) {
+    snprintf(g_err, sizeof(g_err), "%s: nx = %d, nu = %d with room for %d %srows and %d equality rows per stage needs %lld bytes of LDS (limit %d)", who, nx, mb,
+             nd, k.soft ? "soft " : "", ne, k.lds * 8, LQR_LDS_BYTES);
+    return TMPC_E_UNSUPPORTED;
+  }
+  if ((long long)N * ne > 0x7fffffffLL / 4) {
+    snprintf(g_err, sizeof(g_err), "%s: horizon N = %d too long for %d equality rows per stage (32-bit indices inside a slot)", who, N, ne);
+    return TMPC_E_UNSUPPORTED;
+  }
+  // the affine arrays: terminal_rhs needs terminal rows, Ap and Bp come together
+  if (c.aff.t && nt == 0) {
+    snprintf(g_err, sizeof(g_err), "%s: bad argument (terminal_rhs describes the terminal rows; got nt = 0)", who);
+    return TMPC_E_ARG;
+  }
+  if ((c.aff.Ap != nullptr) != (c.aff.Bp != nullptr)) {
+    snprintf(g_err, sizeof(g_err), "%s: bad argument (the plant's Ap and Bp come together; got %s without %s)", who, c.aff.Ap ? "Ap" : "Bp", c.aff.Ap ? "Bp" : "Ap");
+    return TMPC_E_ARG;
+  }
+  *kind = k;
   return TMPC_OK;
 }
 
@@ -2342,250 +2312,143 @@ static int mpc_qp_host_ranges(const char* who, size_t nb, size_t p, const int32_
   return TMPC_OK;
 }
 
+// The outputs that the kernel of a call does not write -- Eol and nviol without SOFT, eres without EQ; Nu and NuT are empty then -- are zero by the header:
+// zero(pointer, bytes) on each that is given; mpc_qp_kernel_call takes them out of the record that the kernel gets.
+static int mpc_qp_zero_unwritten(const MpcQpCall& c, const MpcQpKind& k, hipError_t (*zero)(void*, size_t)) {
+  const size_t sn = (size_t)c.nb * c.ns;
+  if (!k.soft && c.Eol && c.nd > 0) HIPCHK(zero(c.Eol, sn * c.N * c.nd * 8));
+  if (!k.soft && c.nviol) HIPCHK(zero(c.nviol, sn * c.T * sizeof(int32_t)));
+  if (!k.eq && c.eres) HIPCHK(zero(c.eres, sn * c.T * 8));
+  return TMPC_OK;
+}
+static MpcQpCall mpc_qp_kernel_call(MpcQpCall c, const MpcQpKind& k) {
+  if (!k.soft) { c.Eol = nullptr; c.nviol = nullptr; }
+  if (!k.eq) { c.Nu = nullptr; c.NuT = nullptr; c.eres = nullptr; }
+  return c;
+}
+
+static thread_local EigScratch g_mpc_qp_ws;           // workspace slots of all entries, kept between calls and grown on demand
+
+// c: a checked call of mpc_qp_kernel_call with device pointers
+static int mpc_qp_launch(const MpcQpCall& c, const MpcQpKind& k) {
+  using Kernel = decltype(&k_mpc_qp<false, false, false>);
+  static const Kernel kernels[3][2] = {{k_mpc_qp<false, false, false>, k_mpc_qp<true, false, false>},      // [eq + aff][soft]
+                                       {k_mpc_qp<false, true, false>, k_mpc_qp<true, true, false>},
+                                       {k_mpc_qp<false, true, true>, k_mpc_qp<true, true, true>}};
+  const Kernel kern = kernels[(int)k.eq + (int)k.aff][(int)k.soft];
+  const long long ninst = (long long)c.nb * c.ns, per = k.ws * 8;
+  long long slots = ninst < MQ_SLOTS ? ninst : MQ_SLOTS;
+  if (slots * per > MQ_WS_CAP_BYTES) slots = MQ_WS_CAP_BYTES / per;
+  if (slots < 1) slots = 1;
+  HIPCHK(g_mpc_qp_ws.reserve((size_t)(slots * per)));
+  HIPCHK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LQR_LDS_BYTES));
+  int lcw = 0;
+  while ((1 << lcw) < c.nx + c.mb) ++lcw;
+  hipLaunchKernelGGL(kern, dim3((unsigned)slots), dim3(LQR_NT), (size_t)k.lds * sizeof(double), 0, c.p, c.nx, c.mb, c.nd, lcw, c.N, c.ns, c.T, c.k0, ninst, c.A, c.B,
+                     c.H, c.q, c.Pf, c.D, (const int*)c.ndcnt, c.d, c.X0, c.tol, c.max_iter, (double*)g_mpc_qp_ws.p, c.U0, c.XT, c.info, c.X, c.U, (int*)c.iters,
+                     (int*)c.nact, c.hres, c.Xol, c.Uol, c.Lam, c.penalty, c.Eol, (int*)c.nviol, c.ne, c.J, c.r, (const int*)c.necnt, c.ntk(), c.Tx, c.Nu, c.NuT,
+                     c.eres, c.aff);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(0));
+  return TMPC_OK;
+}
+
+// The device entries: the fills run on the null stream ahead of the kernel.
+static int mpc_qp_device(const MpcQpCall& c) {
+  MpcQpKind k;
+  int rc = mpc_qp_validate(c, &k);
+  if (rc == TMPC_OK) rc = mpc_qp_zero_unwritten(c, k, [](void* p, size_t bytes) { return hipMemsetAsync(p, 0, bytes, 0); });
+  if (rc != TMPC_OK) return rc;
+  return mpc_qp_launch(mpc_qp_kernel_call(c, k), k);
+}
+
+static thread_local EigScratch g_mpc_qp_scratch;      // device images of the host entries, whichever is called: kept between calls and grown on demand
+
+// The host entries: the range checks that need the arrays come before the first HIP call; the fills follow the copies back.
+static int mpc_qp_host(const MpcQpCall& c) {
+  MpcQpKind k;
+  int rc = mpc_qp_validate(c, &k);
+  if (rc == TMPC_OK) rc = mpc_qp_host_ranges(c.who, c.nb, c.p, c.ndcnt, c.nd, "ndcnt", "nd", c.penalty, c.nd);
+  if (rc == TMPC_OK) rc = mpc_qp_host_ranges(c.who, c.nb, c.p, c.necnt, c.ne, "necnt", "ne", nullptr, 0);
+  if (rc != TMPC_OK) return rc;
+  // every array that is given and not empty gets an image in one device buffer, 8-byte aligned, in the order of the arguments; dc is the call on the images
+  // (null where there is none).  The list runs twice: for the size of the buffer, then, with the buffer, for the images.
+  MpcQpCall dc = mpc_qp_kernel_call(c, k);
+  struct Img { void* host; void* dev; size_t bytes; bool out; };
+  std::vector<Img> im;
+  char* base = nullptr;
+  size_t total = 0;
+  auto place = [&](auto*& m, size_t bytes, bool out) {
+    if (!m || !bytes) { m = nullptr; return; }
+    if (base) {
+      im.push_back(Img{(void*)m, base + total, bytes, out});
+      m = (std::remove_reference_t<decltype(m)>)(base + total);
+    }
+    total += (bytes + 7) / 8 * 8;
+  };
+  auto arrays = [&]() {
+    const size_t st = (size_t)c.nb * c.p, sn = (size_t)c.nb * c.ns, nx = c.nx, mb = c.mb, n = nx + mb, nd = c.nd, ne = c.ne, ntk = c.ntk(), N = c.N, cS = sn * c.T;
+    total = 0;
+    place(dc.A, st * nx * nx * 8, false); place(dc.B, st * nx * mb * 8, false); place(dc.H, st * n * n * 8, false); place(dc.q, st * n * 8, false);
+    place(dc.Pf, st * nx * nx * 8, false); place(dc.D, st * nd * n * 8, false); place(dc.ndcnt, st * sizeof(int32_t), false); place(dc.d, st * nd * 8, false);
+    place(dc.X0, sn * nx * 8, false);
+    place(dc.U0, sn * mb * 8, true); place(dc.XT, sn * nx * 8, true); place(dc.info, sn * MQ_INFO * 8, true); place(dc.X, sn * (c.T + 1) * nx * 8, true);
+    place(dc.U, cS * mb * 8, true); place(dc.iters, cS * sizeof(int32_t), true); place(dc.nact, cS * sizeof(int32_t), true); place(dc.hres, cS * 8, true);
+    place(dc.Xol, sn * (N + 1) * nx * 8, true); place(dc.Uol, sn * N * mb * 8, true); place(dc.Lam, sn * N * nd * 8, true);
+    place(dc.penalty, st * nd * 8, false); place(dc.Eol, sn * N * nd * 8, true); place(dc.nviol, cS * sizeof(int32_t), true);
+    place(dc.J, st * ne * n * 8, false); place(dc.r, st * ne * 8, false); place(dc.necnt, st * sizeof(int32_t), false); place(dc.Tx, st * ntk * nx * 8, false);
+    place(dc.Nu, sn * N * ne * 8, true); place(dc.NuT, sn * ntk * 8, true); place(dc.eres, cS * 8, true);
+    place(dc.aff.c, st * nx * 8, false); place(dc.aff.qf, st * nx * 8, false); place(dc.aff.t, st * ntk * 8, false); place(dc.aff.Ap, st * nx * nx * 8, false);
+    place(dc.aff.Bp, st * nx * mb * 8, false); place(dc.aff.cp, st * nx * 8, false); place(dc.aff.W, cS * nx * 8, false);
+  };
+  arrays();
+  HIPCHK(g_mpc_qp_scratch.reserve(total + 8));
+  base = (char*)g_mpc_qp_scratch.p;
+  arrays();
+  for (const Img& i : im) if (!i.out) HIPCHK(hipMemcpy(i.dev, i.host, i.bytes, hipMemcpyHostToDevice));
+  rc = mpc_qp_launch(dc, k);
+  if (rc != TMPC_OK) return rc;
+  for (const Img& i : im) if (i.out) HIPCHK(hipMemcpy(i.host, i.dev, i.bytes, hipMemcpyDeviceToHost));
+  return mpc_qp_zero_unwritten(c, k, [](void* p, size_t bytes) { memset(p, 0, bytes); return hipSuccess; });
+}
+
+int tmpc_mpc_qp_batch_device(int nb, int p, int nx, int mb, int nd, int N, int ns, int T, int k0, const double* A, const double* B, const double* H,
+                             const double* q, const double* Pf, const double* D, const int32_t* ndcnt, const double* d, const double* X0, double tol,
+                             int max_iter, double* U0, double* XT, double* info, double* X, double* U, int32_t* iters, int32_t* nact, double* hres, double* Xol,
+                             double* Uol, double* Lam) {
+  return mpc_qp_device(MpcQpCall{"tmpc_mpc_qp_batch_device", MPC_QP_ARGS31});
+}
+
+int tmpc_mpc_qp_batch_host(int nb, int p, int nx, int mb, int nd, int N, int ns, int T, int k0, const double* A, const double* B, const double* H,
+                           const double* q, const double* Pf, const double* D, const int32_t* ndcnt, const double* d, const double* X0, double tol, int max_iter,
+                           double* U0, double* XT, double* info, double* X, double* U, int32_t* iters, int32_t* nact, double* hres, double* Xol, double* Uol,
+                           double* Lam) {
+  return mpc_qp_host(MpcQpCall{"tmpc_mpc_qp_batch_host", MPC_QP_ARGS31});
+}
+
+// The same entries with soft rows (tmpc_mpc_qp.h, the SOFT instantiation).  penalty NULL: the hard kernel, Eol and nviol zero.
 int tmpc_mpc_qp_soft_batch_device(int nb, int p, int nx, int mb, int nd, int N, int ns, int T, int k0, const double* A, const double* B, const double* H,
                                   const double* q, const double* Pf, const double* D, const int32_t* ndcnt, const double* d, const double* X0, double tol,
                                   int max_iter, double* U0, double* XT, double* info, double* X, double* U, int32_t* iters, int32_t* nact, double* hres,
                                   double* Xol, double* Uol, double* Lam, const double* penalty, double* Eol, int32_t* nviol) {
-  const char* who = "tmpc_mpc_qp_soft_batch_device";
-  int rc = mpc_qp_check(who, nb, p, nx, mb, nd, N, ns, T, k0, A, B, H, D, ndcnt, d, X0, tol, max_iter, U0, XT, info);
-  if (rc == TMPC_OK) rc = mpc_qp_soft_check(who, nx, mb, nd, N, penalty);
-  if (rc != TMPC_OK) return rc;
-  if (!penalty) {
-    if (Eol && nd > 0) HIPCHK(hipMemsetAsync(Eol, 0, (size_t)nb * ns * N * nd * 8, 0));
-    if (nviol) HIPCHK(hipMemsetAsync(nviol, 0, (size_t)nb * T * ns * sizeof(int32_t), 0));
-  }
-  return mpc_qp_launch(nb, p, nx, mb, nd, N, ns, T, k0, A, B, H, q, Pf, D, ndcnt, d, X0, tol, max_iter, U0, XT, info, X, U, iters, nact, hres, Xol, Uol, Lam,
-                       penalty, penalty ? Eol : nullptr, penalty ? nviol : nullptr);
+  return mpc_qp_device(MpcQpCall{"tmpc_mpc_qp_soft_batch_device", MPC_QP_ARGS31, penalty, Eol, nviol});
 }
-
-static thread_local EigScratch g_mpc_qp_soft_scratch;      // device images of penalty | Eol | nviol of the host entry
 
 int tmpc_mpc_qp_soft_batch_host(int nb, int p, int nx, int mb, int nd, int N, int ns, int T, int k0, const double* A, const double* B, const double* H,
                                 const double* q, const double* Pf, const double* D, const int32_t* ndcnt, const double* d, const double* X0, double tol,
                                 int max_iter, double* U0, double* XT, double* info, double* X, double* U, int32_t* iters, int32_t* nact, double* hres, double* Xol,
                                 double* Uol, double* Lam, const double* penalty, double* Eol, int32_t* nviol) {
-  const char* who = "tmpc_mpc_qp_soft_batch_host";
-  if (!penalty) {                                                            // the hard entry; no slack, no violated row
-    const int rc = tmpc_mpc_qp_batch_host(nb, p, nx, mb, nd, N, ns, T, k0, A, B, H, q, Pf, D, ndcnt, d, X0, tol, max_iter, U0, XT, info, X, U, iters, nact, hres,
-                                          Xol, Uol, Lam);
-    if (rc != TMPC_OK) return rc;
-    if (Eol) for (size_t i = 0; i < (size_t)nb * ns * N * nd; ++i) Eol[i] = 0.0;
-    if (nviol) for (size_t i = 0; i < (size_t)nb * T * ns; ++i) nviol[i] = 0;
-    return TMPC_OK;
-  }
-  int rc = mpc_qp_check(who, nb, p, nx, mb, nd, N, ns, T, k0, A, B, H, D, ndcnt, d, X0, tol, max_iter, U0, XT, info);
-  if (rc == TMPC_OK) rc = mpc_qp_soft_check(who, nx, mb, nd, N, penalty);
-  if (rc != TMPC_OK) return rc;
-  const size_t st = (size_t)nb * p, sn = (size_t)nb * ns;
-  rc = mpc_qp_host_ranges(who, nb, p, ndcnt, nd, "ndcnt", "nd", penalty, nd);
-  if (rc != TMPC_OK) return rc;
-  // the inputs and outputs of the hard entry pass through device buffers of this entry: A | B | H | q | Pf | D | d | X0 | penalty, then the outputs
-  const size_t n = (size_t)nx + mb;
-  const size_t cA = st * nx * nx, cB = st * nx * mb, cH = st * n * n, cq = q ? st * n : 0, cPf = Pf ? cA : 0, cD = st * nd * n, cd = st * nd, c0 = sn * nx;
-  const size_t cU0 = sn * mb, cI = sn * MQ_INFO, cS = sn * T, cX = X ? sn * (T + 1) * nx : 0, cU = U ? sn * T * mb : 0, ch = hres ? cS : 0;
-  const size_t cXo = Xol ? sn * (N + 1) * nx : 0, cUo = Uol ? sn * N * mb : 0, cL = Lam ? sn * N * nd : 0, cE = Eol ? sn * N * nd : 0;
-  const size_t cN = ndcnt ? (st + 1) / 2 : 0, cit = iters ? (cS + 1) / 2 : 0, cna = nact ? (cS + 1) / 2 : 0, cnv = nviol ? (cS + 1) / 2 : 0;   // int32, in doubles
-  HIPCHK(g_mpc_qp_soft_scratch.reserve((cA + cB + cH + cq + cPf + cD + 2 * cd + 2 * c0 + cU0 + cI + cX + cU + ch + cXo + cUo + cL + cE + cN + cit + cna + cnv + 1) * 8));
-  double* dA = (double*)g_mpc_qp_soft_scratch.p; double* dB = dA + cA; double* dH = dB + cB; double* dq = dH + cH; double* dPf = dq + cq; double* dD = dPf + cPf;
-  double* dd = dD + cD; double* dP = dd + cd; double* d0 = dP + cd; double* dU0 = d0 + c0; double* dXT = dU0 + cU0; double* dI = dXT + c0; double* dX = dI + cI;
-  double* dU = dX + cX; double* dh = dU + cU; double* dXo = dh + ch; double* dUo = dXo + cXo; double* dL = dUo + cUo; double* dE = dL + cL;
-  int32_t* dN = (int32_t*)(dE + cE); int32_t* dit = (int32_t*)((double*)dN + cN); int32_t* dna = (int32_t*)((double*)dit + cit);
-  int32_t* dnv = (int32_t*)((double*)dna + cna);
-  HIPCHK(hipMemcpy(dA, A, cA * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dB, B, cB * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dH, H, cH * 8, hipMemcpyHostToDevice));
-  if (q) HIPCHK(hipMemcpy(dq, q, cq * 8, hipMemcpyHostToDevice));
-  if (Pf) HIPCHK(hipMemcpy(dPf, Pf, cPf * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dD, D, cD * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dd, d, cd * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dP, penalty, cd * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(d0, X0, c0 * 8, hipMemcpyHostToDevice));
-  if (ndcnt) HIPCHK(hipMemcpy(dN, ndcnt, st * sizeof(int32_t), hipMemcpyHostToDevice));
-  const int rl = mpc_qp_launch(nb, p, nx, mb, nd, N, ns, T, k0, dA, dB, dH, q ? dq : nullptr, Pf ? dPf : nullptr, dD, ndcnt ? dN : nullptr, dd, d0, tol, max_iter,
-                               dU0, dXT, dI, X ? dX : nullptr, U ? dU : nullptr, iters ? dit : nullptr, nact ? dna : nullptr, hres ? dh : nullptr,
-                               Xol ? dXo : nullptr, Uol ? dUo : nullptr, Lam ? dL : nullptr, dP, Eol ? dE : nullptr, nviol ? dnv : nullptr);
-  if (rl != TMPC_OK) return rl;
-  HIPCHK(hipMemcpy(U0, dU0, cU0 * 8, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(XT, dXT, c0 * 8, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(info, dI, cI * 8, hipMemcpyDeviceToHost));
-  if (X) HIPCHK(hipMemcpy(X, dX, cX * 8, hipMemcpyDeviceToHost));
-  if (U) HIPCHK(hipMemcpy(U, dU, cU * 8, hipMemcpyDeviceToHost));
-  if (hres) HIPCHK(hipMemcpy(hres, dh, cS * 8, hipMemcpyDeviceToHost));
-  if (Xol) HIPCHK(hipMemcpy(Xol, dXo, cXo * 8, hipMemcpyDeviceToHost));
-  if (Uol) HIPCHK(hipMemcpy(Uol, dUo, cUo * 8, hipMemcpyDeviceToHost));
-  if (Lam) HIPCHK(hipMemcpy(Lam, dL, cL * 8, hipMemcpyDeviceToHost));
-  if (Eol) HIPCHK(hipMemcpy(Eol, dE, cE * 8, hipMemcpyDeviceToHost));
-  if (iters) HIPCHK(hipMemcpy(iters, dit, cS * sizeof(int32_t), hipMemcpyDeviceToHost));
-  if (nact) HIPCHK(hipMemcpy(nact, dna, cS * sizeof(int32_t), hipMemcpyDeviceToHost));
-  if (nviol) HIPCHK(hipMemcpy(nviol, dnv, cS * sizeof(int32_t), hipMemcpyDeviceToHost));
-  return TMPC_OK;
+  return mpc_qp_host(MpcQpCall{"tmpc_mpc_qp_soft_batch_host", MPC_QP_ARGS31, penalty, Eol, nviol});
 }
 
 // The same entries with equality rows J z = r at every stage and terminal rows Tx x_N = 0 (tmpc_mpc_qp.h, the EQ instantiations).  ne = 0 and nt = 0: the
-// entries above, Nu and NuT empty, eres zero.
-static int mpc_qp_eq_check(const char* who, int nx, int mb, int nd, int N, bool soft, int ne, const void* J, const void* r, const void* necnt, int nt,
-                           const void* Tx) {
-  if (ne < 0 || ((ne > 0) != (J != nullptr)) || ((r || necnt) && !J)) {
-    snprintf(g_err, sizeof(g_err), "%s: bad argument (J non-null exactly when ne > 0, the equality-row capacity per stage; r and necnt only with J; got ne = %d)",
-             who, ne);
-    return TMPC_E_ARG;
-  }
-  if (nt < -1 || (nt == -1 && Tx) || (nt > 0 && !Tx) || (nt == 0 && Tx)) {
-    snprintf(g_err, sizeof(g_err), "%s: bad argument (nt = -1: x_N = 0 without Tx; nt = 0: no terminal rows, Tx null; nt > 0: Tx [nb][p][nt][nx]; got nt = %d)",
-             who, nt);
-    return TMPC_E_ARG;
-  }
-  if (nt > nx) {
-    snprintf(g_err, sizeof(g_err), "%s: at most nx = %d terminal rows (got nt = %d)", who, nx, nt);
-    return TMPC_E_UNSUPPORTED;
-  }
-  const long long bytes = (long long)mpc_qp_eq_lds(nx, mb, nd, ne < 65536 ? ne : 65536, soft).total * (long long)sizeof(double);
-  if (bytes > LQR_LDS_BYTES) {
-    snprintf(g_err, sizeof(g_err), "%s: nx = %d, nu = %d with room for %d %srows and %d equality rows per stage needs %lld bytes of LDS (limit %d)", who, nx, mb,
-             nd, soft ? "soft " : "", ne, bytes, LQR_LDS_BYTES);
-    return TMPC_E_UNSUPPORTED;
-  }
-  if ((long long)N * ne > 0x7fffffffLL / 4) {
-    snprintf(g_err, sizeof(g_err), "%s: horizon N = %d too long for %d equality rows per stage (32-bit indices inside a slot)", who, N, ne);
-    return TMPC_E_UNSUPPORTED;
-  }
-  return TMPC_OK;
-}
-
-// The arguments of the AFF instantiations (tmpc_mpc_qp.h): terminal_rhs needs terminal rows, Ap and Bp come together.  aff null or all seven null: no check.
-static bool mpc_qp_aff_any(const MpcQpAff* a) { return a && (a->c || a->qf || a->t || a->Ap || a->Bp || a->cp || a->W); }
-static int mpc_qp_aff_check(const char* who, int nt, const MpcQpAff* a) {
-  if (!mpc_qp_aff_any(a)) return TMPC_OK;
-  if (a->t && nt == 0) {
-    snprintf(g_err, sizeof(g_err), "%s: bad argument (terminal_rhs describes the terminal rows; got nt = 0)", who);
-    return TMPC_E_ARG;
-  }
-  if ((a->Ap != nullptr) != (a->Bp != nullptr)) {
-    snprintf(g_err, sizeof(g_err), "%s: bad argument (the plant's Ap and Bp come together; got %s without %s)", who, a->Ap ? "Ap" : "Bp", a->Ap ? "Bp" : "Ap");
-    return TMPC_E_ARG;
-  }
-  return TMPC_OK;
-}
-
-// Both eq entries and both aff entries: aff null or all seven null is the eq entry, statement by statement.
-static int mpc_qp_eq_device(const char* who, int nb, int p, int nx, int mb, int nd, int N, int ns, int T, int k0, const double* A, const double* B, const double* H,
-                            const double* q, const double* Pf, const double* D, const int32_t* ndcnt, const double* d, const double* X0, double tol,
-                            int max_iter, double* U0, double* XT, double* info, double* X, double* U, int32_t* iters, int32_t* nact, double* hres,
-                            double* Xol, double* Uol, double* Lam, const double* penalty, double* Eol, int32_t* nviol, int ne, const double* J,
-                            const double* r, const int32_t* necnt, int nt, const double* Tx, double* Nu, double* NuT, double* eres, const MpcQpAff* aff) {
-  int rc = mpc_qp_check(who, nb, p, nx, mb, nd, N, ns, T, k0, A, B, H, D, ndcnt, d, X0, tol, max_iter, U0, XT, info);
-  if (rc == TMPC_OK) rc = mpc_qp_soft_check(who, nx, mb, nd, N, penalty);
-  if (rc == TMPC_OK) rc = mpc_qp_eq_check(who, nx, mb, nd, N, penalty != nullptr, ne, J, r, necnt, nt, Tx);
-  if (rc == TMPC_OK) rc = mpc_qp_aff_check(who, nt, aff);
-  if (rc != TMPC_OK) return rc;
-  if (!mpc_qp_aff_any(aff)) aff = nullptr;
-  if (ne == 0 && nt == 0 && !aff) {
-    if (eres) HIPCHK(hipMemsetAsync(eres, 0, (size_t)nb * T * ns * 8, 0));
-    return tmpc_mpc_qp_soft_batch_device(nb, p, nx, mb, nd, N, ns, T, k0, A, B, H, q, Pf, D, ndcnt, d, X0, tol, max_iter, U0, XT, info, X, U, iters, nact, hres,
-                                         Xol, Uol, Lam, penalty, Eol, nviol);
-  }
-  if (!penalty) {
-    if (Eol && nd > 0) HIPCHK(hipMemsetAsync(Eol, 0, (size_t)nb * ns * N * nd * 8, 0));
-    if (nviol) HIPCHK(hipMemsetAsync(nviol, 0, (size_t)nb * T * ns * sizeof(int32_t), 0));
-  }
-  MpcQpEqArgs e;
-  e.ne = ne; e.J = J; e.r = r; e.necnt = necnt; e.nt = nt < 0 ? nx : nt; e.Tx = Tx; e.Nu = Nu; e.NuT = NuT; e.eres = eres;
-  return mpc_qp_launch(nb, p, nx, mb, nd, N, ns, T, k0, A, B, H, q, Pf, D, ndcnt, d, X0, tol, max_iter, U0, XT, info, X, U, iters, nact, hres, Xol, Uol, Lam,
-                       penalty, penalty ? Eol : nullptr, penalty ? nviol : nullptr, &e, aff);
-}
-
+// kernel of the entries above (the same bits), Nu and NuT empty, eres zero.
 int tmpc_mpc_qp_eq_batch_device(int nb, int p, int nx, int mb, int nd, int N, int ns, int T, int k0, const double* A, const double* B, const double* H,
                                 const double* q, const double* Pf, const double* D, const int32_t* ndcnt, const double* d, const double* X0, double tol,
                                 int max_iter, double* U0, double* XT, double* info, double* X, double* U, int32_t* iters, int32_t* nact, double* hres,
                                 double* Xol, double* Uol, double* Lam, const double* penalty, double* Eol, int32_t* nviol, int ne, const double* J,
                                 const double* r, const int32_t* necnt, int nt, const double* Tx, double* Nu, double* NuT, double* eres) {
-  return mpc_qp_eq_device("tmpc_mpc_qp_eq_batch_device", nb, p, nx, mb, nd, N, ns, T, k0, A, B, H, q, Pf, D, ndcnt, d, X0, tol, max_iter, U0, XT, info, X, U, iters,
-                          nact, hres, Xol, Uol, Lam, penalty, Eol, nviol, ne, J, r, necnt, nt, Tx, Nu, NuT, eres, nullptr);
-}
-
-int tmpc_mpc_qp_aff_batch_device(int nb, int p, int nx, int mb, int nd, int N, int ns, int T, int k0, const double* A, const double* B, const double* H,
-                                 const double* q, const double* Pf, const double* D, const int32_t* ndcnt, const double* d, const double* X0, double tol,
-                                 int max_iter, double* U0, double* XT, double* info, double* X, double* U, int32_t* iters, int32_t* nact, double* hres,
-                                 double* Xol, double* Uol, double* Lam, const double* penalty, double* Eol, int32_t* nviol, int ne, const double* J,
-                                 const double* r, const int32_t* necnt, int nt, const double* Tx, double* Nu, double* NuT, double* eres, const double* offset,
-                                 const double* qf, const double* terminal_rhs, const double* Ap, const double* Bp, const double* cp, const double* W) {
-  const MpcQpAff aff = {offset, qf, terminal_rhs, Ap, Bp, cp, W};
-  return mpc_qp_eq_device("tmpc_mpc_qp_aff_batch_device", nb, p, nx, mb, nd, N, ns, T, k0, A, B, H, q, Pf, D, ndcnt, d, X0, tol, max_iter, U0, XT, info, X, U, iters,
-                          nact, hres, Xol, Uol, Lam, penalty, Eol, nviol, ne, J, r, necnt, nt, Tx, Nu, NuT, eres, &aff);
-}
-
-static thread_local EigScratch g_mpc_qp_eq_scratch;      // device images of the host entry with equality rows
-
-// (aff: HOST pointers here)
-static int mpc_qp_eq_host(const char* who, int nb, int p, int nx, int mb, int nd, int N, int ns, int T, int k0, const double* A, const double* B, const double* H,
-                          const double* q, const double* Pf, const double* D, const int32_t* ndcnt, const double* d, const double* X0, double tol,
-                          int max_iter, double* U0, double* XT, double* info, double* X, double* U, int32_t* iters, int32_t* nact, double* hres,
-                          double* Xol, double* Uol, double* Lam, const double* penalty, double* Eol, int32_t* nviol, int ne, const double* J,
-                          const double* r, const int32_t* necnt, int nt, const double* Tx, double* Nu, double* NuT, double* eres, const MpcQpAff* aff) {
-  int rc = mpc_qp_check(who, nb, p, nx, mb, nd, N, ns, T, k0, A, B, H, D, ndcnt, d, X0, tol, max_iter, U0, XT, info);
-  if (rc == TMPC_OK) rc = mpc_qp_soft_check(who, nx, mb, nd, N, penalty);
-  if (rc == TMPC_OK) rc = mpc_qp_eq_check(who, nx, mb, nd, N, penalty != nullptr, ne, J, r, necnt, nt, Tx);
-  if (rc == TMPC_OK) rc = mpc_qp_aff_check(who, nt, aff);
-  if (rc != TMPC_OK) return rc;
-  if (!mpc_qp_aff_any(aff)) aff = nullptr;
-  const size_t st = (size_t)nb * p, sn = (size_t)nb * ns, n = (size_t)nx + mb, cS = sn * T;
-  if (ne == 0 && nt == 0 && !aff) {
-    rc = tmpc_mpc_qp_soft_batch_host(nb, p, nx, mb, nd, N, ns, T, k0, A, B, H, q, Pf, D, ndcnt, d, X0, tol, max_iter, U0, XT, info, X, U, iters, nact, hres, Xol,
-                                     Uol, Lam, penalty, Eol, nviol);
-    if (rc != TMPC_OK) return rc;
-    if (eres) for (size_t i = 0; i < cS; ++i) eres[i] = 0.0;
-    return TMPC_OK;
-  }
-  rc = mpc_qp_host_ranges(who, nb, p, ndcnt, nd, "ndcnt", "nd", penalty, nd);
-  if (rc == TMPC_OK) rc = mpc_qp_host_ranges(who, nb, p, necnt, ne, "necnt", "ne", nullptr, 0);
-  if (rc != TMPC_OK) return rc;
-  const int ntk = nt < 0 ? nx : nt;
-  // every array passes through one device buffer: (host pointer, bytes, input?) in the order of the arguments, each image 8-byte aligned
-  struct Img { const void* in; void* out; size_t bytes; size_t off; };
-  std::vector<Img> im;
-  size_t total = 0;
-  auto add = [&](const void* in, void* out, size_t bytes) {
-    const bool on = (in || out) && bytes > 0;
-    im.push_back(Img{on ? in : nullptr, on ? out : nullptr, on ? bytes : 0, total});
-    if (on) total += (bytes + 7) / 8 * 8;
-    return (int)im.size() - 1;
-  };
-  const int iA = add(A, nullptr, st * nx * nx * 8), iB = add(B, nullptr, st * nx * mb * 8), iH = add(H, nullptr, st * n * n * 8), iq = add(q, nullptr, st * n * 8);
-  const int iPf = add(Pf, nullptr, st * nx * nx * 8), iD = add(D, nullptr, st * nd * n * 8), icnt = add(ndcnt, nullptr, st * sizeof(int32_t));
-  const int id = add(d, nullptr, st * nd * 8), i0 = add(X0, nullptr, sn * nx * 8), ipen = add(penalty, nullptr, st * nd * 8);
-  const int iJ = add(J, nullptr, st * ne * n * 8), ir = add(r, nullptr, st * ne * 8), iec = add(necnt, nullptr, st * sizeof(int32_t));
-  const int iTx = add(Tx, nullptr, st * ntk * nx * 8);
-  const int oU0 = add(nullptr, U0, sn * mb * 8), oXT = add(nullptr, XT, sn * nx * 8), oI = add(nullptr, info, sn * MQ_INFO * 8);
-  const int oX = add(nullptr, X, sn * (T + 1) * nx * 8), oU = add(nullptr, U, cS * mb * 8), oit = add(nullptr, iters, cS * sizeof(int32_t));
-  const int ona = add(nullptr, nact, cS * sizeof(int32_t)), oh = add(nullptr, hres, cS * 8), oXo = add(nullptr, Xol, sn * (N + 1) * nx * 8);
-  const int oUo = add(nullptr, Uol, sn * N * mb * 8), oL = add(nullptr, Lam, sn * N * nd * 8), oE = add(nullptr, penalty ? Eol : nullptr, sn * N * nd * 8);
-  const int onv = add(nullptr, penalty ? nviol : nullptr, cS * sizeof(int32_t)), oNu = add(nullptr, Nu, sn * N * ne * 8), oNT = add(nullptr, NuT, sn * ntk * 8);
-  const int oer = add(nullptr, eres, cS * 8);
-  const int ic = add(aff ? aff->c : nullptr, nullptr, st * nx * 8), iqf = add(aff ? aff->qf : nullptr, nullptr, st * nx * 8);
-  const int itr = add(aff ? aff->t : nullptr, nullptr, st * ntk * 8), iAp = add(aff ? aff->Ap : nullptr, nullptr, st * nx * nx * 8);
-  const int iBp = add(aff ? aff->Bp : nullptr, nullptr, st * nx * mb * 8), icp = add(aff ? aff->cp : nullptr, nullptr, st * nx * 8);
-  const int iW = add(aff ? aff->W : nullptr, nullptr, cS * nx * 8);
-  HIPCHK(g_mpc_qp_eq_scratch.reserve(total + 8));
-  char* base = (char*)g_mpc_qp_eq_scratch.p;
-  auto dev = [&](int i) -> void* { return im[i].bytes ? base + im[i].off : nullptr; };
-  for (int i = 0; i < (int)im.size(); ++i) if (im[i].in) HIPCHK(hipMemcpy(dev(i), im[i].in, im[i].bytes, hipMemcpyHostToDevice));
-  MpcQpEqArgs e;
-  e.ne = ne; e.J = (const double*)dev(iJ); e.r = (const double*)dev(ir); e.necnt = (const int32_t*)dev(iec); e.nt = ntk; e.Tx = (const double*)dev(iTx);
-  e.Nu = (double*)dev(oNu); e.NuT = (double*)dev(oNT); e.eres = (double*)dev(oer);
-  const MpcQpAff daff = {(const double*)dev(ic), (const double*)dev(iqf), (const double*)dev(itr), (const double*)dev(iAp), (const double*)dev(iBp),
-                         (const double*)dev(icp), (const double*)dev(iW)};
-  const int rl = mpc_qp_launch(nb, p, nx, mb, nd, N, ns, T, k0, (const double*)dev(iA), (const double*)dev(iB), (const double*)dev(iH), (const double*)dev(iq),
-                               (const double*)dev(iPf), (const double*)dev(iD), (const int32_t*)dev(icnt), (const double*)dev(id), (const double*)dev(i0), tol,
-                               max_iter, (double*)dev(oU0), (double*)dev(oXT), (double*)dev(oI), (double*)dev(oX), (double*)dev(oU), (int32_t*)dev(oit),
-                               (int32_t*)dev(ona), (double*)dev(oh), (double*)dev(oXo), (double*)dev(oUo), (double*)dev(oL), (const double*)dev(ipen),
-                               (double*)dev(oE), (int32_t*)dev(onv), &e, aff ? &daff : nullptr);
-  if (rl != TMPC_OK) return rl;
-  for (int i = 0; i < (int)im.size(); ++i) if (im[i].out) HIPCHK(hipMemcpy(im[i].out, dev(i), im[i].bytes, hipMemcpyDeviceToHost));
-  if (!penalty) {
-    if (Eol) for (size_t i = 0; i < sn * N * nd; ++i) Eol[i] = 0.0;
-    if (nviol) for (size_t i = 0; i < cS; ++i) nviol[i] = 0;
-  }
-  return TMPC_OK;
+  return mpc_qp_device(MpcQpCall{"tmpc_mpc_qp_eq_batch_device", MPC_QP_ARGS31, penalty, Eol, nviol, ne, J, r, necnt, nt, Tx, Nu, NuT, eres});
 }
 
 int tmpc_mpc_qp_eq_batch_host(int nb, int p, int nx, int mb, int nd, int N, int ns, int T, int k0, const double* A, const double* B, const double* H,
@@ -2593,22 +2456,31 @@ int tmpc_mpc_qp_eq_batch_host(int nb, int p, int nx, int mb, int nd, int N, int 
                               int max_iter, double* U0, double* XT, double* info, double* X, double* U, int32_t* iters, int32_t* nact, double* hres,
                               double* Xol, double* Uol, double* Lam, const double* penalty, double* Eol, int32_t* nviol, int ne, const double* J,
                               const double* r, const int32_t* necnt, int nt, const double* Tx, double* Nu, double* NuT, double* eres) {
-  return mpc_qp_eq_host("tmpc_mpc_qp_eq_batch_host", nb, p, nx, mb, nd, N, ns, T, k0, A, B, H, q, Pf, D, ndcnt, d, X0, tol, max_iter, U0, XT, info, X, U, iters, nact,
-                        hres, Xol, Uol, Lam, penalty, Eol, nviol, ne, J, r, necnt, nt, Tx, Nu, NuT, eres, nullptr);
+  return mpc_qp_host(MpcQpCall{"tmpc_mpc_qp_eq_batch_host", MPC_QP_ARGS31, penalty, Eol, nviol, ne, J, r, necnt, nt, Tx, Nu, NuT, eres});
 }
 
 // The affine problem (tmpc_mpc_qp.h, the AFF instantiations): the 43 arguments of the eq entries, then offset, qf, terminal_rhs, Ap, Bp, cp, W.  All seven
-// NULL: the eq entry.
+// NULL: the kernel of the eq entry with the same arguments (the same bits).
+int tmpc_mpc_qp_aff_batch_device(int nb, int p, int nx, int mb, int nd, int N, int ns, int T, int k0, const double* A, const double* B, const double* H,
+                                 const double* q, const double* Pf, const double* D, const int32_t* ndcnt, const double* d, const double* X0, double tol,
+                                 int max_iter, double* U0, double* XT, double* info, double* X, double* U, int32_t* iters, int32_t* nact, double* hres,
+                                 double* Xol, double* Uol, double* Lam, const double* penalty, double* Eol, int32_t* nviol, int ne, const double* J,
+                                 const double* r, const int32_t* necnt, int nt, const double* Tx, double* Nu, double* NuT, double* eres, const double* offset,
+                                 const double* qf, const double* terminal_rhs, const double* Ap, const double* Bp, const double* cp, const double* W) {
+  return mpc_qp_device(MpcQpCall{"tmpc_mpc_qp_aff_batch_device", MPC_QP_ARGS31, penalty, Eol, nviol, ne, J, r, necnt, nt, Tx, Nu, NuT, eres,
+                                 {offset, qf, terminal_rhs, Ap, Bp, cp, W}});
+}
+
 int tmpc_mpc_qp_aff_batch_host(int nb, int p, int nx, int mb, int nd, int N, int ns, int T, int k0, const double* A, const double* B, const double* H,
                                const double* q, const double* Pf, const double* D, const int32_t* ndcnt, const double* d, const double* X0, double tol,
                                int max_iter, double* U0, double* XT, double* info, double* X, double* U, int32_t* iters, int32_t* nact, double* hres,
                                double* Xol, double* Uol, double* Lam, const double* penalty, double* Eol, int32_t* nviol, int ne, const double* J,
                                const double* r, const int32_t* necnt, int nt, const double* Tx, double* Nu, double* NuT, double* eres, const double* offset,
                                const double* qf, const double* terminal_rhs, const double* Ap, const double* Bp, const double* cp, const double* W) {
-  const MpcQpAff aff = {offset, qf, terminal_rhs, Ap, Bp, cp, W};
-  return mpc_qp_eq_host("tmpc_mpc_qp_aff_batch_host", nb, p, nx, mb, nd, N, ns, T, k0, A, B, H, q, Pf, D, ndcnt, d, X0, tol, max_iter, U0, XT, info, X, U, iters, nact,
-                        hres, Xol, Uol, Lam, penalty, Eol, nviol, ne, J, r, necnt, nt, Tx, Nu, NuT, eres, &aff);
+  return mpc_qp_host(MpcQpCall{"tmpc_mpc_qp_aff_batch_host", MPC_QP_ARGS31, penalty, Eol, nviol, ne, J, r, necnt, nt, Tx, Nu, NuT, eres,
+                               {offset, qf, terminal_rhs, Ap, Bp, cp, W}});
 }
+#undef MPC_QP_ARGS31
 
 int tmpc_tracking_reference_host(tmpc_handle* h, int nstage, const double* Hc, const double* q, const double* wref,
                                  double ts, double* W, double* yref, int32_t* info) {

@@ -208,20 +208,13 @@ def _run(who, A, B, H, X0, horizon, steps, phase0, D, d, ndcnt, q, Pf, tol, max_
         ndcnt = ndcnt.contiguous() if use_torch else np.ascontiguousarray(ndcnt)
     if necnt is not None:
         necnt = necnt.contiguous() if use_torch else np.ascontiguousarray(necnt)
-    if aff is not None:
-        Tx = terminal if isinstance(terminal, str) or terminal is None else lqr._contig(terminal, use_torch)
-        entry = _lib.mpc_qp_aff_batch_device if use_torch else _lib.mpc_qp_aff_batch_host
-        out = entry(A, B, H, q, Pf, D, ndcnt, d, penalty, J, r, necnt, Tx, aff, X0, N, T, k0, float(tol), int(max_iter), bool(return_traj), bool(return_ol))
-    elif J is not None or terminal is not None:
-        Tx = terminal if isinstance(terminal, str) or terminal is None else lqr._contig(terminal, use_torch)
-        entry = _lib.mpc_qp_eq_batch_device if use_torch else _lib.mpc_qp_eq_batch_host
-        out = entry(A, B, H, q, Pf, D, ndcnt, d, penalty, J, r, necnt, Tx, X0, N, T, k0, float(tol), int(max_iter), bool(return_traj), bool(return_ol))
-    elif penalty is None:
-        entry = _lib.mpc_qp_batch_device if use_torch else _lib.mpc_qp_batch_host
-        out = entry(A, B, H, q, Pf, D, ndcnt, d, X0, N, T, k0, float(tol), int(max_iter), bool(return_traj), bool(return_ol))
-    else:
-        entry = _lib.mpc_qp_soft_batch_device if use_torch else _lib.mpc_qp_soft_batch_host
-        out = entry(A, B, H, q, Pf, D, ndcnt, d, penalty, X0, N, T, k0, float(tol), int(max_iter), bool(return_traj), bool(return_ol))
+    # the entry of the lowest level that has the arguments: hard, soft (penalty), eq (J, terminal), aff (the affine arrays); each level appends its own
+    level = 'aff_' if aff is not None else 'eq_' if J is not None or terminal is not None else 'soft_' if penalty is not None else ''
+    args = (A, B, H, q, Pf, D, ndcnt, d) + ((penalty,) if level else ())
+    if level in ('eq_', 'aff_'):
+        args += (J, r, necnt, terminal if isinstance(terminal, str) or terminal is None else lqr._contig(terminal, use_torch)) + ((aff,) if level == 'aff_' else ())
+    entry = getattr(_lib, 'mpc_qp_%sbatch_%s' % (level, 'device' if use_torch else 'host'))
+    out = entry(*args, X0, N, T, k0, float(tol), int(max_iter), bool(return_traj), bool(return_ol))
     info = out['info']
     for i, name in enumerate(INFO_FIELDS):
         col = info[..., i]
