@@ -125,6 +125,9 @@ int tmpc_set_options(tmpc_handle* h, double tol, double center_tol, int max_iter
  *                          (k_cr_trsm_dma_f32: fp64 operands rounded on the fragment read, float32 accumulation, only the float32 copy of O is produced -- the one
  *                          the updates and substitutions of such an iteration read); the Cholesky of the diagonal blocks stays fp64.  0: fp64 solves in every
  *                          iteration (round 6, bit for bit)
+ *   TMPC_TUNE_TRSM_PAIR    1 (default): a workgroup of k_cr_trsm_dma_f32 solves strip r of BOTH edge blocks of an eliminated node on one stream of the node's
+ *                          factor (one item per problem, node and strip; each L fragment read and rounded once for the two edges); 0: one edge per workgroup
+ *                          (round 7's item list).  Same MFMA sequence per output element: bit-identical results
  *   TMPC_TUNE_PERSISTENT   plain-model problems with single-tile Schur blocks and n = nx + mb <= 8 (the reference's own examples) can run their whole
  *                          interior-point loop as ONE launch, one workgroup per problem (tmpc_persist.h).  1 (default): where that is faster -- period
  *                          p <= 8, or at least 96 problems of the call on the chip at once; 0: never (the launch sequence); 2: whenever the shape allows it
@@ -139,6 +142,7 @@ int tmpc_set_options(tmpc_handle* h, double tol, double center_tol, int max_iter
 #define TMPC_TUNE_LOWP_SWITCH 8
 #define TMPC_LOWP_SWITCH_DEFAULT 1e-5
 #define TMPC_TUNE_LOWP_TRSM 9
+#define TMPC_TUNE_TRSM_PAIR 10
 int tmpc_set_tuning(tmpc_handle* h, int key, double value);
 /* The general constructor: ng / nc rows of G_k / C_k (0: none), step3 != 0: room for T_k, lanes = concurrent half-waves on their own streams
  * (0: automatic -- two for problems whose blocks are a single 64 x 64 tile and chunk >= 2, one otherwise; at most 4). */

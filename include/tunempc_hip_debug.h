@@ -64,6 +64,10 @@ typedef struct {
   int32_t *nshift, *dims, *orient;
 } tmpc_debug_factor_io;
 int tmpc_debug_block_factor(tmpc_handle* h, int nb, int p, int d, int count, int mode, const tmpc_debug_factor_io* io);
+/* How many two-edge items (TMPC_TUNE_TRSM_PAIR: problem x node with both edges x strip) the last tmpc_debug_block_factor / tmpc_debug_factor_bench of this
+ * process launched in k_cr_trsm_dma_f32 -- counted on the host from the schedule and the problem list where cr_factor launches the kernel, no device counter.
+ * 0: the key is off, no float32 solve ran, or no node of the schedule has two edges (p = 2). */
+long long tmpc_debug_last_trsm_pairs(void);
 
 /* The elimination schedule for period p (host only, no device needed): out = [nlev, prep, nelim, nupd, nlev x (eoff, nelim,
  * uoff, nupd), nelim x 8 ints (node, na, nb, ea, eb, fill, fx, facc), nupd x 8 ints (node, e0, src0, e1, src1, 0, 0, 0),

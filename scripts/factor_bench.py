@@ -8,6 +8,10 @@ if os.environ.get('FB_LOWP'):
     h.set_tuning(lowp_switch=2.0)      # (a switch >= 1 in the debug entries: every Schur-complement update in single precision)
 if float(os.environ.get('FB_LOWP_VALUE', '0')) > 0:
     h.set_tuning(lowp_switch=float(os.environ['FB_LOWP_VALUE']))      # (scripts/gpu_r6_ablate.sh)
+if os.environ.get('FB_LOWP_TRSM'):
+    h.set_tuning(lowp_trsm=int(os.environ['FB_LOWP_TRSM']))      # (with FB_LOWP: 0 = fp64 triangular solves, the bench of rounds 6-8)
+if os.environ.get('FB_TRSM_PAIR'):
+    h.set_tuning(trsm_pair=int(os.environ['FB_TRSM_PAIR']))      # (0 = one edge per workgroup in k_cr_trsm_dma_f32)
 cases = [(512, 8, 300), (64, 8, 300), (8, 8, 300), (512, 64, 300), (64, 64, 300), (8, 64, 300), (1, 64, 300), (64, 200, 210), (1, 30, 10)]
 if len(sys.argv) > 1:
     cases = [tuple(int(v) for v in a.split(',')) for a in sys.argv[1:]]

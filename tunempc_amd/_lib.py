@@ -34,6 +34,7 @@ EXPORTS = [
 DEBUG_EXPORTS = [
     'tmpc_debug_gemm_nt', 'tmpc_debug_block_solve', 'tmpc_debug_cr_schedule', 'tmpc_debug_get_multipliers', 'tmpc_debug_get_array',
     'tmpc_debug_min_eig', 'tmpc_debug_min_eig_lane', 'tmpc_debug_factor_bench', 'tmpc_debug_block_factor',
+    'tmpc_debug_last_trsm_pairs',
 ]
 FLAG_DEBUG_NO_DMA = 32      # tunempc_hip_debug.h: TMPC_DEBUG_FLAG_NO_DMA
 # mode bits of tmpc_debug_block_factor (tunempc_hip_debug.h)
@@ -186,6 +187,8 @@ def load_library():
     lib.tmpc_debug_block_factor.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_FactorIO)]
     lib.tmpc_debug_factor_bench.restype = C.c_int
     lib.tmpc_debug_factor_bench.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, dp]
+    lib.tmpc_debug_last_trsm_pairs.restype = C.c_longlong
+    lib.tmpc_debug_last_trsm_pairs.argtypes = []
     lib.tmpc_debug_min_eig.restype = C.c_int
     lib.tmpc_debug_min_eig.argtypes = [vp, C.c_int, C.c_int, dp, dp]
     lib.tmpc_debug_min_eig_lane.restype = C.c_int
@@ -251,9 +254,9 @@ class HipConvexifier:
         _check(self.lib, self.lib.tmpc_set_options(self._h, float(tol or 0.0), float(center_tol or 0.0),
                                                    int(max_iter or 0), int(center_iter or 0), self.flags), 'tmpc_set_options')
 
-    def set_tuning(self, chord_step=None, small_blocks=None, eig_pretest=None, fuse_fwd=None, graph=None, persistent=None, lowp_switch=None, lowp_trsm=None):
+    def set_tuning(self, chord_step=None, small_blocks=None, eig_pretest=None, fuse_fwd=None, graph=None, persistent=None, lowp_switch=None, lowp_trsm=None, trsm_pair=None):
         """Performance knobs of the handle (include/tunempc_hip.h: tmpc_set_tuning); None keeps the current value."""
-        for key, v in ((1, chord_step), (2, small_blocks), (3, eig_pretest), (4, fuse_fwd), (5, graph), (7, persistent), (8, lowp_switch), (9, lowp_trsm)):
+        for key, v in ((1, chord_step), (2, small_blocks), (3, eig_pretest), (4, fuse_fwd), (5, graph), (7, persistent), (8, lowp_switch), (9, lowp_trsm), (10, trsm_pair)):
             if v is not None:
                 _check(self.lib, self.lib.tmpc_set_tuning(self._h, key, float(v)), 'tmpc_set_tuning')
 
@@ -591,6 +594,10 @@ class HipConvexifier:
         out = np.zeros(2)
         _check(self.lib, self.lib.tmpc_debug_factor_bench(self._h, nb, p, d, reps, _dptr(out)), 'tmpc_debug_factor_bench')
         return out
+
+    def debug_last_trsm_pairs(self):
+        """Two-edge items of k_cr_trsm_dma_f32 in the last debug_block_factor / debug_factor_bench (tmpc_debug_last_trsm_pairs: a host-side count)."""
+        return int(self.lib.tmpc_debug_last_trsm_pairs())
 
     def debug_block_solve(self, D, Ccpl, rhs):
         D = np.ascontiguousarray(D, dtype=np.float64); Ccpl = np.ascontiguousarray(Ccpl, dtype=np.float64)

@@ -146,7 +146,7 @@ struct tmpc_handle {
   CrSched sched;                 // elimination order of the block factorisation (tmpc_cr.h)
   int* d_sched;                  // device copy: elimination records | update records | orientation
   int rs, mt;                    // rows per workgroup of k_cr_trsm / output tile edge of k_cr_update (0: chosen per launch)
-  int tune_small, tune_pretest, tune_fuse, tune_graph, tune_persist, tune_lowp_trsm;     // tmpc_set_tuning
+  int tune_small, tune_pretest, tune_fuse, tune_graph, tune_persist, tune_lowp_trsm, tune_trsm_pair;     // tmpc_set_tuning
   void* dd_slab;                 // tight mode (tmpc_set_tight): low words of the double-double planes, allocated on first use
   size_t dd_bytes;
   int tight;                     // 1: the tight phase follows the default solve
@@ -547,7 +547,8 @@ static bool cr_small_levels(const Dims& dm, const CrSched& sc, CrLevs* out) {
 // rs / mt: rows per workgroup of the triangular solves / edge of the output tile of the updates; 0 = by the amount of work
 // (whole 128-wide pieces while every CU still gets several workgroups, 64 otherwise).  The result does not depend on them.
 static void cr_factor(const WS& w, const Dims& dm, const CrSched& sc, const int* d_sched, const int* alist, int count, hipStream_t st,
-                      int rs_opt, int mt_opt, std::vector<hipEvent_t>* kev = nullptr, int* nkev = nullptr, int fuse_fwd1 = 0, int nlowp = 0) {
+                      int rs_opt, int mt_opt, std::vector<hipEvent_t>* kev = nullptr, int* nkev = nullptr, int fuse_fwd1 = 0, int nlowp = 0, long long* npairs = nullptr) {
+  // npairs (debug entries): += the two-edge items of k_cr_trsm_dma_f32 this call launches, from the schedule and nlowp
   // nlowp: how many of the `count` problems run their Schur-complement updates in single precision (exact: k_ctrl_d / k_init_prob counted them)
   const CrDev cd = cr_dev(sc, d_sched, alist);
   int ke = 0;
@@ -600,8 +601,14 @@ static void cr_factor(const WS& w, const Dims& dm, const CrSched& sc, const int*
       const bool trsm32 = (dm.flags & DF_LOWP_TRSM) != 0;
       if (!trsm32 || nlowp < count)
         hipLaunchKernelGGL(k_cr_trsm_dma, dim3(cr_grid((long)count * lv.nelim * 2 * nt64)), dim3(256), trsm_lds, st, w, dm, cd, lv.eoff, lv.nelim, count);
-      if (trsm32 && nlowp > 0)
-        hipLaunchKernelGGL(k_cr_trsm_dma_f32, dim3(cr_grid((long)count * lv.nelim * 2 * nt64)), dim3(256), (size_t)trf_lds_doubles() * sizeof(double), st, w, dm, cd, lv.eoff, lv.nelim, count);
+      if (trsm32 && nlowp > 0) {
+        // TMPC_TUNE_TRSM_PAIR: one item per (problem, node, strip) carries both edges of the node on one factor stream; off: one item per edge
+        const bool pair = (dm.flags & DF_TRSM_PAIR) != 0;
+        hipLaunchKernelGGL(k_cr_trsm_dma_f32, dim3(cr_grid((long)count * lv.nelim * (pair ? 1 : 2) * nt64)), dim3(256), (size_t)trf_lds_doubles() * sizeof(double), st, w, dm, cd, lv.eoff, lv.nelim, count);
+        if (pair && npairs)
+          for (int e = lv.eoff; e < lv.eoff + lv.nelim; ++e)
+            if (sc.elim[(size_t)e * CR_EW + CE_EA] >= 0 && sc.elim[(size_t)e * CR_EW + CE_EB] >= 0) *npairs += (long long)nlowp * nt64;
+      }
     }
     else if (mf) hipLaunchKernelGGL((k_cr_trsm<true, 2>), dim3(cr_grid(it_trsm)), dim3(256), factor_lds(), st, w, dm, cd, lv.eoff, lv.nelim, count, rs);
     else hipLaunchKernelGGL((k_cr_trsm<false, 2>), dim3(cr_grid(it_trsm)), dim3(256), factor_lds(), st, w, dm, cd, lv.eoff, lv.nelim, count, rs);
@@ -745,7 +752,7 @@ static int run_chunk(tmpc_handle* h, Lane* ln, int nb, const double* dA, const d
   // (at the defaults, 1e-5 against 2^-25 ~ 3e-8, the clamp does not bind)
   if (o.lowp_switch > 0.0) o.lowp_switch = fmax(o.lowp_switch, 16.0 * o.tol);
   if (o.lowp_switch > 0.0) {
-    dm.flags |= DF_LOWP | (h->tune_lowp_trsm ? DF_LOWP_TRSM : 0);
+    dm.flags |= DF_LOWP | (h->tune_lowp_trsm ? DF_LOWP_TRSM : 0) | (h->tune_trsm_pair ? DF_TRSM_PAIR : 0);
     // the float32 copies are laid out by this call's block width; where the last call used another one (a handle with room for rows serving the plain model, or
     // the other way round) its data sit where the zero padding of this call's rows must be
     if (ln->o32_dp != 0 && ln->o32_dp != dm.dp) HIPCHK(hipMemsetAsync(w.O32, 0, 2 * (size_t)h->dm.B * h->dm.p * h->dm.dp * ((h->dm.dp + 31) & ~31) * sizeof(float), st));
@@ -1147,7 +1154,7 @@ static int create_handle(tmpc_handle** out, int chunk, int p, int nx, int mb, in
   h->dm = make_dims(cap, p, nx, mb, ng, nc, step3);
   h->sched = cr_build(p);
   h->rs = 0; h->mt = 0;
-  h->tune_small = 1; h->tune_pretest = 1; h->tune_fuse = 1; h->tune_graph = 1; h->tune_persist = 1; h->tune_lowp_trsm = 1;
+  h->tune_small = 1; h->tune_pretest = 1; h->tune_fuse = 1; h->tune_graph = 1; h->tune_persist = 1; h->tune_lowp_trsm = 1; h->tune_trsm_pair = 1;
   h->opt.tol = 0x1p-25; h->opt.center_tol = 1e-9; h->opt.max_iter = 50; h->opt.center_iter = 12;
   h->opt.fast_exit = 0;
   h->opt.lowp_switch = TMPC_LOWP_SWITCH_DEFAULT;
@@ -1230,6 +1237,7 @@ int tmpc_set_tuning(tmpc_handle* h, int key, double value) {
     case TMPC_TUNE_GRAPH: h->tune_graph = value != 0.0; return TMPC_OK;
     case TMPC_TUNE_PERSISTENT: if (!(value >= 0.0 && value <= 2.0)) return TMPC_E_ARG; h->tune_persist = (int)value; return TMPC_OK;
     case TMPC_TUNE_LOWP_TRSM: h->tune_lowp_trsm = value != 0.0; return TMPC_OK;
+    case TMPC_TUNE_TRSM_PAIR: h->tune_trsm_pair = value != 0.0; return TMPC_OK;
     default: snprintf(g_err, sizeof(g_err), "tmpc_set_tuning: unknown key %d", key); return TMPC_E_ARG;
   }
 }
@@ -2662,6 +2670,8 @@ int tmpc_debug_block_solve(tmpc_handle* h, int p, int d, const double* D, const 
 
 // The factorisation and its substitutions as run_chunk drives them, on nb distinct systems, with the factor read back (tunempc_hip_debug.h): the problem list,
 // the per-problem I_LOWP, DF_LOWP_TRSM, nlowp, fuse_fwd1 / skip_fwd and the pass reach cr_factor / cr_solve (dd_factor / dd_solve) exactly as they do from there.
+static long long g_last_trsm_pairs = 0;      // two-edge items of k_cr_trsm_dma_f32 in the last debug factorisation (host-side count: cr_factor)
+long long tmpc_debug_last_trsm_pairs(void) { return g_last_trsm_pairs; }
 int tmpc_debug_block_factor(tmpc_handle* h, int nb, int p, int d, int count, int mode, const tmpc_debug_factor_io* io) {
   if (!h || !io || nb < 1 || p < 1 || d < 1 || count < 0 || count > nb || !io->D || !io->Ccpl || !io->rhs || (count > 0 && !io->list)) return TMPC_E_ARG;
   if (mode & ~(TMPC_DEBUG_FACTOR_PASS1 | TMPC_DEBUG_FACTOR_FUSE_FWD1 | TMPC_DEBUG_FACTOR_LOWP_TRSM | TMPC_DEBUG_FACTOR_DD)) return TMPC_E_ARG;
@@ -2696,7 +2706,7 @@ int tmpc_debug_block_factor(tmpc_handle* h, int nb, int p, int d, int count, int
     if (O32b.alloc(n32 * sizeof(float)) != hipSuccess) return TMPC_E_NOMEM;
     HIPCHK(hipMemset(O32b.p, 0, n32 * sizeof(float)));            // (the workspace of a handle: zero when created, the padding stays so)
     w.O32 = O32b.as<float>();
-    dm.flags |= DF_LOWP | ((mode & TMPC_DEBUG_FACTOR_LOWP_TRSM) ? DF_LOWP_TRSM : 0);
+    dm.flags |= DF_LOWP | ((mode & TMPC_DEBUG_FACTOR_LOWP_TRSM) ? DF_LOWP_TRSM : 0) | (h->tune_trsm_pair ? DF_TRSM_PAIR : 0);
   }
   if (ddm) {
     if (Dlb.alloc(nb * per * 8) != hipSuccess || Olb.alloc(nb * per * 8) != hipSuccess || Flb.alloc(nb * per * 8) != hipSuccess ||
@@ -2735,6 +2745,7 @@ int tmpc_debug_block_factor(tmpc_handle* h, int nb, int p, int d, int count, int
     for (int b = 0; b < nb; ++b) hi[(size_t)b * IS + I_LOWP] = io->lowp[b] ? 1 : 0;
     HIPCHK(hipMemcpy(w.iprob, hi.data(), hi.size() * sizeof(int), hipMemcpyHostToDevice));
   }
+  g_last_trsm_pairs = 0;
   if (count > 0) {
     const int pass = pass1 ? 1 : 2;
     if (ddm) {
@@ -2742,7 +2753,7 @@ int tmpc_debug_block_factor(tmpc_handle* h, int nb, int p, int d, int count, int
       rc = dd_solve(w, dm, cb.sc, cb.d_sched, w.alist, count, 0, pass, nb);
       if (rc != TMPC_OK) return rc;
     } else {
-      cr_factor(w, dm, cb.sc, cb.d_sched, w.alist, count, 0, h->rs, h->mt, nullptr, nullptr, fuse ? 1 : 0, nlowp);
+      cr_factor(w, dm, cb.sc, cb.d_sched, w.alist, count, 0, h->rs, h->mt, nullptr, nullptr, fuse ? 1 : 0, nlowp, &g_last_trsm_pairs);
       cr_solve(w, dm, cb.sc, cb.d_sched, w.alist, count, 0, pass, fuse);
     }
   }
@@ -2779,6 +2790,9 @@ int tmpc_debug_factor_bench(tmpc_handle* h, int nb, int p, int d, int reps, doub
   cb.ablate = (int)h->opt.lowp_switch - 2;      // (-DTMPC_ABLATE builds: 3, 4, 5, 6 = the ablations of wg_tile_dma_f32)
   int rc = cb.init(nb, p, d, h->flags, h->opt.lowp_switch >= 1.0);
   if (rc != TMPC_OK) return rc;
+  // the handle's keys, as run_chunk sets them: with single-precision updates the solves are single precision too (TMPC_TUNE_LOWP_TRSM), two edges per workgroup (TMPC_TUNE_TRSM_PAIR)
+  if (cb.dm.flags & DF_LOWP) cb.dm.flags |= (h->tune_lowp_trsm ? DF_LOWP_TRSM : 0) | (h->tune_trsm_pair ? DF_TRSM_PAIR : 0);
+  g_last_trsm_pairs = 0;
   const int dp = cb.dm.dp;
   const size_t bs = (size_t)dp * dp, per = (size_t)p * bs;
   // T = sum_k J_k' J_k + I  with J_k = [E_k G_k] on blocks (k, k+1): SPD by construction
@@ -2814,7 +2828,7 @@ int tmpc_debug_factor_bench(tmpc_handle* h, int nb, int p, int d, int reps, doub
       HIPCHK(hipMemcpyAsync(cb.w.O + b * per, pO.p, per * 8, hipMemcpyDeviceToDevice, 0));
     }
     HIPCHK(hipEventRecord(e0, 0));
-    cr_factor(cb.w, cb.dm, cb.sc, cb.d_sched, cb.w.alist, nb, 0, h->rs, h->mt, nullptr, nullptr, 0, cb.w.O32 ? nb : 0);
+    cr_factor(cb.w, cb.dm, cb.sc, cb.d_sched, cb.w.alist, nb, 0, h->rs, h->mt, nullptr, nullptr, 0, cb.w.O32 ? nb : 0, r == reps ? &g_last_trsm_pairs : nullptr);
     HIPCHK(hipEventRecord(e1, 0));
     cr_solve(cb.w, cb.dm, cb.sc, cb.d_sched, cb.w.alist, nb, 0, 2);
     HIPCHK(hipEventRecord(e2, 0));

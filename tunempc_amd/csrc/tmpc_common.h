@@ -80,7 +80,7 @@ struct Dims {
   int d;        // nx(nx+1)/2
   int dp;       // d padded to a multiple of 16
   int nt;       // ceil(dp / TB)
-  int flags;    // bit 0: debug - replace MFMA by scalar FMAs; DF_LOWP, DF_LOWP_TRSM below; bits 24-26: ablations (TMPC_ABLATE builds); other bits: host side only (tmpc_api.hip)
+  int flags;    // bit 0: debug - replace MFMA by scalar FMAs; DF_LOWP, DF_LOWP_TRSM, DF_TRSM_PAIR below; bits 24-26: ablations (TMPC_ABLATE builds); other bits: host side only (tmpc_api.hip)
   int ng;       // rows of the equality-constraint Jacobian G_k per stage (0: none), <= NGM
   int nr;       // row stride of the stage-local multipliers: ng + (max rows of the active-constraint Jacobians C_k, Step 2), <= NRM
   int nz;       // stride of the stage-local variable vector: nr (+ 2 epigraph variables of the norm terms in Step 2)
@@ -90,6 +90,7 @@ struct Dims {
 // bits of Dims::flags that device code reads
 constexpr int DF_LOWP = 8;        // single-precision updates are on for this call (Opts::lowp_switch > 0, the handle has the float32 copies): k_init_prob decides the first iteration
 constexpr int DF_LOWP_TRSM = 16;  // ... and the triangular solves of those iterations run in single precision too (TMPC_TUNE_LOWP_TRSM): k_cr_trsm_dma_f32
+constexpr int DF_TRSM_PAIR = 32;  // ... with strip r of BOTH edges of a node in one workgroup, on one factor stream (TMPC_TUNE_TRSM_PAIR): the item list of k_cr_trsm_dma_f32
 constexpr int NGM = 31;  // max ng
 constexpr int NCM = 31;  // max rows of C_k
 constexpr int NRM = NGM + NCM, NZM = NRM + 2;      // (nz <= 64: one lane per stage-local variable)

@@ -616,9 +616,16 @@ __global__ void __launch_bounds__(256, 2) k_cr_trsm_dma(WS w, Dims dm, CrDev cr,
 // four k a lane feeds (granules fk and 4 + fk of the L slab) are one 16-byte read, and the eight lanes of an LDS cycle (rows fr .. fr + 7) hit distinct banks.
 // Accumulators: four sets of 4 x float4 (64 VGPRs, half of trd_strip's); every product step runs four independent MFMA chains
 // (C layout: the four row fragments; R layout: the column strips) against the 40-cycle dependent-issue latency.
-constexpr int trf_lds_doubles() { return 2048 + TRD_DEPTH * 2048; }       // float32 X_i (four 64 x 16 slabs) + the B steps in flight
-__device__ __forceinline__ void trf_strip(const double* X, const double* Dk, const double* Li, int rows, int nt, int dp, int it, double* lds, float* X32, int ld32) {
-  constexpr int ASL = 64 * 16, DP = TRD_DEPTH;              // floats per A slab
+// Round 9: NE = 2 edges per workgroup.  Both edges of an eliminated node (EA, EB) are solved against the same L_i, so strip r of both rides on ONE slab
+// stream: the slabs are issued once per step, every L fragment is read from LDS and rounded to float32 once and feeds the MFMAs of edge 0 and of edge 1
+// (eight independent chains per product step instead of four).  Each edge has its own float32 A image (lds + e * 2048 doubles) and its own four accumulator
+// sets (128 VGPRs at NE = 2); loads of E, parks and stores run edge by edge, and every one of them is counted in vmtot, so the counted waits on the slab DMAs
+// stay exact.  An output element sees the MFMA sequence of the one-edge form, in the same k order: O32 is bit-identical.  NE = 1 is the one-edge form
+// (a node with one edge, or TMPC_TUNE_TRSM_PAIR = 0).
+constexpr int trf_lds_doubles() { return 2 * 2048 + TRD_DEPTH * 2048; }   // float32 X_i of two edges (four 64 x 16 slabs each) + the B steps in flight
+template <int NE>
+__device__ __forceinline__ void trf_strip(const double* X0, const double* X1, const double* Dk, const double* Li, int rows, int nt, int dp, int it, double* lds, float* Y0, float* Y1, int ld32) {
+  constexpr int ASL = 64 * 16, AE = 4 * ASL, DP = TRD_DEPTH;          // floats per A slab, per A image of an edge
   const int tid = threadIdx.x;
   const int lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int ws = (wv + it) & 3, wc0 = ws * 16;              // this wave's column strip ("C") or row fragment ("R"), as in trd_strip
@@ -628,80 +635,103 @@ __device__ __forceinline__ void trf_strip(const double* X, const double* Dk, con
   const int ntd = nt;
   const bool rw = ws < i1;
   float* At = (float*)lds;
-  double* Bs = lds + 2048;
-  unsigned voT[2], voL[2];
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const int row = wv * 16 + 8 * h + (lane >> 3), c = lane & 7;
-    voT[h] = (unsigned)(row * TB + 2 * (c ^ dma_sw(row))) * 8u;
-    voL[h] = (unsigned)(row * dp + 2 * (c ^ dma_sw(row))) * 8u;
-  }
+  double* Bs = lds + NE * 2048;                             // edge e parks its X_i at At + e * AE
+  // NE = 2: the per-lane constants of the rare steps (DMA offsets, store rows, park slots) are rebuilt where they are used, from a lane id the compiler cannot
+  // see through, instead of living across the ci loop next to 128 accumulator registers (the same device as in trd_strip<true>)
+#define TRF_LANE(V) int V = lane; if (NE > 1) asm volatile("" : "+v"(V));
   int of[2];                                                // L slab: granule 4 hh + fk of row fr (of any 16-row group), in doubles
 #pragma unroll
   for (int hh = 0; hh < 2; ++hh) of[hh] = fr * 16 + 2 * ((4 * hh + fk) ^ dma_sw(fr));
   const int asw = (fr >> 1) & 3, ofa = fr * 16 + 4 * (fk ^ asw);                           // float32 A image: this lane's four k of row fr
-  const int opa0 = 4 * ((2 * fk) & 3 ^ asw) + 2 * (fk >> 1), opa1 = 4 * ((2 * fk + 1) & 3 ^ asw) + 2 * (fk >> 1);    // where columns 4 fk, + 1 / 4 fk + 2, + 3 of a slab go
-  float4_t acc0[4], acc1[4], acc2[4], acc3[4];
+  // where columns 4 fk, + 1 / 4 fk + 2, + 3 of a slab go (fk_, fr_: from TRF_LANE)
+#define TRF_OPA()                                                                                           \
+    TRF_LANE(l_)                                                                                            \
+    const int fk_ = l_ >> 4, fr_ = l_ & 15, asw_ = (fr_ >> 1) & 3;                                          \
+    const int opa0 = 4 * ((2 * fk_) & 3 ^ asw_) + 2 * (fk_ >> 1), opa1 = 4 * ((2 * fk_ + 1) & 3 ^ asw_) + 2 * (fk_ >> 1);
+  float4_t acc0[NE][4], acc1[NE][4], acc2[NE][4], acc3[NE][4];
+#define TRF_EDGES _Pragma("unroll") for (int ed = 0; ed < NE; ++ed)
   int vmtot = 0, vmk0 = 0, vmk1 = 0, vmk2 = 0;
 #define TRF_NB(T) ((dp - 64 * (T) < 64) ? dp - 64 * (T) : 64)
-  // C layout: SET[i][r] = T[16 i + fr][wc0 + 4 fk + r] of tile I
-#define TRF_LOAD_C(I, SET)                                                                                  \
+  // C layout: SET[ed][i][r] = T[16 i + fr][wc0 + 4 fk + r] of tile I of edge ed.  The fp64 loads (FETCH, into a buffer of eight 16-byte registers) and the
+  // negate-and-round (CVT) are separate: in flight a (tile, edge) group costs 32 VGPRs, converted 16, so the prologue keeps four groups in flight -- all of
+  // them at NE = 1, half of them at NE = 2, where eight at once would not leave room for the 128 accumulator registers
+#define TRF_FETCH_C(I, ED, BUF)                                                                             \
   {                                                                                                         \
     const bool on_ = wc0 < TRF_NB(I);                                                                       \
+    const double* X = (ED) ? X1 : X0;                                                                       \
     _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                          \
-      double2_t u0 = (double2_t){0.0, 0.0}, u1 = u0;                                                        \
+      BUF[2 * i] = (double2_t){0.0, 0.0}; BUF[2 * i + 1] = BUF[2 * i];                                      \
       if (on_ && i < i1) {                                                                                  \
         gcptr2 cp = (gcptr2)(X + (size_t)(16 * i + fr) * dp + 64 * (I) + wc0 + 4 * fk);                     \
-        u0 = cp[0]; u1 = cp[1];                                                                             \
+        BUF[2 * i] = cp[0]; BUF[2 * i + 1] = cp[1];                                                         \
       }                                                                                                     \
-      SET[i] = (float4_t){(float)-u0[0], (float)-u0[1], (float)-u1[0], (float)-u1[1]};                      \
     }                                                                                                       \
     if (on_) vmtot += 2 * i1;                                                                               \
   }
+#define TRF_CVT_C(SET, ED, BUF)                                                                             \
+  _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                              \
+    SET[ED][i] = (float4_t){(float)-BUF[2 * i][0], (float)-BUF[2 * i][1], (float)-BUF[2 * i + 1][0], (float)-BUF[2 * i + 1][1]};
   // R layout: SET[c][r] = T[wc0 + fr][16 c + 4 fk + r] of tile I, strips c < NC
 #define TRF_LOAD_R(I, NC, SET)                                                                              \
   {                                                                                                         \
-    _Pragma("unroll") for (int c = 0; c < 4; ++c) {                                                          \
-      double2_t u0 = (double2_t){0.0, 0.0}, u1 = u0;                                                        \
-      if (rw && c < (NC)) {                                                                                 \
-        gcptr2 cp = (gcptr2)(X + (size_t)(wc0 + fr) * dp + 64 * (I) + 16 * c + 4 * fk);                     \
-        u0 = cp[0]; u1 = cp[1];                                                                             \
+    TRF_EDGES {                                                                                             \
+      const double* X = ed ? X1 : X0;                                                                       \
+      _Pragma("unroll") for (int c = 0; c < 4; ++c) {                                                        \
+        double2_t u0 = (double2_t){0.0, 0.0}, u1 = u0;                                                      \
+        if (rw && c < (NC)) {                                                                               \
+          gcptr2 cp = (gcptr2)(X + (size_t)(wc0 + fr) * dp + 64 * (I) + 16 * c + 4 * fk);                   \
+          u0 = cp[0]; u1 = cp[1];                                                                           \
+        }                                                                                                   \
+        SET[ed][c] = (float4_t){(float)-u0[0], (float)-u0[1], (float)-u1[0], (float)-u1[1]};                \
       }                                                                                                     \
-      SET[c] = (float4_t){(float)-u0[0], (float)-u0[1], (float)-u1[0], (float)-u1[1]};                      \
+      if (rw) vmtot += 2 * (NC);                                                                            \
     }                                                                                                       \
-    if (rw) vmtot += 2 * (NC);                                                                              \
   }
 #define TRF_STORE_R(I, NC, SET)                                                                             \
   if (rw) {                                                                                                 \
     typedef float4_t __attribute__((address_space(1)))* gptr4;                                              \
-    _Pragma("unroll") for (int c = 0; c < 4; ++c)                                                            \
-      if (c < (NC)) *(gptr4)(X32 + (size_t)(wc0 + fr) * ld32 + 64 * (I) + 16 * c + 4 * fk) = SET[c];        \
-    vmtot += (NC);                                                                                          \
+    TRF_LANE(l_)                                                                                            \
+    const int fk_ = l_ >> 4, fr_ = l_ & 15;                                                                 \
+    TRF_EDGES {                                                                                             \
+      float* X32 = ed ? Y1 : Y0;                                                                            \
+      _Pragma("unroll") for (int c = 0; c < 4; ++c)                                                          \
+        if (c < (NC)) *(gptr4)(X32 + (size_t)(wc0 + fr_) * ld32 + 64 * (I) + 16 * c + 4 * fk_) = SET[ed][c]; \
+      vmtot += (NC);                                                                                        \
+    }                                                                                                       \
   }
   // (+-) set -> A operand (float32 image).  C: slab = this wave's strip, rows 16 i + fr; R: row wc0 + fr of the slabs c < NC
 #define TRF_PARK_C(SET)      /* negated */                                                                  \
   {                                                                                                         \
-    _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                          \
-      float* q = At + ws * ASL + (16 * i + fr) * 16;                                                        \
-      *(float2_t*)(q + opa0) = (float2_t){-SET[i][0], -SET[i][1]};                                           \
-      *(float2_t*)(q + opa1) = (float2_t){-SET[i][2], -SET[i][3]};                                           \
+    TRF_OPA()                                                                                               \
+    TRF_EDGES _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                \
+      float* q = At + ed * AE + ws * ASL + (16 * i + fr_) * 16;                                             \
+      *(float2_t*)(q + opa0) = (float2_t){-SET[ed][i][0], -SET[ed][i][1]};                                   \
+      *(float2_t*)(q + opa1) = (float2_t){-SET[ed][i][2], -SET[ed][i][3]};                                   \
     }                                                                                                       \
   }
 #define TRF_PARK_R(NC, SET, SG)                                                                             \
   if (rw) {                                                                                                 \
-    _Pragma("unroll") for (int c = 0; c < 4; ++c) {                                                          \
+    TRF_OPA()                                                                                               \
+    TRF_EDGES _Pragma("unroll") for (int c = 0; c < 4; ++c) {                                                \
       if (c < (NC)) {                                                                                       \
-        float* q = At + c * ASL + (wc0 + fr) * 16;                                                          \
-        *(float2_t*)(q + opa0) = (float2_t){SG SET[c][0], SG SET[c][1]};                                     \
-        *(float2_t*)(q + opa1) = (float2_t){SG SET[c][2], SG SET[c][3]};                                     \
+        float* q = At + ed * AE + c * ASL + (wc0 + fr_) * 16;                                               \
+        *(float2_t*)(q + opa0) = (float2_t){SG SET[ed][c][0], SG SET[ed][c][1]};                             \
+        *(float2_t*)(q + opa1) = (float2_t){SG SET[ed][c][2], SG SET[ed][c][3]};                             \
       }                                                                                                     \
     }                                                                                                       \
   }
-#define TRF_ZERO(SET) { _Pragma("unroll") for (int i = 0; i < 4; ++i) SET[i] = (float4_t){0.f, 0.f, 0.f, 0.f}; }
+#define TRF_ZERO(SET) { TRF_EDGES _Pragma("unroll") for (int i = 0; i < 4; ++i) SET[ed][i] = (float4_t){0.f, 0.f, 0.f, 0.f}; }
   int ii = 0, ij = 0, is = 0, nissued = 0, ndone = 0;
 #define TRF_ISSUE()          /* the slab stream of trd_strip */                                             \
   {                                                                                                         \
     if (ii < ntd) {                                                                                         \
+      TRF_LANE(l_)                                                                                          \
+      unsigned voT[2], voL[2];                              /* wave wv moves rows 16 wv .. + 15 of a B slab, two pieces of 8 rows */ \
+      _Pragma("unroll") for (int h = 0; h < 2; ++h) {                                                        \
+        const int row = wv * 16 + 8 * h + (l_ >> 3), c = l_ & 7;                                            \
+        voT[h] = (unsigned)(row * TB + 2 * (c ^ dma_sw(row))) * 8u;                                         \
+        voL[h] = (unsigned)(row * dp + 2 * (c ^ dma_sw(row))) * 8u;                                         \
+      }                                                                                                     \
       double* dst_ = Bs + (nissued % DP) * 2048 + wv * 256;                                                 \
       const int nsl_ = (ij == ii) ? (TRF_NB(ii) >> 4) : 4;                                                  \
       const bool two_ = 2 * is + 1 < nsl_;                                                                  \
@@ -732,27 +762,31 @@ __device__ __forceinline__ void trf_strip(const double* X, const double* Dk, con
   // 2 hh + e of the lane's float4 of the A image.  C: the four row fragments x this wave's strip; R: this wave's fragment x the strips C0 <= c < NC
 #define TRF_MMA_C(TGT, AS, BS)                                                                              \
   {                                                                                                         \
-    float4_t a_[4];                                                                                          \
-    _Pragma("unroll") for (int i = 0; i < 4; ++i) a_[i] = *(const float4_t*)((AS) + i * 256 + ofa);         \
+    float4_t a_[NE][4];                                                                                      \
+    TRF_EDGES _Pragma("unroll") for (int i = 0; i < 4; ++i) a_[ed][i] = *(const float4_t*)((AS) + ed * AE + i * 256 + ofa); \
     _Pragma("unroll") for (int hh = 0; hh < 2; ++hh) {                                                      \
       const double2_t b_ = *(const double2_t*)((BS) + wc0 * 16 + of[hh]);                                   \
       _Pragma("unroll") for (int e = 0; e < 2; ++e) {                                                        \
         const float bf_ = (float)b_[e];                                                                      \
         _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                        \
-          TGT[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(bf_, a_[i][2 * hh + e], TGT[i], 0, 0, 0);           \
+          TRF_EDGES TGT[ed][i] = __builtin_amdgcn_mfma_f32_16x16x4f32(bf_, a_[ed][i][2 * hh + e], TGT[ed][i], 0, 0, 0); \
       }                                                                                                     \
     }                                                                                                       \
   }
 #define TRF_MMA_R(TGT, AS, BS, C0, NC)                                                                      \
   {                                                                                                         \
-    const float4_t a_ = *(const float4_t*)((AS) + wc0 * 16 + ofa);                                          \
+    float4_t a_[NE];                                                                                         \
+    TRF_EDGES a_[ed] = *(const float4_t*)((AS) + ed * AE + wc0 * 16 + ofa);                                 \
     _Pragma("unroll") for (int hh = 0; hh < 2; ++hh) {                                                      \
       double2_t b_[4];                                                                                       \
       _Pragma("unroll") for (int c = 0; c < 4; ++c)                                                          \
         if (c >= (C0) && c < (NC)) b_[c] = *(const double2_t*)((BS) + c * 256 + of[hh]);                    \
       _Pragma("unroll") for (int e = 0; e < 2; ++e) {                                                        \
         _Pragma("unroll") for (int c = 0; c < 4; ++c)                                                        \
-          if (c >= (C0) && c < (NC)) TGT[c] = __builtin_amdgcn_mfma_f32_16x16x4f32((float)b_[c][e], a_[2 * hh + e], TGT[c], 0, 0, 0); \
+          if (c >= (C0) && c < (NC)) {                                                                      \
+            const float bf_ = (float)b_[c][e];                                                               \
+            TRF_EDGES TGT[ed][c] = __builtin_amdgcn_mfma_f32_16x16x4f32(bf_, a_[ed][2 * hh + e], TGT[ed][c], 0, 0, 0); \
+          }                                                                                                 \
       }                                                                                                     \
     }                                                                                                       \
   }
@@ -764,10 +798,37 @@ __device__ __forceinline__ void trf_strip(const double* X, const double* Dk, con
   __syncthreads();
   TRF_ISSUE()
   if (DP > 2) TRF_ISSUE()
-  TRF_LOAD_C(0, acc0)
-  if (nt > 2) TRF_LOAD_C(1, acc1) else TRF_ZERO(acc1)
-  if (nt > 3) TRF_LOAD_C(2, acc2) else TRF_ZERO(acc2)
-  if (nt > 4) TRF_LOAD_C(3, acc3) else TRF_ZERO(acc3)
+  {
+    // E_0 .. E_3 of every edge: group g = (tile g / NE, edge g % NE); tile t > 0 exists if it is not the last one (nt > t + 1), else its set is zero
+    constexpr int NG = 4 * NE;
+    double2_t eb_[4][8];
+#define TRF_HAS(T) ((T) == 0 || nt > (T) + 1)
+#define TRF_FETCH_G(G) { if (TRF_HAS((G) / NE)) TRF_FETCH_C((G) / NE, (G) % NE, eb_[(G) & 3]) }
+#define TRF_CVT_G(G)                                                                                        \
+  {                                                                                                         \
+    const int t_ = (G) / NE, e_ = (G) % NE;                                                                 \
+    if (TRF_HAS(t_)) {                                                                                      \
+      if (t_ == 0) { TRF_CVT_C(acc0, e_, eb_[(G) & 3]) } else if (t_ == 1) { TRF_CVT_C(acc1, e_, eb_[(G) & 3]) }                  \
+      else if (t_ == 2) { TRF_CVT_C(acc2, e_, eb_[(G) & 3]) } else { TRF_CVT_C(acc3, e_, eb_[(G) & 3]) }                          \
+    } else {                                                                                                \
+      _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                        \
+        const float4_t z_ = (float4_t){0.f, 0.f, 0.f, 0.f};                                                  \
+        if (t_ == 1) acc1[e_][i] = z_; else if (t_ == 2) acc2[e_][i] = z_; else acc3[e_][i] = z_;            \
+      }                                                                                                     \
+    }                                                                                                       \
+  }
+#pragma unroll
+    for (int g = 0; g < 4; ++g) TRF_FETCH_G(g)
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+      __builtin_amdgcn_sched_barrier(0);                    // (the loads of group g + 4 are not hoisted above the conversion that frees their registers)
+      TRF_CVT_G(g)
+      if (g + 4 < NG) TRF_FETCH_G(g + 4)
+    }
+#undef TRF_CVT_G
+#undef TRF_FETCH_G
+#undef TRF_HAS
+  }
   TRF_PARK_C(acc0)                                          // T_0 = E_0 (the set holds -E_0)
   TRF_ZERO(acc0)
 #define TRF_STEP_BEGIN()                                                                                    \
@@ -842,16 +903,23 @@ __device__ __forceinline__ void trf_strip(const double* X, const double* Dk, con
 #undef TRF_PARK_C
 #undef TRF_STORE_R
 #undef TRF_LOAD_R
-#undef TRF_LOAD_C
+#undef TRF_CVT_C
+#undef TRF_FETCH_C
 #undef TRF_NB
+#undef TRF_EDGES
+#undef TRF_OPA
+#undef TRF_LANE
 }
 
 // The items of k_cr_trsm_dma for the problems with single-precision updates this iteration (cr_lowp) when the call has the float32 solves on (DF_LOWP_TRSM):
 // X_x = T[x,i] L_i^-T in float32 into the float32 O copy only; the fp64 O blocks of such a problem are neither written nor read in that iteration.
+// DF_TRSM_PAIR (default): one item per (problem, node, strip) -- both edges EA, EB of the node in one workgroup (trf_strip<2>), a node with one edge as
+// trf_strip<1>; the choice is workgroup-uniform.  Without the flag: the item list of k_cr_trsm_dma, one edge per workgroup.
 __global__ void __launch_bounds__(256, 2) k_cr_trsm_dma_f32(WS w, Dims dm, CrDev cr, int eoff, int nelim, int count) {
   const int dp = dm.dp;
   const int nst = (dp + 63) / 64;
-  const int per = 2 * nst;
+  const bool pair = (dm.flags & DF_TRSM_PAIR) != 0;         // one item per (problem, node, strip) with both edges; off: one per (problem, node, edge, strip)
+  const int per = pair ? nst : 2 * nst;
   const int it = cr_item(count * nelim * per);
   if (it < 0) return;
   extern __shared__ __attribute__((aligned(16))) double lds[];
@@ -859,15 +927,19 @@ __global__ void __launch_bounds__(256, 2) k_cr_trsm_dma_f32(WS w, Dims dm, CrDev
   const int b = cr.alist[g / nelim];
   if (!cr_lowp(w, b)) return;                               // this problem's solves run in fp64: k_cr_trsm_dma
   const int* er = cr.elim + (size_t)(eoff + g % nelim) * CR_EW;
-  const int which = r / nst, strip = r - which * nst;
-  const int slot = which ? er[CE_EB] : er[CE_EA];
-  if (slot < 0) return;
+  const int which = pair ? 0 : r / nst, strip = r - which * nst;
+  int s0 = which ? er[CE_EB] : er[CE_EA], s1 = pair ? er[CE_EB] : -1;        // (workgroup-uniform)
+  if (s0 < 0) { s0 = s1; s1 = -1; }
+  if (s0 < 0) return;
   const int node = er[CE_NODE];
   const double* Dk = w.D + ((size_t)b * dm.p + node) * (size_t)dp * dp;
   const double* Li = w.Linv + ((size_t)b * dm.p + node) * dm.nt * TB * TB;
-  const int r0 = strip * 64;
+  const int r0 = strip * 64, rows = (dp - r0 < 64) ? dp - r0 : 64;
   const int ld32 = cr_ld32(dm);
-  trf_strip(cr_edge(w, dm, b, slot) + (size_t)r0 * dp, Dk, Li, (dp - r0 < 64) ? dp - r0 : 64, dm.nt, dp, it, lds, cr_edge32(w, dm, b, slot) + (size_t)r0 * ld32, ld32);
+  const double* X0 = cr_edge(w, dm, b, s0) + (size_t)r0 * dp;
+  float* Y0 = cr_edge32(w, dm, b, s0) + (size_t)r0 * ld32;
+  if (s1 < 0) trf_strip<1>(X0, nullptr, Dk, Li, rows, dm.nt, dp, it, lds, Y0, nullptr, ld32);
+  else trf_strip<2>(X0, cr_edge(w, dm, b, s1) + (size_t)r0 * dp, Dk, Li, rows, dm.nt, dp, it, lds, Y0, cr_edge32(w, dm, b, s1) + (size_t)r0 * ld32, ld32);
 }
 
 // ---- phase 1 on the same sweep: block row r of the factor is the triangular solve of the row strip r of D against the rows above it,
