@@ -14,9 +14,9 @@
 extern "C" {
 #endif
 
-/* Debug bit for tmpc_set_options(flags): the solve stops after ASSEMBLING the Schur system of the first iteration, which then sits
- * unfactored in the workspace for tmpc_debug_get_array (tests/tools/step3_asm_check.py).  The outputs of such a call are NOT a
- * solution -- never set it in product code. */
+/* Debug bit for tmpc_set_options(flags): the solve stops after ASSEMBLING the Schur system of the first iteration (of iteration k after
+ * tmpc_debug_set_stop_iteration(h, k)), which then sits unfactored in the workspace for tmpc_debug_get_array (tests/tools/step3_asm_check.py,
+ * tests/test_gpu_schur_assembly.py).  The outputs of such a call are NOT a solution -- never set it in product code. */
 #define TMPC_DEBUG_FLAG_STOP_ASSEMBLED 8
 /* Debug bit: no relative lift of the Schur diagonal after frozen pivots (REG_MAX = 0): frozen pivots in the centering phase then go straight to the
  * route 'back mu_t off and take the step of this factorisation' (ctrl_backoff_before_rhs / k_ctrl_c), which the lifts make rare in practice
@@ -78,9 +78,23 @@ int tmpc_debug_cr_schedule(int p, int32_t* out, int cap);
  * directions, each [nb][p][nr]; any pointer may be NULL. */
 int tmpc_debug_get_multipliers(tmpc_handle* h, int nb, int nr, double* phi, double* z, double* dphi, double* dz);
 
-/* Raw workspace read-back for diagnostics: which = 0 psm, 1 pvec, 2 Ddiag, 3 D, 4 part, 5 O (edge slots 0..p-1), 6 F (fill slots);
- * `count` doubles from `offset` (no bounds check beyond the pointer being allocated). */
+/* Raw workspace read-back for diagnostics, LANE 0 ONLY (a handle made with tmpc_create_ex(..., lanes = 1) and chunk >= the batch keeps a whole call there):
+ * `count` doubles from `offset` of the array `which` (no bounds check beyond the pointer being allocated).  Shapes as in the workspace, B = problems of the chunk:
+ *   0 psm [B,p,nz*nz+6*nz]   1 pvec [B,p,2,nr,2n+2nx]   2 Ddiag [B,p,dp]   3 D [B,p,dp,dp]   4 part [B,p,26]   5 O [B,p,dp,dp] (edge slots 0..p-1)
+ *   6 F [B,p,dp,dp] (fill slots)   7 W3 [B,p,dp,3] (pass-1 right-hand sides: rhs | u_tau | u_alpha)   8 U [B,p,dp,2] (border columns tau, alpha)
+ *   the iterate and the scaled data:   9 X1   10 X2   11 S1   12 S2 [B,p,n,n]   13 P [B,p,nx,nx]   14 V = [A B] [B,p,nx,n]   15 Hb = s H [B,p,n,n]
+ *   the stage data of the iteration:   16 S1i   17 S2i   18 Rd1   19 Rd2   20 T1   21 T2 [B,p,n,n]
+ *   what the assembly kernels read and write:   22 KF [B,p,12,nx,nx] (Kronecker factors: XXX, SIXX, KX, KS, FX, FS of LMI 1, then of LMI 2)
+ *   23 adjV   24 adjE [B,p,3,nx,nx] (adjoint pieces: G = T1 - T2, Psi, PhiH)   25 Z [B,p,dp]   26 prob [B,48] (per-problem scalars: 0 tau, 1 alpha, 2 s0, 3 x0,
+ *   4 mu, 5 mu_t, 6 sigma mu, ...: the P_* enum of csrc/tmpc_common.h)   27 trace [B,80,10] (row i-1: iteration i as written by its k_ctrl_c: it, phase, mu, tau,
+ *   pinf, dinf, ap, ad, stepn, shifts)
+ * A code whose array this handle does not have is TMPC_E_ARG. */
 int tmpc_debug_get_array(tmpc_handle* h, int which, uint64_t offset, uint64_t count, double* out);
+
+/* With TMPC_DEBUG_FLAG_STOP_ASSEMBLED: stop at iteration k >= 1 instead of the first (the default, k = 1).  Iterations 1 .. k-1 run exactly as the solver runs them
+ * (launch sequence: the flag turns graph replay and the persistent kernel off for the call); iteration k runs k_stage_pre, k_ctrl_a, the assembly and the pass-1
+ * right-hand sides (k_stage_rhs, k_gather) and returns, so row k of the trace is not written yet.  Without the flag the value is not read. */
+int tmpc_debug_set_stop_iteration(tmpc_handle* h, int k);
 
 /* Smallest eigenvalue of nmat symmetric n x n matrices (Householder tridiagonalisation + Sturm multisection). */
 int tmpc_debug_min_eig(tmpc_handle* h, int nmat, int n, const double* W, double* out);

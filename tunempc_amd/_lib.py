@@ -34,7 +34,7 @@ EXPORTS = [
 DEBUG_EXPORTS = [
     'tmpc_debug_gemm_nt', 'tmpc_debug_block_solve', 'tmpc_debug_cr_schedule', 'tmpc_debug_get_multipliers', 'tmpc_debug_get_array',
     'tmpc_debug_min_eig', 'tmpc_debug_min_eig_lane', 'tmpc_debug_factor_bench', 'tmpc_debug_block_factor',
-    'tmpc_debug_last_trsm_pairs',
+    'tmpc_debug_last_trsm_pairs', 'tmpc_debug_set_stop_iteration',
 ]
 FLAG_DEBUG_NO_DMA = 32      # tunempc_hip_debug.h: TMPC_DEBUG_FLAG_NO_DMA
 # mode bits of tmpc_debug_block_factor (tunempc_hip_debug.h)
@@ -97,6 +97,8 @@ def load_library():
     lib.tmpc_debug_get_multipliers.argtypes = [vp, C.c_int, C.c_int, dp, dp, dp, dp]
     lib.tmpc_debug_get_array.restype = C.c_int
     lib.tmpc_debug_get_array.argtypes = [vp, C.c_int, C.c_uint64, C.c_uint64, dp]
+    lib.tmpc_debug_set_stop_iteration.restype = C.c_int
+    lib.tmpc_debug_set_stop_iteration.argtypes = [vp, C.c_int]
     lib.tmpc_convexify_con_batch_device.restype = C.c_int
     lib.tmpc_convexify_con_batch_device.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, C.c_double] + [vp] * 10 + [vp]
     lib.tmpc_convexify_step3_batch_device.restype = C.c_int
@@ -322,6 +324,10 @@ class HipConvexifier:
         out = np.empty(int(count))
         _check(self.lib, self.lib.tmpc_debug_get_array(self._h, int(which), int(offset), int(count), _dptr(out)), 'tmpc_debug_get_array')
         return out
+
+    def debug_set_stop_iteration(self, k):
+        """With flags=8 (TMPC_DEBUG_FLAG_STOP_ASSEMBLED): stop at the assembled system of iteration k (default 1); tunempc_hip_debug.h."""
+        _check(self.lib, self.lib.tmpc_debug_set_stop_iteration(self._h, int(k)), 'tmpc_debug_set_stop_iteration')
 
     def debug_multipliers(self, nb, nr):
         out = [np.empty((nb, self.p, nr)) for _ in range(4)]

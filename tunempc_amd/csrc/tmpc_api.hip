@@ -138,6 +138,7 @@ struct tmpc_handle {
   int nlanes;
   Opts opt;
   int flags;
+  int stop_it;      // TMPC_DEBUG_FLAG_STOP_ASSEMBLED: the iteration whose assembled system the call stops at (tmpc_debug_set_stop_iteration; 1 = the first)
   Lane lane[MAXL];
   void* slab;
   size_t slab_bytes;
@@ -870,7 +871,7 @@ static int run_chunk(tmpc_handle* h, Lane* ln, int nb, const double* dA, const d
     if (t3 && nfac > 0 && big) hipLaunchKernelGGL(k_t3_schur<true>, dim3(nfac * dm.p), dim3(256), t3_schur_lds, st, wf, dm);
     else if (t3 && nfac > 0) hipLaunchKernelGGL(k_t3_schur<false>, dim3(nfac * dm.p), dim3(256), t3_schur_lds, st, wf, dm);
     if (t3 && eq && nfac > 0) hipLaunchKernelGGL(k_t3_cross, dim3(nfac * dm.p), dim3(64), 0, st, wf, dm);
-    if (h->flags & TMPC_DEBUG_FLAG_STOP_ASSEMBLED) {   // debug (tunempc_hip_debug.h; tests/tools/step3_asm_check.py): stop with the assembled, unfactored system of the first iteration in the workspace
+    if ((h->flags & TMPC_DEBUG_FLAG_STOP_ASSEMBLED) && it + 1 >= h->stop_it) {   // debug (tunempc_hip_debug.h; tests/tools/step3_asm_check.py, tests/test_gpu_schur_assembly.py): stop with the assembled, unfactored system of iteration stop_it (default: the first) in the workspace
       if (big) hipLaunchKernelGGL(kb_stage_rhs, dim3(BP), dim3(256), 0, st, w, dm, 1);
       else TMPC_STAGE_LAUNCH(k_stage_rhs, slots_bytes(RHS_SLOTS), st, w, dm, 1);
       if (t3) hipLaunchKernelGGL(k_t3_rhs, dim3(BP), dim3(64), t3_lds, st, w, dm, 1);
@@ -1159,7 +1160,7 @@ static int create_handle(tmpc_handle** out, int chunk, int p, int nx, int mb, in
   h->opt.fast_exit = 0;
   h->opt.lowp_switch = TMPC_LOWP_SWITCH_DEFAULT;
   h->opt.chord_step = 10.0;       // centering: re-use the factorisation once the iterate moves by < 1/10 in the local norm (profiles/r2z_chord_default.txt: +3.7 %, same answers to 1e-10); tmpc_set_tuning(TMPC_TUNE_CHORD_STEP, 0) disables
-  h->flags = 0;
+  h->flags = 0; h->stop_it = 1;
   WS tmp;
   const size_t lane_bytes = carve(tmp, h->dm, nullptr, nullptr);
   h->slab_bytes = lane_bytes * nl;
@@ -1366,10 +1367,35 @@ int tmpc_debug_get_array(tmpc_handle* h, int which, uint64_t offset, uint64_t co
     case 6: src = ws.F; break;
     case 7: src = ws.W3; break;
     case 8: src = ws.U; break;
+    case 9: src = ws.X1; break;
+    case 10: src = ws.X2; break;
+    case 11: src = ws.S1; break;
+    case 12: src = ws.S2; break;
+    case 13: src = ws.P; break;
+    case 14: src = ws.V; break;
+    case 15: src = ws.Hb; break;
+    case 16: src = ws.S1i; break;
+    case 17: src = ws.S2i; break;
+    case 18: src = ws.Rd1; break;
+    case 19: src = ws.Rd2; break;
+    case 20: src = ws.T1; break;
+    case 21: src = ws.T2; break;
+    case 22: src = ws.KF; break;
+    case 23: src = ws.adjV; break;
+    case 24: src = ws.adjE; break;
+    case 25: src = ws.Z; break;
+    case 26: src = ws.prob; break;
+    case 27: src = ws.trace; break;
     default: return TMPC_E_ARG;
   }
   if (!src) return TMPC_E_ARG;
   HIPCHK(hipMemcpy(out, src + offset, count * sizeof(double), hipMemcpyDeviceToHost));
+  return TMPC_OK;
+}
+
+int tmpc_debug_set_stop_iteration(tmpc_handle* h, int k) {
+  if (!h || k < 1) return TMPC_E_ARG;
+  h->stop_it = k;
   return TMPC_OK;
 }
 
