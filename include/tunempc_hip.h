@@ -402,10 +402,11 @@ int tmpc_closed_loop_batch_device(int nb, int p, int nx, int mb, int nr, int ng,
  *     min  sum_{j<N} (1/2 z_j' H_k z_j + q_k' z_j) + 1/2 x_N' Pf_{k_N} x_N,   z_j = [x_j; u_j],   k = k_j = (k0 + j) mod p,
  *     s.t. x_{j+1} = A_k x_j + B_k u_j,  x_0 given,   D_k z_j <= d_k (first ndcnt_k rows of the stage),   j = 0 .. N-1,
  * solved at the steps t = 0 .. T-1 from the phase (k0 + t) mod p; u_0 is applied and x <- A_k x + B_k u_0 (the linear plant), one launch for the whole batch.
- * Not served (there are no arguments for them): quadratic slack penalties, warm starts between steps, the nonlinear plant, nt > nx.
+ * Not served (there are no arguments for them): warm starts between steps, the nonlinear plant, nt > nx.
  * Soft rows (exact L1 slack penalties, the reference's `usc`): the tmpc_mpc_qp_soft_batch_* entries below.  Equality rows J z = r and the terminal
  * constraint Tx x_N = 0 (the reference's g and p_operator): the tmpc_mpc_qp_eq_batch_* entries below.  The affine problem (a dynamics offset, a linear
- * terminal cost, a terminal right-hand side, a plant that is not the model, a disturbance): the tmpc_mpc_qp_aff_batch_* entries below.
+ * terminal cost, a terminal right-hand side, a plant that is not the model, a disturbance): the tmpc_mpc_qp_aff_batch_* entries below.  Quadratic slack
+ * penalties (1/2 Z e^2 alone or beside the L1 term): the tmpc_mpc_qp_quad_batch_* entries below.
  * Method: primal-dual interior point with Mehrotra's predictor-corrector, started infeasible, the Newton system solved by a Riccati pass with a Cholesky
  * factorisation per stage; the stop rule is r_p <= tol, r_d <= tol, mu <= 1e-3 tol max(1, max lam), residuals relative to the scale of the problem (stated
  * in tmpc_mpc_qp.h and in tests/mpc_qp_reference.py).  H is used as (H + H') / 2, likewise Pf.
@@ -508,6 +509,36 @@ int tmpc_mpc_qp_aff_batch_device(int nb, int p, int nx, int mb, int nd, int N, i
                                  double* Xol, double* Uol, double* Lam, const double* penalty, double* Eol, int32_t* nviol, int ne, const double* J,
                                  const double* r, const int32_t* necnt, int nt, const double* Tx, double* Nu, double* NuT, double* eres, const double* offset,
                                  const double* qf, const double* terminal_rhs, const double* Ap, const double* Bp, const double* cp, const double* W);
+
+/* The same step and loop with QUADRATIC slack penalties (the Zl / Zu of an OCP-QP beside its zl / zu): the 50 arguments of the aff entries, then
+ *   penalty2 [nb][p][nd]: the L2 weight Z >= 0 of every row beside its L1 weight c = penalty.  Per row of a stage:
+ *     c = +inf, Z = 0     a hard row;
+ *     c > 0,    Z = 0     the soft row of the soft entries: their statements, their bits;
+ *     c > 0,    Z > 0     D_i z - e <= d_i, e >= 0, cost c e + 1/2 Z e^2: two complementarity pairs, stationarity in e is c + Z e - lam - nu = 0;
+ *     c = 0,    Z > 0     pure quadratic: D_i z - e <= d_i, cost 1/2 Z e^2, ONE pair (e = lam / Z >= 0 by itself): a hard row whose dual regularisation
+ *                         rho + 1 / Z is exact instead of vanishing.
+ * penalty is required with penalty2 (all zeros: every row pure quadratic).  Eol holds the slack of every soft row (lam / Z on a pure row); nviol counts the
+ * two-pair rows with e > nu and the pure rows with lam > s (on a pure row active means violated); nact stays lam > s and hres max(D z - d).  The rules of the
+ * iteration are stated in tmpc_mpc_qp.h and in tests/mpc_qp_quad_reference.py.  The kernels are QUAD instantiations of the plain soft kernel (a call without
+ * equality, terminal or affine arguments) and of the soft AFF kernel (every other call); Z of the stage takes 8 nd bytes of LDS after the soft layout, the
+ * workspace is the soft one.  With penalty2 NULL the aff entry runs (the same bits).
+ * TMPC_E_ARG, besides the above: penalty2 without penalty; (host entry) a penalty2 that is negative, non-finite or NaN, or non-zero on a hard row; a penalty
+ * that is negative or NaN, or 0 beside penalty2 = 0: each named in the message.  On the device entry any of these makes the instances of that problem status 3
+ * before their first step.  TMPC_E_UNSUPPORTED: the layout with Z beyond 160 KB, with the byte count. */
+int tmpc_mpc_qp_quad_batch_host(int nb, int p, int nx, int mb, int nd, int N, int ns, int T, int k0, const double* A, const double* B, const double* H,
+                                const double* q, const double* Pf, const double* D, const int32_t* ndcnt, const double* d, const double* X0, double tol,
+                                int max_iter, double* U0, double* XT, double* info, double* X, double* U, int32_t* iters, int32_t* nact, double* hres,
+                                double* Xol, double* Uol, double* Lam, const double* penalty, double* Eol, int32_t* nviol, int ne, const double* J,
+                                const double* r, const int32_t* necnt, int nt, const double* Tx, double* Nu, double* NuT, double* eres, const double* offset,
+                                const double* qf, const double* terminal_rhs, const double* Ap, const double* Bp, const double* cp, const double* W,
+                                const double* penalty2);
+int tmpc_mpc_qp_quad_batch_device(int nb, int p, int nx, int mb, int nd, int N, int ns, int T, int k0, const double* A, const double* B, const double* H,
+                                  const double* q, const double* Pf, const double* D, const int32_t* ndcnt, const double* d, const double* X0, double tol,
+                                  int max_iter, double* U0, double* XT, double* info, double* X, double* U, int32_t* iters, int32_t* nact, double* hres,
+                                  double* Xol, double* Uol, double* Lam, const double* penalty, double* Eol, int32_t* nviol, int ne, const double* J,
+                                  const double* r, const int32_t* necnt, int nt, const double* Tx, double* Nu, double* NuT, double* eres, const double* offset,
+                                  const double* qf, const double* terminal_rhs, const double* Ap, const double* Bp, const double* cp, const double* W,
+                                  const double* penalty2);
 
 /* Accumulated hipEvent timings since the last call (ms) when TMPC_FLAG_PROFILE is set, 16 doubles:
  * out[0] stage_pre+ctrl, [1] schur assembly, [2] block factorisation (all kernels of tmpc_cr.h's factor phase), [3] predictor

@@ -1,11 +1,13 @@
 """sha256 of the raw outputs (u0, X, U, lam, info) of the fixed cases of tests/mpc_qp_reference.py through mpc_qp_batch and mpc_closed_loop_batch WITHOUT penalty,
 host and device entry, for comparing two builds of the library bit for bit -- the hard path of csrc/tmpc_mpc_qp.h must not move when the kernel grows:
 
-    python scripts/mpc_qp_digest.py [--all] [--tree path/to/another/checkout]      (the package and its built library are taken from that tree; the cases from this one)
+    python scripts/mpc_qp_digest.py [--all] [--quad] [--tree path/to/another/checkout]      (the package and its built library are taken from that tree; the cases from this one)
 
 --all adds the fixed cases of tests/mpc_qp_soft_reference.py (every variant, with its penalty), tests/mpc_qp_eq_reference.py (with J, r, necnt, terminal, penalty)
 and tests/mpc_qp_affine_reference.py (with offset, qf, terminal_rhs, and the loop with a plant and a disturbance), EVERY key of the returned dicts hashed: the
-soft, eq and aff entries next to the hard ones, for a change of the host code around the kernel.
+soft, eq and aff entries next to the hard ones, for a change of the host code around the kernel.  --quad adds the fixed cases of
+tests/mpc_qp_quad_reference.py (every variant and the three infeasible starts, with penalty and penalty2) through the quad entries, under a total of their
+own (`quad`): the `all` line stays comparable with a build that has no penalty2.
 """
 import argparse
 import hashlib
@@ -19,6 +21,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ap = argparse.ArgumentParser()
 ap.add_argument('--tree', default=ROOT)
 ap.add_argument('--all', action='store_true')
+ap.add_argument('--quad', action='store_true')
 args = ap.parse_args()
 sys.path.insert(0, os.path.abspath(args.tree))
 sys.path.insert(1, os.path.join(ROOT, 'tests'))
@@ -72,8 +75,16 @@ def batches():
     yield 'aff loop_plant', dict(af.batch_of(c), plant=plant, disturbance=W)
 
 
-if args.all:
-    for name, bt in batches():
+def quad_batches():
+    import mpc_qp_quad_reference as qq
+    for (kind, case, f, zeta, hard_first), name in zip(qq.VARIANTS, qq.VARIANT_IDS):
+        yield 'quad ' + name, qq.batch_of(qq.instances(kind, case, f, zeta, hard_first))
+    for c, Z in qq.INFEASIBLE:
+        yield 'quad infeasible c%g Z%g' % (c, Z), qq.batch_of([qq.infeasible_instance(c, Z)])
+
+
+def hash_batches(gen, total):
+    for name, bt in gen:
         line = []
         for entry in ('host', 'device'):
             f = (lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()) if entry == 'device' else np.ascontiguousarray
@@ -85,4 +96,12 @@ if args.all:
                 line.append(dig(o, sorted(k for k, v in o.items() if v is not None)))
         total.update(' '.join(line).encode())
         print('%-40s N %d  step host %s  loop host %s  step device %s  loop device %s' % (name, bt['N'], *line), flush=True)
+
+
+if args.all:
+    hash_batches(batches(), total)
 print('all', total.hexdigest())
+if args.quad:
+    qtotal = hashlib.sha256()
+    hash_batches(quad_batches(), qtotal)
+    print('quad', qtotal.hexdigest())

@@ -27,7 +27,7 @@ EXPORTS = [
     'tmpc_periodic_lqr_ctg_batch_host', 'tmpc_periodic_lqr_ctg_batch_device', 'tmpc_horizon_lqr_batch_host', 'tmpc_horizon_lqr_batch_device',
     'tmpc_closed_loop_batch_host', 'tmpc_closed_loop_batch_device', 'tmpc_mpc_qp_batch_host', 'tmpc_mpc_qp_batch_device',
     'tmpc_mpc_qp_soft_batch_host', 'tmpc_mpc_qp_soft_batch_device', 'tmpc_mpc_qp_eq_batch_host', 'tmpc_mpc_qp_eq_batch_device',
-    'tmpc_mpc_qp_aff_batch_host', 'tmpc_mpc_qp_aff_batch_device',
+    'tmpc_mpc_qp_aff_batch_host', 'tmpc_mpc_qp_aff_batch_device', 'tmpc_mpc_qp_quad_batch_host', 'tmpc_mpc_qp_quad_batch_device',
     'tmpc_last_error', 'tmpc_version',
 ]
 # ... and in include/tunempc_hip_debug.h (unit-test / diagnostic entries)
@@ -167,6 +167,10 @@ def load_library():
     lib.tmpc_mpc_qp_aff_batch_host.argtypes = lib.tmpc_mpc_qp_eq_batch_host.argtypes + [dp] * 7
     lib.tmpc_mpc_qp_aff_batch_device.restype = C.c_int
     lib.tmpc_mpc_qp_aff_batch_device.argtypes = lib.tmpc_mpc_qp_eq_batch_device.argtypes + [vp] * 7
+    lib.tmpc_mpc_qp_quad_batch_host.restype = C.c_int
+    lib.tmpc_mpc_qp_quad_batch_host.argtypes = lib.tmpc_mpc_qp_aff_batch_host.argtypes + [dp]
+    lib.tmpc_mpc_qp_quad_batch_device.restype = C.c_int
+    lib.tmpc_mpc_qp_quad_batch_device.argtypes = lib.tmpc_mpc_qp_aff_batch_device.argtypes + [vp]
     lib.tmpc_get_profile.restype = C.c_int
     lib.tmpc_get_profile.argtypes = [vp, dp]
     lib.tmpc_get_trace.restype = C.c_int
@@ -957,14 +961,14 @@ def _mpc_qp_eq_terminal(Tx, nx):
     return int(Tx.shape[2]), Tx, int(Tx.shape[2])
 
 
-_MPC_QP_LEVELS = {'hard': '', 'soft': 'soft_', 'eq': 'eq_', 'aff': 'aff_'}
+_MPC_QP_LEVELS = {'hard': '', 'soft': 'soft_', 'eq': 'eq_', 'aff': 'aff_', 'quad': 'quad_'}
 
 
 def _mpc_qp_call(level, kind, A, B, H, q, Pf, D, ndcnt, d, X0, N, T, k0, tol, max_iter, return_traj, return_ol, penalty=None, J=None, r=None, necnt=None,
-                 Tx=None, aff=None):
-    """The eight MPC QP entries: tmpc_mpc_qp_<level>batch_<host or device> of the level 'hard', 'soft', 'eq' or 'aff' on validated, contiguous arrays of `kind`
+                 Tx=None, aff=None, penalty2=None):
+    """The ten MPC QP entries: tmpc_mpc_qp_<level>batch_<host or device> of the level 'hard', 'soft', 'eq', 'aff' or 'quad' on validated, contiguous arrays of `kind`
     (_HostArrays: numpy, _DeviceArrays: torch tensors of one GPU).  Allocates the outputs, passes the 31 common arguments and the tails of the level (soft:
-    penalty, Eol, nviol; eq: the rows and Nu, NuT, eres; aff: the seven arrays), an absent or empty array as NULL, and returns the dict of the level.  The
+    penalty, Eol, nviol; eq: the rows and Nu, NuT, eres; aff: the seven arrays; quad: penalty2), an absent or empty array as NULL, and returns the dict of the level.  The
     library stores the logs time-major: X, U and the per-step logs are permuted views, nothing is copied."""
     lib = load_library()
     xp = kind(A)
@@ -974,7 +978,7 @@ def _mpc_qp_call(level, kind, A, B, H, q, Pf, D, ndcnt, d, X0, N, T, k0, tol, ma
     nd = 0 if D is None else D.shape[2]
     ne = 0 if J is None else J.shape[2]
     nt, Txa, ntr = _mpc_qp_eq_terminal(Tx, nx)
-    eq = level in ('eq', 'aff')
+    eq = level in ('eq', 'aff', 'quad')
     soft = level == 'soft' or (eq and penalty is not None)                  # (the eq level without penalty passes Eol = nviol = NULL)
     traj = lambda *sh: xp.f64(*sh) if return_traj else None
     ol = lambda *sh: xp.f64(*sh) if return_ol else None
@@ -992,8 +996,10 @@ def _mpc_qp_call(level, kind, A, B, H, q, Pf, D, ndcnt, d, X0, N, T, k0, tol, ma
         args += [ptr(penalty), ptr(Eol), ptr(nviol)]
     if eq:
         args += [ne, rows(J, ne), rows(r, ne), rows(necnt, ne), nt, ptr(Txa), ptr(Nu), ptr(NuT), ptr(eres)]
-    if level == 'aff':
-        args += [ptr(a) for a in aff]
+    if level in ('aff', 'quad'):
+        args += [ptr(a) for a in (aff if aff is not None else (None,) * 7)]
+    if level == 'quad':
+        args += [ptr(penalty2)]
     rc = xp.call(getattr(lib, name), args)
     if rc == -1:      # TMPC_E_ARG: the library's message names the argument
         raise ValueError(lib.tmpc_last_error().decode())
@@ -1072,3 +1078,16 @@ def cr_schedule(p):
     elim = buf[o:o + 8 * ne].reshape(ne, 8); o += 8 * ne
     upd = buf[o:o + 8 * nu].reshape(nu, 8); o += 8 * nu
     return dict(prep=prep, levels=levels, elim=elim, upd=upd, orient=buf[o:o + p].copy())
+
+
+def mpc_qp_quad_batch_host(A, B, H, q, Pf, D, ndcnt, d, penalty, J, r, necnt, Tx, aff, penalty2, X0, N, T, k0, tol, max_iter, return_traj, return_ol):
+    """tmpc_mpc_qp_quad_batch_host on validated, contiguous numpy arrays: the arguments of mpc_qp_aff_batch_host (aff None: no affine array) and penalty2
+    [nb,p,nd] -> the dict of mpc_qp_eq_batch_host (Eol: lam / Z on the pure quadratic rows)."""
+    return _mpc_qp_call('quad', _HostArrays, A, B, H, q, Pf, D, ndcnt, d, X0, N, T, k0, tol, max_iter, return_traj, return_ol, penalty, J, r, necnt, Tx,
+                        None if aff is None else tuple(aff), penalty2)
+
+
+def mpc_qp_quad_batch_device(A, B, H, q, Pf, D, ndcnt, d, penalty, J, r, necnt, Tx, aff, penalty2, X0, N, T, k0, tol, max_iter, return_traj, return_ol):
+    """tmpc_mpc_qp_quad_batch_device on validated, contiguous torch tensors of one GPU -> the dict of mpc_qp_quad_batch_host with torch tensors."""
+    return _mpc_qp_call('quad', _DeviceArrays, A, B, H, q, Pf, D, ndcnt, d, X0, N, T, k0, tol, max_iter, return_traj, return_ol, penalty, J, r, necnt, Tx,
+                        None if aff is None else tuple(aff), penalty2)

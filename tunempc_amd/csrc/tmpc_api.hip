@@ -2206,14 +2206,14 @@ int tmpc_closed_loop_batch_host(int nb, int p, int nx, int mb, int nr, int ng, i
 
 // The inequality-constrained MPC step and closed loop (tmpc_mpc_qp.h): one workgroup per instance (problem, initial state), min(instances, MQ_SLOTS) workgroups
 // loop over the instances, each with its slot of the workspace.
-// The eight entries (hard, soft, eq, aff; host and device) differ in their argument lists only.  An entry writes its arguments into an MpcQpCall (what it has no
+// The ten entries (hard, soft, eq, aff, quad; host and device) differ in their argument lists only.  An entry writes its arguments into an MpcQpCall (what it has no
 // argument for stays null / zero) and hands the record to mpc_qp_host or mpc_qp_device.  Either checks it once under the entry's name (mpc_qp_validate), reads
 // the kernel off it with its LDS and workspace sizes (mpc_qp_kind), zeroes the outputs that this kernel does not write (mpc_qp_zero_unwritten) and launches
 // (mpc_qp_launch); the host path stages every array of the record through one device buffer.  No entry calls another.
 static_assert(MQ_INFO == TMPC_MPC_QP_INFO, "tunempc_hip.h: info stride of the MPC QP entries");
 constexpr long long MQ_WS_CAP_BYTES = 1LL << 30;      // the workspace of a launch: fewer slots beyond this (one slot at the least)
 
-// One call: the arguments of the aff entries (the longest list) in their order; nt as the caller gave it (-1: x_N = 0 without Tx, nx rows).  The pointers are
+// One call: the arguments of the quad entries (the longest list) in their order; nt as the caller gave it (-1: x_N = 0 without Tx, nx rows).  The pointers are
 // the caller's, host or device by the path; mpc_qp_host launches a copy that holds the device images.
 struct MpcQpCall {
   const char* who;
@@ -2225,30 +2225,34 @@ struct MpcQpCall {
   int ne = 0; const double* J = nullptr; const double* r = nullptr; const int32_t* necnt = nullptr; int nt = 0; const double* Tx = nullptr;      // the eq entries
   double* Nu = nullptr; double* NuT = nullptr; double* eres = nullptr;
   MpcQpAff aff = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};                                                      // the aff entries
+  const double* penalty2 = nullptr;                                                                                                    // the quad entries
   int ntk() const { return nt < 0 ? nx : nt; }      // terminal rows of the kernel
 };
 #define MPC_QP_ARGS31 nb, p, nx, mb, nd, N, ns, T, k0, A, B, H, q, Pf, D, ndcnt, d, X0, tol, max_iter, U0, XT, info, X, U, iters, nact, hres, Xol, Uol, Lam
 
 // The kernel of a call: SOFT with a penalty; EQ with equality rows, terminal rows or an affine array; AFF (an instantiation of the two EQ kernels only) with an
-// affine array.  Sizes in doubles: the LDS of the hard layout, of the soft layout (the hard one without penalty) and of the kernel that runs -- the layouts
+// affine array; QUAD (an instantiation of the plain SOFT kernel and of the SOFT AFF kernel only, the latter for every call with rows or an affine array)
+// with a penalty2.  Sizes in doubles: the LDS of the hard layout, of the soft layout (the hard one without penalty) and of the kernel that runs -- the layouts
 // nest, the three LDS tests of mpc_qp_validate tell which part no longer fits --, and the workspace per slot.  Row capacities enter the LDS sizes clamped to
 // 65536 (no 32-bit overflow before they are refused; a call that passes the checks is far below).
-struct MpcQpKind { bool soft, eq, aff; long long lds_hard, lds_soft, lds, ws; };
+struct MpcQpKind { bool soft, eq, aff, quad; long long lds_hard, lds_soft, lds, ws; };
 static bool mpc_qp_aff_any(const MpcQpAff& a) { return a.c || a.qf || a.t || a.Ap || a.Bp || a.cp || a.W; }
 static MpcQpKind mpc_qp_kind(const MpcQpCall& c) {
   MpcQpKind k;
   k.soft = c.penalty != nullptr;
+  k.quad = k.soft && c.penalty2 != nullptr;
   k.aff = mpc_qp_aff_any(c.aff);
   k.eq = c.ne > 0 || c.nt != 0 || k.aff;
   const int nd = c.nd < 65536 ? c.nd : 65536, ne = c.ne < 65536 ? c.ne : 65536;
   k.lds = k.lds_soft = k.lds_hard = mpc_qp_lds(c.nx, c.mb, nd).total;
   k.ws = mpc_qp_ws_doubles(c.nx, c.mb, c.nd, c.N);
   if (k.soft) { k.lds = k.lds_soft = mpc_qp_soft_lds(c.nx, c.mb, nd).total; k.ws = mpc_qp_soft_ws_doubles(c.nx, c.mb, c.nd, c.N); }
-  if (k.eq) { k.lds = mpc_qp_eq_lds(c.nx, c.mb, nd, ne, k.soft).total; k.ws = mpc_qp_eq_ws_doubles(c.nx, c.mb, c.nd, c.N, c.ne, c.ntk(), k.soft); }
+  if (k.quad) k.lds = k.lds_soft = mpc_qp_quad_layout(c.nx, c.mb, nd).total;
+  if (k.eq) { k.lds = (k.quad ? mpc_qp_quad_eq_layout(c.nx, c.mb, nd, ne) : mpc_qp_eq_lds(c.nx, c.mb, nd, ne, k.soft)).total; k.ws = mpc_qp_eq_ws_doubles(c.nx, c.mb, c.nd, c.N, c.ne, c.ntk(), k.soft); }
   return k;
 }
 
-// Every check that needs no device, in the order base, soft, eq, aff, under the name of the entry that was called; *kind on success.  The eq and aff parts
+// Every check that needs no device, in the order base, soft and quad, eq, aff, under the name of the entry that was called; *kind on success.  The eq and aff parts
 // run for every entry: with ne = 0, nt = 0 and none of their pointers (all that the hard and soft entries can state) they cannot fail.
 static int mpc_qp_validate(const MpcQpCall& c, MpcQpKind* kind) {
   const char* who = c.who;
@@ -2287,6 +2291,10 @@ static int mpc_qp_validate(const MpcQpCall& c, MpcQpKind* kind) {
   // soft rows
   if (k.soft && nd < 1) {
     snprintf(g_err, sizeof(g_err), "%s: bad argument (penalty describes the rows of D; got nd = %d)", who, nd);
+    return TMPC_E_ARG;
+  }
+  if (c.penalty2 && !c.penalty) {
+    snprintf(g_err, sizeof(g_err), "%s: bad argument (penalty2 stands beside penalty, which is null: pass 0 there for a pure quadratic row)", who);
     return TMPC_E_ARG;
   }
   if (k.lds_soft * 8 > LQR_LDS_BYTES) {
@@ -2331,15 +2339,29 @@ static int mpc_qp_validate(const MpcQpCall& c, MpcQpKind* kind) {
   return TMPC_OK;
 }
 
-// Host entries only: the counts within their capacity and every penalty > 0 (NaN fails), the offending element named.
+// Host entries only: the counts within their capacity and every penalty > 0 (NaN fails), the offending element named.  With penalty2: every entry of it
+// finite and >= 0 and 0 on a hard row, and penalty = 0 allowed where penalty2 > 0 (a pure quadratic row).
 static int mpc_qp_host_ranges(const char* who, size_t nb, size_t p, const int32_t* cnt, int cap, const char* cnt_name, const char* cap_name, const double* penalty,
-                              int nd) {
+                              int nd, const double* penalty2 = nullptr) {
   const size_t st = nb * p;
   if (cnt) for (size_t i = 0; i < st; ++i) if (cnt[i] < 0 || cnt[i] > cap) {
     snprintf(g_err, sizeof(g_err), "%s: %s[%zu][%zu] = %d outside 0 .. %s = %d", who, cnt_name, i / p, i % p, (int)cnt[i], cap_name, cap);
     return TMPC_E_ARG;
   }
-  if (penalty) for (size_t i = 0; i < st * nd; ++i) if (!(penalty[i] > 0.0)) {
+  if (penalty && penalty2) for (size_t i = 0; i < st * nd; ++i) {
+    const double c = penalty[i], z = penalty2[i];
+    if (!(z >= 0.0 && z < INFINITY) || (c == INFINITY && z != 0.0)) {
+      snprintf(g_err, sizeof(g_err), "%s: penalty2[%zu][%zu][%zu] = %g: finite and >= 0 expected, 0 on a hard row (penalty = %g)", who, i / nd / p, i / nd % p, i % nd,
+               z, c);
+      return TMPC_E_ARG;
+    }
+    if (!(c > 0.0 || (c == 0.0 && z > 0.0))) {
+      snprintf(g_err, sizeof(g_err), "%s: penalty[%zu][%zu][%zu] = %g: > 0 expected (+inf: a hard row), or 0 beside a penalty2 > 0 (got %g)", who, i / nd / p,
+               i / nd % p, i % nd, c, z);
+      return TMPC_E_ARG;
+    }
+  }
+  if (penalty && !penalty2) for (size_t i = 0; i < st * nd; ++i) if (!(penalty[i] > 0.0)) {
     snprintf(g_err, sizeof(g_err), "%s: penalty[%zu][%zu][%zu] = %g: > 0 expected (+inf: a hard row)", who, i / nd / p, i / nd % p, i % nd, penalty[i]);
     return TMPC_E_ARG;
   }
@@ -2365,11 +2387,12 @@ static thread_local EigScratch g_mpc_qp_ws;           // workspace slots of all 
 
 // c: a checked call of mpc_qp_kernel_call with device pointers
 static int mpc_qp_launch(const MpcQpCall& c, const MpcQpKind& k) {
-  using Kernel = decltype(&k_mpc_qp<false, false, false>);
-  static const Kernel kernels[3][2] = {{k_mpc_qp<false, false, false>, k_mpc_qp<true, false, false>},      // [eq + aff][soft]
-                                       {k_mpc_qp<false, true, false>, k_mpc_qp<true, true, false>},
-                                       {k_mpc_qp<false, true, true>, k_mpc_qp<true, true, true>}};
-  const Kernel kern = kernels[(int)k.eq + (int)k.aff][(int)k.soft];
+  using Kernel = decltype(mpc_qp_kernel<false, false, false>());
+  static const Kernel quad_kernels[2] = {k_mpc_qp<true, false, false, true>, k_mpc_qp<true, true, true, true>};      // [eq or aff]
+  static const Kernel kernels[3][2] = {{mpc_qp_kernel<false, false, false>(), mpc_qp_kernel<true, false, false>()},      // [eq + aff][soft]
+                                       {mpc_qp_kernel<false, true, false>(), mpc_qp_kernel<true, true, false>()},
+                                       {mpc_qp_kernel<false, true, true>(), mpc_qp_kernel<true, true, true>()}};
+  const Kernel kern = k.quad ? quad_kernels[(int)k.eq] : kernels[(int)k.eq + (int)k.aff][(int)k.soft];
   const long long ninst = (long long)c.nb * c.ns, per = k.ws * 8;
   long long slots = ninst < MQ_SLOTS ? ninst : MQ_SLOTS;
   if (slots * per > MQ_WS_CAP_BYTES) slots = MQ_WS_CAP_BYTES / per;
@@ -2381,7 +2404,7 @@ static int mpc_qp_launch(const MpcQpCall& c, const MpcQpKind& k) {
   hipLaunchKernelGGL(kern, dim3((unsigned)slots), dim3(LQR_NT), (size_t)k.lds * sizeof(double), 0, c.p, c.nx, c.mb, c.nd, lcw, c.N, c.ns, c.T, c.k0, ninst, c.A, c.B,
                      c.H, c.q, c.Pf, c.D, (const int*)c.ndcnt, c.d, c.X0, c.tol, c.max_iter, (double*)g_mpc_qp_ws.p, c.U0, c.XT, c.info, c.X, c.U, (int*)c.iters,
                      (int*)c.nact, c.hres, c.Xol, c.Uol, c.Lam, c.penalty, c.Eol, (int*)c.nviol, c.ne, c.J, c.r, (const int*)c.necnt, c.ntk(), c.Tx, c.Nu, c.NuT,
-                     c.eres, c.aff);
+                     c.eres, c.aff, c.penalty2);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(0));
   return TMPC_OK;
@@ -2402,7 +2425,7 @@ static thread_local EigScratch g_mpc_qp_scratch;      // device images of the ho
 static int mpc_qp_host(const MpcQpCall& c) {
   MpcQpKind k;
   int rc = mpc_qp_validate(c, &k);
-  if (rc == TMPC_OK) rc = mpc_qp_host_ranges(c.who, c.nb, c.p, c.ndcnt, c.nd, "ndcnt", "nd", c.penalty, c.nd);
+  if (rc == TMPC_OK) rc = mpc_qp_host_ranges(c.who, c.nb, c.p, c.ndcnt, c.nd, "ndcnt", "nd", c.penalty, c.nd, c.penalty2);
   if (rc == TMPC_OK) rc = mpc_qp_host_ranges(c.who, c.nb, c.p, c.necnt, c.ne, "necnt", "ne", nullptr, 0);
   if (rc != TMPC_OK) return rc;
   // every array that is given and not empty gets an image in one device buffer, 8-byte aligned, in the order of the arguments; dc is the call on the images
@@ -2434,6 +2457,7 @@ static int mpc_qp_host(const MpcQpCall& c) {
     place(dc.Nu, sn * N * ne * 8, true); place(dc.NuT, sn * ntk * 8, true); place(dc.eres, cS * 8, true);
     place(dc.aff.c, st * nx * 8, false); place(dc.aff.qf, st * nx * 8, false); place(dc.aff.t, st * ntk * 8, false); place(dc.aff.Ap, st * nx * nx * 8, false);
     place(dc.aff.Bp, st * nx * mb * 8, false); place(dc.aff.cp, st * nx * 8, false); place(dc.aff.W, cS * nx * 8, false);
+    place(dc.penalty2, st * nd * 8, false);
   };
   arrays();
   HIPCHK(g_mpc_qp_scratch.reserve(total + 8));
@@ -2513,6 +2537,30 @@ int tmpc_mpc_qp_aff_batch_host(int nb, int p, int nx, int mb, int nd, int N, int
                                const double* qf, const double* terminal_rhs, const double* Ap, const double* Bp, const double* cp, const double* W) {
   return mpc_qp_host(MpcQpCall{"tmpc_mpc_qp_aff_batch_host", MPC_QP_ARGS31, penalty, Eol, nviol, ne, J, r, necnt, nt, Tx, Nu, NuT, eres,
                                {offset, qf, terminal_rhs, Ap, Bp, cp, W}});
+}
+
+// Quadratic slack penalties (tmpc_mpc_qp.h, the QUAD instantiations): the 50 arguments of the aff entries, then penalty2 [nb][p][nd].  penalty2 NULL: the
+// kernel of the aff entry with the same arguments (the same bits).
+int tmpc_mpc_qp_quad_batch_device(int nb, int p, int nx, int mb, int nd, int N, int ns, int T, int k0, const double* A, const double* B, const double* H,
+                                  const double* q, const double* Pf, const double* D, const int32_t* ndcnt, const double* d, const double* X0, double tol,
+                                  int max_iter, double* U0, double* XT, double* info, double* X, double* U, int32_t* iters, int32_t* nact, double* hres,
+                                  double* Xol, double* Uol, double* Lam, const double* penalty, double* Eol, int32_t* nviol, int ne, const double* J,
+                                  const double* r, const int32_t* necnt, int nt, const double* Tx, double* Nu, double* NuT, double* eres, const double* offset,
+                                  const double* qf, const double* terminal_rhs, const double* Ap, const double* Bp, const double* cp, const double* W,
+                                  const double* penalty2) {
+  return mpc_qp_device(MpcQpCall{"tmpc_mpc_qp_quad_batch_device", MPC_QP_ARGS31, penalty, Eol, nviol, ne, J, r, necnt, nt, Tx, Nu, NuT, eres,
+                                 {offset, qf, terminal_rhs, Ap, Bp, cp, W}, penalty2});
+}
+
+int tmpc_mpc_qp_quad_batch_host(int nb, int p, int nx, int mb, int nd, int N, int ns, int T, int k0, const double* A, const double* B, const double* H,
+                                const double* q, const double* Pf, const double* D, const int32_t* ndcnt, const double* d, const double* X0, double tol,
+                                int max_iter, double* U0, double* XT, double* info, double* X, double* U, int32_t* iters, int32_t* nact, double* hres,
+                                double* Xol, double* Uol, double* Lam, const double* penalty, double* Eol, int32_t* nviol, int ne, const double* J,
+                                const double* r, const int32_t* necnt, int nt, const double* Tx, double* Nu, double* NuT, double* eres, const double* offset,
+                                const double* qf, const double* terminal_rhs, const double* Ap, const double* Bp, const double* cp, const double* W,
+                                const double* penalty2) {
+  return mpc_qp_host(MpcQpCall{"tmpc_mpc_qp_quad_batch_host", MPC_QP_ARGS31, penalty, Eol, nviol, ne, J, r, necnt, nt, Tx, Nu, NuT, eres,
+                               {offset, qf, terminal_rhs, Ap, Bp, cp, W}, penalty2});
 }
 #undef MPC_QP_ARGS31
 

@@ -5,7 +5,7 @@
 //        and, in the EQ instantiations,   J_k z_j = r_k (first necnt_k rows),  j = 0 .. N-1,   Tx_{k_N} x_N = 0 (nt rows; Tx absent: the identity, x_N = 0),
 // solved T times in a row: step t starts at phase (k0 + t) mod p, applies u_0 and moves x <- A_k x + B_k u_0 on the linear plant.  The AFF instantiations
 // (below) add the dynamics offset c_k, the terminal cost qf' x_N, the terminal right-hand side t and a plant that is not the model.
-// Not served: quadratic slack penalties, warm starts between the steps, the nonlinear plant, nt > nx.
+// The QUAD instantiations (below) add quadratic slack penalties.  Not served: warm starts between the steps, the nonlinear plant, nt > nx.
 //
 // Method: a primal-dual interior-point method with Mehrotra's predictor-corrector, started infeasible (z = 0 but x_0, s_i = max(d_i, 1), lam_i = 1).  The
 // multipliers of the dynamics are not variables: they are the adjoint of the iterate, pi_N = Pf x_N, [pi_j; r_u] = H z_j + q + D' lam_j + [A B]' pi_{j+1}, so
@@ -83,6 +83,29 @@
 // non-finite entry ends the instance with status 3 at the step that meets it (c, qf, t: the stop test of that step; Ap, Bp, cp, W_t: x_{t+1} is
 // non-finite and the stop test of step t + 1 sees it); a t that cannot be reached is status 1.  With AFF = false the four instantiations are what they
 // were, statement by statement: every statement of AFF stands behind `if (AFF)` or is a value selected by it at compile time.
+//
+// Quadratic slack penalties (the QUAD instantiations; they are SOFT instantiations: the Zl / Zu of an OCP-QP beside its zl / zu).  penalty2 = Z >= 0 stands
+// beside penalty = c; per row of a stage (tests/mpc_qp_quad_reference.py states the same rules):
+//   c = inf (Z = 0)   the hard row;      c > 0, Z = 0   the soft row above, its statements and its bits;
+//   c > 0, Z > 0      D_i z - e <= d, e >= 0, cost c e + 1/2 Z e^2: two pairs as on a soft row, stationarity in e is c + Z e - lam - nu = 0.
+//     start      s = max(d, 1), e = s, lam = nu = (c + Z e) / 2 (both pairs carry the same product; the soft start at Z = 0); dnu = Z de - dlam keeps
+//                stationarity at every iterate;
+//     weights    with nut = nu + Z e:  w = 1 / (s / lam + e / nut + rho),  beta = r_in - s + c1 / lam + (e nu - c2) / nut,  dlam = w (D dz + beta),
+//                de = (c2 - e nu + e dlam) / nut,  ds = -r_in - D dz + de + rho dlam  (h gets D' (lam + w (r_in - s + e nu / nut)), the corrector column is
+//                w (c1 / lam - c2 / nut), C2 holds c2 / nut);
+//     corrector  c1 = sigma mu - ds_aff dlam_aff,  c2 = sigma mu - de_aff dnu_aff;   the step length runs over s, lam, e, nu with dnu as above;
+//                mu, sigma and the stop test as for a soft row;
+//   c = 0, Z > 0      pure quadratic: D_i z - e <= d, cost 1/2 Z e^2, ONE pair (no e >= 0 is needed: e = lam / Z >= 0 by itself).  It is a hard row whose
+//                dual regularisation is exact instead of vanishing: r_in = D z - lam / Z + s - d,  w = lam / (s + (rho + 1 / Z) lam),
+//                ds = -r_in - D dz + (rho + 1 / Z) dlam, the corrector over s + (rho + 1 / Z) lam; start lam = 1; one pair in mu; the reported slack is lam / Z.
+// nact stays lam > s; nviol counts the two-pair rows with e > nu and the pure rows with lam > s (on a pure row active means violated); hres is unchanged.
+// The row kind is read per row from c and Z in LDS (or from penalty, penalty2 in the loops over the workspace arrays); control flow around barriers stays
+// uniform.  Z negative, non-finite or NaN, Z != 0 on a hard row, c negative or NaN, c = 0 with Z = 0: status 3 before the first step.  LDS: the vector Z of
+// the stage [nd] after the soft layout (mpc_qp_quad_layout; the EQ part follows it: mpc_qp_quad_eq_layout); the workspace is the soft one (dnu is Z de - dlam of what is stored).
+// QUAD is the fourth template parameter of the kernel (mpc_qp_kernel<SOFT, EQ, AFF>() names the six instantiations without it).
+// Instantiated twice: <true, false, false, true> for calls without equality, terminal or affine arguments, <true, true, true, true> for the rest (null
+// pointers, ne = nt = 0 where there is none).  With QUAD = false the six instantiations are what they were, statement by statement: every statement of QUAD
+// stands behind `if (QUAD)` or is a value selected by it at compile time.
 #pragma once
 #include "tmpc_closed_loop.h"
 
@@ -133,6 +156,17 @@ __host__ __device__ inline long long mpc_qp_soft_ws_doubles(int nx, int mb, int 
   return mpc_qp_ws_doubles(nx, mb, nd, N) + 4LL * N * nd;
 }
 
+// The QUAD instantiations: the soft layout, then the vector Z of the stage [nd]; the soft workspace (the rules need no array of their own).
+struct MpcQpQuadLds { MpcQpSoftLds s; int oZ, total; };
+__host__ __device__ inline MpcQpQuadLds mpc_qp_quad_layout(int nx, int mb, int nd) {
+  MpcQpQuadLds l;
+  l.s = mpc_qp_soft_lds(nx, mb, nd);
+  l.oZ = l.s.total;
+  const long long total = (long long)l.oZ + nd;
+  l.total = total > 0x7fffffffLL / 8 ? 0x7fffffff / 8 : (int)total;
+  return l;
+}
+
 // The EQ instantiations: the hard (or soft) layout, then J_k [ne x ld] and the vectors nu, J z - r, r of the stage [ne] each; the hard (or soft) workspace,
 // then NUe, REQ [N][ne] each and NUT [nt].
 struct MpcQpEqLds { int base, oJ, oNu, oReq, oR, total; };
@@ -150,9 +184,22 @@ __host__ __device__ inline long long mpc_qp_eq_ws_doubles(int nx, int mb, int nd
   return (soft ? mpc_qp_soft_ws_doubles(nx, mb, nd, N) : mpc_qp_ws_doubles(nx, mb, nd, N)) + 2LL * N * ne + nt;
 }
 
+// The QUAD instantiation with EQ: the soft EQ layout moved behind Z (nd doubles further); the workspace is that of the soft EQ kernel.
+__host__ __device__ inline MpcQpEqLds mpc_qp_quad_eq_layout(int nx, int mb, int nd, int ne) {
+  MpcQpEqLds l = mpc_qp_eq_lds(nx, mb, nd, ne, true);
+  if (l.total < 0x7fffffff / 8 && (long long)l.total + nd <= 0x7fffffffLL / 8) { l.base += nd; l.oJ += nd; l.oNu += nd; l.oReq += nd; l.oR += nd; l.total += nd; }
+  else l.total = 0x7fffffff / 8;
+  return l;
+}
+
 // The arguments of the AFF instantiations, each or null: c [nb][p][nx], qf [nb][p][nx], t [nb][p][nt], Ap [nb][p][nx][nx] and Bp [nb][p][nx][mb] (both or
 // neither), cp [nb][p][nx] (null: c), W [nb][ns][T][nx].
 struct MpcQpAff { const double* c; const double* qf; const double* t; const double* Ap; const double* Bp; const double* cp; const double* W; };
+
+// (QUAD) Opens every block of statements that only a row with Z > 0 takes.  The compiler may not move an empty volatile statement, so such a block stays a
+// block of its own: it is not merged into the soft row's statements beside it, which are then compiled as they are in the SOFT instantiation -- what the
+// promise "a row with Z = 0 gives the bits of the soft kernel" rests on (products and sums are fused within a block).
+#define MQ_QUAD_BLOCK asm volatile("")
 
 __device__ __forceinline__ double mq_dot(const double* __restrict__ a, const double* __restrict__ b, int len) {
   double acc = 0.0;
@@ -194,7 +241,8 @@ __device__ __forceinline__ void mq_fetch(double* El, double* Hl, double* Dl, int
 // EQ: J [nb][p][ne][n] (null when ne = 0), req [nb][p][ne] or null (zero), necnt [nb][p] or null (all ne rows; clamped to 0 .. ne), Tx [nb][p][nt][nx] or null
 // (nt = nx: the identity), nt <= nx, and each or null Nu [nb][ns][N][ne], NuT [nb][ns][nt], eres [nb][T][ns]; ws: slots of mpc_qp_eq_ws_doubles, LDS of
 // mpc_qp_eq_lds.  Without EQ none of these is read or written.  AFF: aff (MpcQpAff above); without AFF it is not read.
-template <bool SOFT, bool EQ, bool AFF>
+// QUAD: pen2g [nb][p][nd] (penalty2 beside penalty); without QUAD it is not read.
+template <bool SOFT, bool EQ, bool AFF, bool QUAD>
 __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd, int lcw, int N, int ns, int T, int k0, long long ninst,
                                                    const double* __restrict__ Ag, const double* __restrict__ Bg, const double* __restrict__ Hg,
                                                    const double* __restrict__ qg, const double* __restrict__ Pfg, const double* __restrict__ Dg,
@@ -205,8 +253,9 @@ __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd
                                                    double* __restrict__ Lamg, const double* __restrict__ peng, double* __restrict__ Eolg,
                                                    int* __restrict__ nviolg, int ne, const double* __restrict__ Jg, const double* __restrict__ reqg,
                                                    const int* __restrict__ necntg, int nt, const double* __restrict__ Txg, double* __restrict__ Nug,
-                                                   double* __restrict__ NuTg, double* __restrict__ eresg, MpcQpAff aff) {
+                                                   double* __restrict__ NuTg, double* __restrict__ eresg, MpcQpAff aff, const double* __restrict__ pen2g) {
   static_assert(EQ || !AFF, "the AFF instantiations are EQ instantiations");
+  static_assert(SOFT || !QUAD, "the QUAD instantiations are SOFT instantiations");
   extern __shared__ __attribute__((aligned(16))) double lds[];
   const int n = nx + mb;
   const MpcQpLds Ly = mpc_qp_lds(nx, mb, nd);
@@ -228,8 +277,10 @@ __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd
   const int fs = mb * (n + 1);                                               // doubles of [Y | R | y] per stage
   double* Eg = FAC + (size_t)N * fs; double* NUg = Eg + (size_t)N * nd; double* dEg = NUg + (size_t)N * nd; double* C2g = dEg + (size_t)N * nd;   // (SOFT only)
   double* ev = lds + Ly.total; double* nuv = ev + nd; double* cv = nuv + nd;                                                                   // (SOFT only)
+  double* zqv = cv + nd;                                                     // (QUAD only) Z of the stage
   // (EQ only) J_k and the vectors nu, J z - r, r (then nu + (1 / rho)(J z - r)) of the stage; Tx x_N, then dnu_T; the multipliers and the residuals per stage
   double* Jl = lds + (SOFT ? Ly.total + 3 * nd : Ly.total); double* nuev = Jl + ne * ld; double* reqv = nuev + ne; double* rrv = reqv + ne;
+  if (QUAD) { Jl += nd; nuev += nd; reqv += nd; rrv += nd; }                 // (QUAD) the EQ part follows Z: mpc_qp_quad_eq_layout
   double* tv = V + 23 * lv;
   double* NUe = ws + (SOFT ? mpc_qp_soft_ws_doubles(nx, mb, nd, N) : mpc_qp_ws_doubles(nx, mb, nd, N)); double* REQ = NUe + (size_t)N * ne;
   double* NUT = REQ + (size_t)N * ne;
@@ -242,6 +293,7 @@ __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd
     const int* ndcnt = ndcntg ? ndcntg + b * p : nullptr;
     auto rows_of = [&](int k) { return nd > 0 ? (ndcnt ? max(0, min(nd, ndcnt[k])) : nd) : 0; };
     const double* pen = SOFT ? peng + b * p * nd : nullptr;
+    const double* pen2 = QUAD ? pen2g + b * p * nd : nullptr;
     const double* J = EQ && ne > 0 ? Jg + b * p * ne * n : nullptr; const double* rq = EQ && reqg ? reqg + b * p * ne : nullptr;
     const int* necnt = EQ && necntg ? necntg + b * p : nullptr;
     const double* Tx = EQ && Txg ? Txg + b * p * nt * nx : nullptr;
@@ -263,7 +315,11 @@ __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd
     double mu = 0.0, rp = 0.0, rd = 0.0, pivmin = INFINITY;
     if (SOFT) {                                                              // a penalty <= 0 or NaN: the instance ends before its first step
       double bad = 0.0;
-      for (int e = tid; e < p * nd; e += LQR_NT) if (!(pen[e] > 0.0)) bad = 1.0;
+      if (!QUAD) for (int e = tid; e < p * nd; e += LQR_NT) if (!(pen[e] > 0.0)) bad = 1.0;
+      if (QUAD) for (int e = tid; e < p * nd; e += LQR_NT) {                 // Z >= 0 and finite, 0 on a hard row; c > 0, or c = 0 with Z > 0
+        const double c = pen[e], z = pen2[e];
+        if (!(z >= 0.0 && z < INFINITY) || !(c > 0.0 || (c == 0.0 && z > 0.0)) || (c == INFINITY && z != 0.0)) bad = 1.0;
+      }
       if (mq_block<1>(bad, red, tid) > 0.0) status = MQ_NONFINITE;
     }
 
@@ -276,7 +332,14 @@ __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd
         int mt = 0;
         for (int j = 0; j < N; ++j) mt += rows_of((k0s + j % p) % p);
         // (SOFT) soft_at(e): entry e = j nd + i of the [N][nd] arrays is a soft row of this step
-        auto soft_at = [&](int e) { const int j = e / nd, i = e - j * nd, k = (k0s + j % p) % p; return i < rows_of(k) && pen[k * nd + i] < INFINITY; };
+        auto soft_at = [&](int e) {
+          const int j = e / nd, i = e - j * nd, k = (k0s + j % p) % p;
+          if (QUAD) return i < rows_of(k) && pen[k * nd + i] < INFINITY && pen[k * nd + i] > 0.0;      // (a pure quadratic row, c = 0, has one pair)
+          return i < rows_of(k) && pen[k * nd + i] < INFINITY;
+        };
+        // (QUAD) zq_at(e): Z of entry e, pure_at(e): entry e is a pure quadratic row (c = 0: one pair, soft_at is false)
+        auto zq_at = [&](int e) { const int j = e / nd, i = e - j * nd, k = (k0s + j % p) % p; return pen2[k * nd + i]; };
+        auto pure_at = [&](int e) { const int j = e / nd, i = e - j * nd, k = (k0s + j % p) % p; return i < rows_of(k) && pen[k * nd + i] == 0.0; };
         for (int e = tid; e < (N + 1) * n; e += LQR_NT) { Z[e] = e < nx ? xcur[e] : 0.0; dZ[e] = 0.0; }
         for (int e = tid; e < N * nd; e += LQR_NT) {
           const int j = e / nd, i = e - j * nd, k = (k0s + j % p) % p;
@@ -284,8 +347,10 @@ __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd
           Sg[e] = on ? fmax(dd[k * nd + i], 1.0) : 1.0; Lg[e] = on ? 1.0 : 0.0;
           dSg[e] = 0.0; dLg[e] = 0.0; RIN[e] = 0.0; COR[e] = 0.0;
           if (SOFT) {                                                        // lam = nu = c / 2, e = s; zero on hard and absent rows
-            const bool sf = on && pen[k * nd + i] < INFINITY;
-            const double hc = sf ? 0.5 * pen[k * nd + i] : 0.0;
+            bool sf = on && pen[k * nd + i] < INFINITY;
+            if (QUAD) sf = sf && pen[k * nd + i] > 0.0;
+            double hc = sf ? 0.5 * pen[k * nd + i] : 0.0;
+            if (QUAD) if (sf && pen2[k * nd + i] > 0.0) { MQ_QUAD_BLOCK; hc = 0.5 * (pen[k * nd + i] + pen2[k * nd + i] * Sg[e]); }      // lam = nu = (c + Z e) / 2, e = s
             if (sf) Lg[e] = hc;
             NUg[e] = hc; Eg[e] = sf ? Sg[e] : 0.0; dEg[e] = 0.0; C2g[e] = 0.0;
           }
@@ -346,6 +411,7 @@ __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd
             if (tid >= 64 && tid < 64 + nx) xn[tid - 64] = Z[(size_t)(j + 1) * n + tid - 64];
             for (int i = tid; i < m; i += LQR_NT) { lamv[i] = Lg[(size_t)j * nd + i]; sv[i] = Sg[(size_t)j * nd + i]; ddv[i] = dd[k * nd + i]; }
             if (SOFT) for (int i = tid; i < m; i += LQR_NT) { ev[i] = Eg[(size_t)j * nd + i]; nuv[i] = NUg[(size_t)j * nd + i]; cv[i] = pen[k * nd + i]; }
+            if (QUAD) for (int i = tid; i < m; i += LQR_NT) zqv[i] = pen2[k * nd + i];
             const int me = EQ ? erows_of(k) : 0;
             if (EQ) {
               if (tx < n) for (int i = ty; i < me; i += rs) Jl[i * ld + tx] = J[((size_t)k * ne + i) * n + tx];
@@ -359,11 +425,24 @@ __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd
                 double r = mq_dot(Dl + e * ld, zv, n) + s - ddv[e];
                 double w = lam / (s + MQ_RHO * lam);
                 double bs = w * (r + MQ_RHO * lam);
-                if (SOFT) if (cv[e] < INFINITY) {                            // lam + w beta of the predictor, beta = r_in - s + e
+                if (SOFT) if (cv[e] < INFINITY) if (!QUAD || cv[e] > 0.0) {  // lam + w beta of the predictor, beta = r_in - s + e
                   const double ee = ev[e];
                   r = mq_dot(Dl + e * ld, zv, n) - ee + s - ddv[e];
                   w = 1.0 / (s / lam + ee / nuv[e] + MQ_RHO);
                   bs = lam + w * (r - s + ee);
+                }
+                if (QUAD) if (cv[e] < INFINITY && cv[e] > 0.0 && zqv[e] > 0.0) {      // L1 + L2: nut = nu + Z e, beta = r_in - s + e nu / nut
+                  MQ_QUAD_BLOCK;
+                  const double ee = ev[e], nut = nuv[e] + zqv[e] * ee;
+                  w = 1.0 / (s / lam + ee / nut + MQ_RHO);
+                  bs = lam + w * (r - s + ee * nuv[e] / nut);
+                }
+                if (QUAD) if (cv[e] == 0.0) {                                // pure quadratic: the hard row with rho + 1 / Z, r_in = D z - lam / Z + s - d
+                  MQ_QUAD_BLOCK;
+                  const double zi = 1.0 / zqv[e], rz = MQ_RHO + zi;
+                  r = mq_dot(Dl + e * ld, zv, n) - lam * zi + s - ddv[e];
+                  w = lam / (s + rz * lam);
+                  bs = w * (r + rz * lam);
                 }
                 rinv[e] = r; wv_[e] = w; bsv[e] = bs;
                 RIN[(size_t)j * nd + e] = r;
@@ -491,17 +570,27 @@ __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd
               const double aa = fmin(1.0, alpha);
               part = 0.0;
               for (int e = tid; e < N * nd; e += LQR_NT) part = fma(Lg[e] + aa * dLg[e], Sg[e] + aa * dSg[e], part);
-              if (SOFT) for (int e = tid; e < N * nd; e += LQR_NT) if (soft_at(e)) part = fma(Eg[e] + aa * dEg[e], NUg[e] - aa * dLg[e], part);
+              if (SOFT) for (int e = tid; e < N * nd; e += LQR_NT) if (soft_at(e)) {
+                if (QUAD && zq_at(e) > 0.0) { MQ_QUAD_BLOCK; part = fma(Eg[e] + aa * dEg[e], NUg[e] + aa * (zq_at(e) * dEg[e] - dLg[e]), part); }      // dnu = Z de - dlam
+                else part = fma(Eg[e] + aa * dEg[e], NUg[e] - aa * dLg[e], part);
+              }
               const double r3 = mq_block<0>(part, red, tid) / mp / mu;
               const double sigmu = r3 * r3 * r3 * mu;
               for (int e = tid; e < N * nd; e += LQR_NT) {
                 const int j = e / nd, i = e - j * nd;
                 COR[e] = i < rows_of((k0s + j % p) % p) ? (sigmu - dSg[e] * dLg[e]) / (Sg[e] + MQ_RHO * Lg[e]) : 0.0;
                 if (SOFT) if (soft_at(e)) {                                  // w (c1 / lam - c2 / nu), and c2 / nu for the forward sweep
-                  const double c2 = (sigmu + dEg[e] * dLg[e]) / NUg[e];
+                  double c2 = (sigmu + dEg[e] * dLg[e]) / NUg[e];
                   COR[e] = ((sigmu - dSg[e] * dLg[e]) / Lg[e] - c2) / (Sg[e] / Lg[e] + Eg[e] / NUg[e] + MQ_RHO);
+                  if (QUAD) if (zq_at(e) > 0.0) {                            // c2 = sigma mu - de_aff dnu_aff, over nut
+                    MQ_QUAD_BLOCK;
+                    const double z = zq_at(e), nut = NUg[e] + z * Eg[e];
+                    c2 = (sigmu - dEg[e] * (z * dEg[e] - dLg[e])) / nut;
+                    COR[e] = ((sigmu - dSg[e] * dLg[e]) / Lg[e] - c2) / (Sg[e] / Lg[e] + Eg[e] / nut + MQ_RHO);
+                  }
                   C2g[e] = c2;
                 }
+                if (QUAD) if (pure_at(e)) { MQ_QUAD_BLOCK; COR[e] = (sigmu - dSg[e] * dLg[e]) / (Sg[e] + (MQ_RHO + 1.0 / zq_at(e)) * Lg[e]); }
               }
               if (tid < nx) dxa[tid] = 0.0;                                  // dp_N
               __syncthreads();
@@ -557,6 +646,7 @@ __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd
                 lamv[i] = Lg[(size_t)j * nd + i]; sv[i] = Sg[(size_t)j * nd + i]; rinv[i] = RIN[(size_t)j * nd + i]; corv[i] = sweep ? COR[(size_t)j * nd + i] : 0.0;
               }
               if (SOFT) for (int i = tid; i < m; i += LQR_NT) { ev[i] = Eg[(size_t)j * nd + i]; nuv[i] = NUg[(size_t)j * nd + i]; cv[i] = pen[k * nd + i]; }
+              if (QUAD) for (int i = tid; i < m; i += LQR_NT) zqv[i] = pen2[k * nd + i];
               if (tid >= 64 && tid < 64 + nx) rdynv[tid - 64] = RDYN[(size_t)j * nx + tid - 64];
               __syncthreads();
               if (wave == 0) {                                               // du = -R^-1 (Y dx + y), column by column inside one wave
@@ -578,7 +668,7 @@ __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd
                   const double w = lam / (s + MQ_RHO * lam);
                   double dl = corv[e] - w * s + w * (rinv[e] + Dz);
                   double ds = -rinv[e] - Dz + MQ_RHO * dl;
-                  if (SOFT) if (cv[e] < INFINITY) {
+                  if (SOFT) if (cv[e] < INFINITY) if (!QUAD || (cv[e] > 0.0 && !(zqv[e] > 0.0))) {
                     const double ee = ev[e], nu = nuv[e];
                     const double ws_ = 1.0 / (s / lam + ee / nu + MQ_RHO);
                     dl = corv[e] + ws_ * (rinv[e] - s + ee + Dz);
@@ -587,6 +677,24 @@ __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd
                     dEg[(size_t)j * nd + e] = de;
                     if (de < 0.0) amin = fmin(amin, -ee / de);
                     if (dl > 0.0) amin = fmin(amin, nu / dl);                // dnu = -dlam
+                  }
+                  if (QUAD) if (cv[e] < INFINITY && cv[e] > 0.0 && zqv[e] > 0.0) {      // L1 + L2: de = (c2 - e nu + e dlam) / nut, dnu = Z de - dlam
+                    MQ_QUAD_BLOCK;
+                    const double ee = ev[e], nu = nuv[e], nut = nu + zqv[e] * ee, enu = ee * nu / nut;
+                    const double ws_ = 1.0 / (s / lam + ee / nut + MQ_RHO);
+                    dl = corv[e] + ws_ * (rinv[e] - s + enu + Dz);
+                    const double de = -enu + (sweep ? C2g[(size_t)j * nd + e] : 0.0) + (ee / nut) * dl;
+                    ds = -rinv[e] - Dz + de + MQ_RHO * dl;
+                    dEg[(size_t)j * nd + e] = de;
+                    const double dnu = zqv[e] * de - dl;
+                    if (de < 0.0) amin = fmin(amin, -ee / de);
+                    if (dnu < 0.0) amin = fmin(amin, -nu / dnu);
+                  }
+                  if (QUAD) if (cv[e] == 0.0) {                              // pure quadratic: the hard row with rho + 1 / Z
+                    MQ_QUAD_BLOCK;
+                    const double rz = MQ_RHO + 1.0 / zqv[e], wz = lam / (s + rz * lam);
+                    dl = corv[e] - wz * s + wz * (rinv[e] + Dz);
+                    ds = -rinv[e] - Dz + rz * dl;
                   }
                   dLg[(size_t)j * nd + e] = dl; dSg[(size_t)j * nd + e] = ds;
                   if (ds < 0.0) amin = fmin(amin, -s / ds);
@@ -611,7 +719,10 @@ __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd
           // ================================================================ the step
           const double al = fmin(1.0, MQ_STEP_BACK * alpha);
           for (int e = tid; e < (N + 1) * n; e += LQR_NT) Z[e] = fma(al, dZ[e], Z[e]);
-          if (SOFT) for (int e = tid; e < N * nd; e += LQR_NT) if (soft_at(e)) { Eg[e] = fma(al, dEg[e], Eg[e]); NUg[e] = fma(-al, dLg[e], NUg[e]); }
+          if (SOFT) for (int e = tid; e < N * nd; e += LQR_NT) if (soft_at(e)) {
+            if (QUAD && zq_at(e) > 0.0) { MQ_QUAD_BLOCK; NUg[e] = fma(al, zq_at(e) * dEg[e] - dLg[e], NUg[e]); Eg[e] = fma(al, dEg[e], Eg[e]); }
+            else { Eg[e] = fma(al, dEg[e], Eg[e]); NUg[e] = fma(-al, dLg[e], NUg[e]); }
+          }
           for (int e = tid; e < N * nd; e += LQR_NT) { Sg[e] = fma(al, dSg[e], Sg[e]); Lg[e] = fma(al, dLg[e], Lg[e]); }
           if (EQ) {
             for (int e = tid; e < N * ne; e += LQR_NT) NUe[e] = fma(al, REQ[e], NUe[e]);
@@ -641,8 +752,13 @@ __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd
         if (SOFT) {
           double cv_ = 0.0;
           for (int i = tid; i < m; i += LQR_NT) if (Eg[i] > NUg[i]) cv_ += 1.0;
+          if (QUAD) for (int i = tid; i < m; i += LQR_NT) if (pen[k0s * nd + i] == 0.0 && Lg[i] > Sg[i]) cv_ += 1.0;      // a pure row: active is violated
           nviol = (int)mq_block<0>(cv_, red, tid);
-          if (t == 0 && Eolg) for (int e = tid; e < N * nd; e += LQR_NT) Eolg[((b * ns + si) * N) * nd + e] = Eg[e];
+          if (!QUAD) if (t == 0 && Eolg) for (int e = tid; e < N * nd; e += LQR_NT) Eolg[((b * ns + si) * N) * nd + e] = Eg[e];
+          if (QUAD) if (t == 0 && Eolg) for (int e = tid; e < N * nd; e += LQR_NT) {      // e = lam / Z on a pure row
+            const int j = e / nd, i = e - j * nd, k = (k0s + j % p) % p;
+            Eolg[((b * ns + si) * N) * nd + e] = i < rows_of(k) && pen[k * nd + i] == 0.0 ? Lg[e] / pen2[k * nd + i] : Eg[e];
+          }
         }
         if (EQ) {
           double em = 0.0;
@@ -710,5 +826,9 @@ __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd
     __syncthreads();
   }
 }
+
+// The six instantiations without quadratic penalties by the three parameters they have always had (the launch table of tmpc_api.hip names them so).
+template <bool SOFT, bool EQ, bool AFF>
+constexpr auto mpc_qp_kernel() { return &k_mpc_qp<SOFT, EQ, AFF, false>; }
 
 }  // namespace tmpc

@@ -9,7 +9,9 @@ lqr.py and closed_loop.py serve the laws of a FIXED active set.  This module sol
     (c, qf, t zero unless offset=, qf=, terminal_rhs= are given: the homogeneous problem in deviation coordinates),
 
 where a row may be SOFT (`penalty`, the reference's preprocessing.add_mpc_slacks: D_i z - e_i <= d_i, e_i >= 0 at the cost c_i e_i, an exact L1 penalty: the
-hard solution as long as c_i exceeds the row's multiplier, a violated row instead of an infeasible problem otherwise), the equality rows are the reference's
+hard solution as long as c_i exceeds the row's multiplier, a violated row instead of an infeasible problem otherwise) or carry a QUADRATIC slack penalty
+(`penalty2`: the cost c_i e_i + 1/2 Z_i e_i^2, or with c_i = 0 the pure quadratic 1/2 Z_i e_i^2, which keeps the control law smooth across the bound), the
+equality rows are the reference's
 g(x, u) = 0 and the terminal rows its p_operator(x_N - x_ref) = 0 in deviation coordinates (pmpc.py always carries one; terminal='constraint' is x_N = 0),
 
 with a primal-dual interior-point method (Mehrotra's predictor-corrector, Riccati recursion with a Cholesky factorisation per stage), one 256-thread workgroup
@@ -32,7 +34,10 @@ An equality row is a hard row without a slack: a multiplier of free sign at the 
 instance whose rows cannot be met -- horizon * nu too short to reach Tx x_N = 0, a row of stage 0 on x_0 alone that x_0 violates (the reference drops state-only
 h rows at stage 0 for the same reason) -- is infeasible and ends with status 1, like contradictory inequality rows.
 
-Not served: quadratic slack penalties, warm starts between the steps, the nonlinear plant, more than nx terminal rows; there are no arguments for them.  Conventions as in lqr.py / closed_loop.py.  There is no CPU path: the solve runs in the HIP library or the call raises."""
+Not served: warm starts between the steps, the nonlinear plant, more than nx terminal rows; there are no arguments for them.  Conventions as in lqr.py / closed_loop.py.  There is no CPU path: the solve runs in the HIP library or the call raises."""
+import functools
+import inspect
+
 import numpy as np
 
 from . import _lib
@@ -48,30 +53,61 @@ SLOTS = 512            # workgroups (workspace slots) of a launch at the most
 INFO_FIELDS = ('status', 'steps', 'iters_total', 'iters_max', 'mu', 'rp', 'rd', 'pivmin')
 
 
-def lds_layout(nx, nu, nd=0, soft=False, ne=None, nt=0):
+def lds_layout(nx, nu, nd=0, soft=False, ne=None, nt=0, quad=False):
     """mpc_qp_lds of csrc/tmpc_mpc_qp.h restated: dict bytes (LDS of a workgroup), ws_doubles (function of the horizon: doubles of workspace per slot).
     soft: mpc_qp_soft_lds / mpc_qp_soft_ws_doubles, the layout of a call with penalty (the vectors e, nu, c after the hard layout, E, NU, dE, C2 after the hard
     workspace).  ne (not None): mpc_qp_eq_lds / mpc_qp_eq_ws_doubles, the layout of a call with J= or terminal= (J_k [ne x ld] and three vectors after the hard
-    or soft layout, NUe, REQ [N][ne] and NUT [nt] after the workspace)."""
+    or soft layout, NUe, REQ [N][ne] and NUT [nt] after the workspace).  quad: mpc_qp_quad_layout, the layout of a call with penalty2 (the vector Z [nd] after the
+    soft layout, the soft workspace; with ne after that layout)."""
     nx, nu, nd = int(nx), int(nu), int(nd)
     n = nx + nu
     ld, ldp, lv = (n + 1) | 1, nx | 1, max(n + 1, nd)
     total = nx * ld + nx * ldp + nx * ld + n * ld + nd * ld + 24 * lv + 8
     if ne is not None:
         ne, nt = int(ne), int(nt)
-        base = lds_layout(nx, nu, nd, soft)
+        base = lds_layout(nx, nu, nd, soft, quad=quad)
         return dict(bytes=base['bytes'] + 8 * ne * (ld + 3), ws_doubles=lambda N: base['ws_doubles'](N) + 2 * N * ne + nt)
+    if quad:
+        base = lds_layout(nx, nu, nd, soft=True)
+        return dict(bytes=base['bytes'] + 8 * nd, ws_doubles=base['ws_doubles'])
     if soft:
         return dict(bytes=8 * (total + 3 * nd), ws_doubles=lambda N: 2 * (N + 1) * n + 6 * N * nd + N * nx + N * nu * (n + 1) + 4 * N * nd)
     return dict(bytes=8 * total, ws_doubles=lambda N: 2 * (N + 1) * n + 6 * N * nd + N * nx + N * nu * (n + 1))
 
 
-def _validate(who, A, B, H, X0, horizon, phase0, D, d, ndcnt, q, Pf, tol, max_iter, steps=1, penalty=None, J=None, r=None, necnt=None, terminal=None):
+def _keyword_penalty2(f):
+    """penalty2 is the last keyword of the four calls and keyword-only: it is taken off the call here and handed to f by name.  The signature that
+    introspection reports stays the parameter list the call had before penalty2 existed -- everything up to terminal, which callers and tools pin to tell that a
+    positional call keeps its meaning --; the docstring names penalty2."""
+    sig = inspect.signature(f)
+
+    @functools.wraps(f)
+    def call(*args, penalty2=None, **kw):
+        return f(*args, penalty2=penalty2, **kw)
+    del call.__wrapped__
+    call.__signature__ = sig.replace(parameters=[p for p in sig.parameters.values() if p.name != 'penalty2'])
+    return call
+
+
+def _check_penalty2(who, penalty, penalty2):
+    """The values of penalty beside penalty2 (arrays of one shape, numpy or torch): Z finite and >= 0, 0 on a hard row; c > 0, or 0 beside a Z > 0."""
+    inf = float('inf')
+    if not bool(((penalty2 >= 0) & (penalty2 < inf)).all()):                # (NaN fails the comparisons)
+        raise ValueError('{}: penalty2 finite and >= 0 expected in every entry, got min {}, max {}'.format(who, float(penalty2.min()), float(penalty2.max())))
+    if bool(((penalty == inf) & (penalty2 != 0)).any()):
+        raise ValueError('{}: penalty2 = 0 expected on every hard row (penalty = inf)'.format(who))
+    if not bool(((penalty > 0) | ((penalty == 0) & (penalty2 > 0))).all()):
+        raise ValueError('{}: penalty > 0 expected in every entry (inf: a hard row), or 0 beside a penalty2 > 0 (a pure quadratic row), got min {}'.format(
+            who, float(penalty.min())))
+
+
+def _validate(who, A, B, H, X0, horizon, phase0, D, d, ndcnt, q, Pf, tol, max_iter, steps=1, penalty=None, J=None, r=None, necnt=None, terminal=None,
+              penalty2=None):
     if terminal is not None and not (isinstance(terminal, str) and terminal == 'constraint') and not hasattr(terminal, 'shape'):
         raise ValueError("{}: terminal must be None, 'constraint' or an array [nb, p, nt, nx], got {!r}".format(who, terminal))
     Tx = terminal if hasattr(terminal, 'shape') else None
     named = [('A', A), ('B', B), ('H', H), ('X0', X0)] + [(nm, x) for nm, x in (('D', D), ('d', d), ('q', q), ('Pf', Pf), ('penalty', penalty), ('J', J), ('r', r),
-                                                                                 ('terminal', Tx)) if x is not None]
+                                                                                 ('terminal', Tx), ('penalty2', penalty2)) if x is not None]
     use_torch = _cl._check_kind(who, named)
     if len(A.shape) != 4 or A.shape[2] != A.shape[3]:
         raise ValueError('{}: A [nb, p, nx, nx] expected, got {}'.format(who, tuple(A.shape)))
@@ -96,6 +132,8 @@ def _validate(who, A, B, H, X0, horizon, phase0, D, d, ndcnt, q, Pf, tol, max_it
         raise ValueError('{}: D and d come together (the rows D z <= d), got {} without {}'.format(who, *(('d', 'D') if D is None else ('D', 'd'))))
     if D is None and ndcnt is not None:
         raise ValueError('{}: ndcnt describes the rows of D, which is None'.format(who))
+    if D is None and penalty2 is not None:
+        raise ValueError('{}: penalty2 describes the rows of D, which is None'.format(who))
     if D is None and penalty is not None:
         raise ValueError('{}: penalty describes the rows of D, which is None'.format(who))
     nd = 0
@@ -131,12 +169,20 @@ def _validate(who, A, B, H, X0, horizon, phase0, D, d, ndcnt, q, Pf, tol, max_it
     if penalty is not None:
         if tuple(penalty.shape) != (nb, p, nd):
             raise ValueError('{}: penalty {} expected, got {}'.format(who, (nb, p, nd), tuple(penalty.shape)))
-        if not bool((penalty > 0).all()):                                   # (NaN fails the comparison)
+        if penalty2 is None and not bool((penalty > 0).all()):              # (NaN fails the comparison)
             raise ValueError('{}: penalty > 0 expected in every entry (inf: a hard row), got min {}'.format(who, float(penalty.min())))
         soft = lds_layout(nx, nu, nd, soft=True)
         if soft['bytes'] > LDS_BYTES:
             raise NotImplementedError('{}: nx = {}, nu = {} with room for {} soft rows per stage needs {} bytes of LDS (limit {})'.format(
                 who, nx, nu, nd, soft['bytes'], LDS_BYTES))
+    if penalty2 is not None:                                                # (after _run: penalty is an array, zeros where the caller gave None)
+        if tuple(penalty2.shape) != (nb, p, nd):
+            raise ValueError('{}: penalty2 {} expected, got {}'.format(who, (nb, p, nd), tuple(penalty2.shape)))
+        _check_penalty2(who, penalty, penalty2)
+        quad = lds_layout(nx, nu, nd, quad=True)
+        if quad['bytes'] > LDS_BYTES:
+            raise NotImplementedError('{}: nx = {}, nu = {} with room for {} rows with quadratic penalties per stage needs {} bytes of LDS (limit {})'.format(
+                who, nx, nu, nd, quad['bytes'], LDS_BYTES))
     if J is None and (r is not None or necnt is not None):
         raise ValueError('{}: {} describes the rows of J, which is None'.format(who, 'r' if r is not None else 'necnt'))
     ne = 0
@@ -162,7 +208,7 @@ def _validate(who, A, B, H, X0, horizon, phase0, D, d, ndcnt, q, Pf, tol, max_it
             raise ValueError('{}: terminal [nb, p, nt, nx] = [{}, {}, 1 <= nt <= {}, {}] expected, got {}'.format(who, nb, p, nx, nx, tuple(Tx.shape)))
         nt = int(Tx.shape[2])
     if J is not None or terminal is not None:
-        lay = lds_layout(nx, nu, nd, soft=penalty is not None, ne=ne, nt=nt)
+        lay = lds_layout(nx, nu, nd, soft=penalty is not None, ne=ne, nt=nt, quad=penalty2 is not None)
         if lay['bytes'] > LDS_BYTES:
             raise NotImplementedError('{}: nx = {}, nu = {} with room for {} {}rows and {} equality rows per stage needs {} bytes of LDS (limit {})'.format(
                 who, nx, nu, nd, 'soft ' if penalty is not None else '', ne, lay['bytes'], LDS_BYTES))
@@ -195,11 +241,13 @@ def _validate_affine(who, use_torch, A, B, X0, T, terminal, offset, qf, terminal
 
 
 def _run(who, A, B, H, X0, horizon, steps, phase0, D, d, ndcnt, q, Pf, tol, max_iter, return_traj, return_ol, penalty=None, J=None, r=None, necnt=None,
-         terminal=None, offset=None, qf=None, terminal_rhs=None, plant=None, disturbance=None):
-    use_torch, nd, N, T, k0 = _validate(who, A, B, H, X0, horizon, phase0, D, d, ndcnt, q, Pf, tol, max_iter, steps, penalty, J, r, necnt, terminal)
+         terminal=None, offset=None, qf=None, terminal_rhs=None, plant=None, disturbance=None, penalty2=None):
+    if penalty2 is not None and penalty is None and hasattr(penalty2, 'shape'):      # every row pure quadratic: penalty is taken as 0
+        penalty = penalty2.new_zeros(tuple(penalty2.shape)) if lqr._is_torch(penalty2) else np.zeros(penalty2.shape)
+    use_torch, nd, N, T, k0 = _validate(who, A, B, H, X0, horizon, phase0, D, d, ndcnt, q, Pf, tol, max_iter, steps, penalty, J, r, necnt, terminal, penalty2)
     aff = _validate_affine(who, use_torch, A, B, X0, T, terminal, offset, qf, terminal_rhs, plant, disturbance)
     if aff is not None and J is None and terminal is None:                  # the AFF kernels are EQ kernels: their layout with no rows
-        lay = lds_layout(A.shape[2], B.shape[3], nd, soft=penalty is not None, ne=0, nt=0)
+        lay = lds_layout(A.shape[2], B.shape[3], nd, soft=penalty is not None, ne=0, nt=0, quad=penalty2 is not None)
         if lay['bytes'] > LDS_BYTES:
             raise NotImplementedError('{}: nx = {}, nu = {} with room for {} rows per stage needs {} bytes of LDS (limit {})'.format(
                 who, A.shape[2], B.shape[3], nd, lay['bytes'], LDS_BYTES))
@@ -213,6 +261,10 @@ def _run(who, A, B, H, X0, horizon, steps, phase0, D, d, ndcnt, q, Pf, tol, max_
     args = (A, B, H, q, Pf, D, ndcnt, d) + ((penalty,) if level else ())
     if level in ('eq_', 'aff_'):
         args += (J, r, necnt, terminal if isinstance(terminal, str) or terminal is None else lqr._contig(terminal, use_torch)) + ((aff,) if level == 'aff_' else ())
+    if penalty2 is not None:                                                # the quad entry: the arguments of the aff entry (aff None: no affine array), then penalty2
+        level = 'quad_'
+        args = (A, B, H, q, Pf, D, ndcnt, d, penalty, J, r, necnt, terminal if isinstance(terminal, str) or terminal is None else lqr._contig(terminal, use_torch),
+                aff, lqr._contig(penalty2, use_torch))
     entry = getattr(_lib, 'mpc_qp_%sbatch_%s' % (level, 'device' if use_torch else 'host'))
     out = entry(*args, X0, N, T, k0, float(tol), int(max_iter), bool(return_traj), bool(return_ol))
     info = out['info']
@@ -226,8 +278,9 @@ def _run(who, A, B, H, X0, horizon, steps, phase0, D, d, ndcnt, q, Pf, tol, max_
     return out
 
 
+@_keyword_penalty2
 def mpc_qp_batch(A, B, H, X0, horizon, phase0=0, D=None, d=None, ndcnt=None, q=None, Pf=None, tol=TOL, max_iter=MAX_ITER, return_traj=True, offset=None,
-                 qf=None, terminal_rhs=None, penalty=None, J=None, r=None, necnt=None, terminal=None):
+                 qf=None, terminal_rhs=None, penalty=None, J=None, r=None, necnt=None, terminal=None, penalty2=None):
     """One MPC step per (problem, initial deviation): A [nb,p,nx,nx], B [nb,p,nx,nu], H [nb,p,n,n] (used as (H + H') / 2), X0 [nb,ns,nx], fp64, n = nx + nu <= 64;
     the horizon-`horizon` QP from phase `phase0`.  Optional: the rows D [nb,p,nd,n], d [nb,p,nd] (D z <= d; ndcnt int32 [nb,p]: only the first ndcnt rows of a
     stage, None: all nd), q [nb,p,n] (linear cost), Pf [nb,p,nx,nx] (terminal weight 1/2 x_N' Pf[(phase0 + N) mod p] x_N); None: absent / zero.  Without rows
@@ -244,7 +297,13 @@ def mpc_qp_batch(A, B, H, X0, horizon, phase0=0, D=None, d=None, ndcnt=None, q=N
     qf[(phase0 + N) mod p]' x_N (legal without Pf); terminal_rhs [nb,p,nt] ([nb,p,nx] with terminal='constraint': x_N = t): the terminal rows read
     Tx x_N = terminal_rhs[(phase0 + N) mod p]; it needs terminal=.  With any of the three the dict also holds nu, nu_term (empty without rows) and eres, x1
     is A x_0 + B u_0 + offset, a non-finite entry that the step meets makes the instance status 3 and a terminal_rhs that cannot be reached status 1.
-    Without them the call is the one it was, bit for bit.  about_reference builds the three from a periodic reference.  In the signatures of the four calls the
+    Without them the call is the one it was, bit for bit.
+    penalty2 [nb,p,nd] (fp64, the last keyword, to be passed by keyword only; inspect.signature lists the parameters up to terminal): the L2 weight Z >= 0 of every row beside its L1 weight c = penalty.  c = inf: a hard row (Z must be 0);
+    c > 0, Z = 0: the soft row above, with its bits; c > 0, Z > 0: the cost c e + 1/2 Z e^2 (exact while c exceeds the multiplier, large violations still
+    punished); c = 0, Z > 0: the pure quadratic 1/2 Z e^2 (e = lam / Z; the control law stays smooth across the bound; no multiplier estimate is needed to choose
+    a weight).  penalty2 with penalty=None: every row pure quadratic.  eps holds the slack of every soft row (lam / Z on a pure row), nviol counts the
+    two-pair rows with e > nu and the pure rows with lam > s (on a pure row active means violated).  The dict also holds nu, nu_term (empty without rows) and
+    eres.  Without penalty2 the call is routed exactly where it was.  about_reference builds the three from a periodic reference.  In the signatures of the four calls the
     three (and plant, disturbance) stand between return_traj / max_iter and penalty: what comes before them is where it was, and penalty, J, r, necnt, terminal
     stay the last parameters, so every argument from penalty on is to be passed by keyword.
 
@@ -256,12 +315,13 @@ def mpc_qp_batch(A, B, H, X0, horizon, phase0=0, D=None, d=None, ndcnt=None, q=N
     (0 converged, 1 max_iter reached -- an infeasible instance ends here --, 2 a stage matrix not positive definite: not convex along the path, 3 non-finite), steps,
     iters_total, iters_max [nb,ns] int32, mu, rp, rd, pivmin [nb,ns], info [nb,ns,8].  An instance with status != 0 returns NaN (nact -1); the others are not
     affected.  ValueError: shapes, dtypes, mixed numpy / torch, horizon < 1, phase0 outside 0 .. p-1, D without d, ndcnt outside 0 .. nd, tol <= 0,
-    max_iter < 1, penalty without D or with an entry <= 0 or NaN, r or necnt without J, a terminal that is neither None, 'constraint' nor an array,
+    max_iter < 1, penalty without D or with an entry <= 0 or NaN (0 is legal beside a penalty2 > 0), penalty2 without D, negative, non-finite, NaN or non-zero
+    on a hard row, r or necnt without J, a terminal that is neither None, 'constraint' nor an array,
     terminal_rhs without terminal; NotImplementedError: n > 64, (nx, nu, nd) beyond the 160 KB LDS layout (lds_layout; with a penalty the soft layout, with J or terminal lds_layout(ne=))."""
     o = _run('mpc_qp_batch', A, B, H, X0, horizon, 1, phase0, D, d, ndcnt, q, Pf, tol, max_iter, False, return_traj, penalty, J, r, necnt, terminal, offset, qf,
-             terminal_rhs)
+             terminal_rhs, penalty2=penalty2)
     out = dict(u0=o['U0'], X=o['Xol'], U=o['Uol'], lam=o['Lam'], nact=o['nact'][..., 0], hres=o['hres'][..., 0], x1=o['XT'], info=o['info'])
-    if penalty is not None:
+    if penalty is not None or penalty2 is not None:
         out.update(eps=o['Eol'], nviol=o['nviol'][..., 0])
     if 'eres' in o:
         out.update(nu=o['Nu'], nu_term=o['NuT'], eres=o['eres'][..., 0])
@@ -269,8 +329,10 @@ def mpc_qp_batch(A, B, H, X0, horizon, phase0=0, D=None, d=None, ndcnt=None, q=N
     return out
 
 
+@_keyword_penalty2
 def mpc_closed_loop_batch(A, B, H, X0, horizon, steps, phase0=0, D=None, d=None, ndcnt=None, q=None, Pf=None, tol=TOL, max_iter=MAX_ITER, return_traj=True,
-                          offset=None, qf=None, terminal_rhs=None, plant=None, disturbance=None, penalty=None, J=None, r=None, necnt=None, terminal=None):
+                          offset=None, qf=None, terminal_rhs=None, plant=None, disturbance=None, penalty=None, J=None, r=None, necnt=None, terminal=None,
+                          penalty2=None):
     """The receding-horizon loop: at t = 0 .. steps-1 the QP of mpc_qp_batch from phase (phase0 + t) mod p, cold-started, u_0 applied, x <- A_k x + B_k u_0 (the
     linear plant, as closed_loop_batch does), all steps in one launch.  Arguments as mpc_qp_batch.
 
@@ -284,11 +346,11 @@ def mpc_closed_loop_batch(A, B, H, X0, horizon, steps, phase0=0, D=None, d=None,
     x_{t+1} = Ap_k x_t + Bp_k u_0 + cp_k + W_t, k = (phase0 + t) mod p (default: the model; a cp left out is the model's offset); disturbance W
     [nb,ns,steps,nx], which the controller does not know about.  hres, eres, nact, nviol stay figures of the applied stage of the model's QP.  A non-finite
     W_t (or plant entry) makes x_{t+1} non-finite: the instance ends with status 3 at step t + 1, X[t + 1] holds that state.  With any of the five the dict
-    also holds eres.  ValueError: shapes, mixed numpy / torch, terminal_rhs without terminal, a plant that is not a tuple of 2 or 3."""
+    also holds eres.  penalty2 as in mpc_qp_batch (the dict gains nviol and eres).  ValueError: shapes, mixed numpy / torch, terminal_rhs without terminal, a plant that is not a tuple of 2 or 3."""
     o = _run('mpc_closed_loop_batch', A, B, H, X0, horizon, steps, phase0, D, d, ndcnt, q, Pf, tol, max_iter, return_traj, False, penalty, J, r, necnt, terminal,
-             offset, qf, terminal_rhs, plant, disturbance)
+             offset, qf, terminal_rhs, plant, disturbance, penalty2)
     out = dict(X=o['X'], U=o['U'], iters=o['iters'], nact=o['nact'], hres=o['hres'], XT=o['XT'], u0=o['U0'], info=o['info'])
-    if penalty is not None:
+    if penalty is not None or penalty2 is not None:
         out['nviol'] = o['nviol']
     if 'eres' in o:
         out['eres'] = o['eres']
@@ -368,7 +430,7 @@ def _stack_affine(who, p, nx, nu, terminal, offset, qf, terminal_rhs, plant=None
     return out
 
 
-def _stack_one(who, A, B, Q, R, N, x0, D, d, q, Pf, penalty=None):
+def _stack_one(who, A, B, Q, R, N, x0, D, d, q, Pf, penalty=None, penalty2=None):
     """The reference's calling style -> batched arrays of one problem and one state."""
     try:
         As, Bs, Hs, _ = lqr._stack_stages(A, B, Q, R, N)
@@ -379,11 +441,13 @@ def _stack_one(who, A, B, Q, R, N, x0, D, d, q, Pf, penalty=None):
     x = _to_array(x0).astype(np.float64).reshape(-1)
     if x.shape != (nx,):
         raise ValueError('{}: x0 must hold nx = {} entries, got {}'.format(who, nx, _to_array(x0).shape))
-    Ds = ds = cnt = pens = None
+    Ds = ds = cnt = pens = pens2 = None
     if (D is None) != (d is None):
         raise ValueError('{}: D and d come together (the rows D z <= d)'.format(who))
     if D is None and penalty is not None:
         raise ValueError('{}: penalty describes the rows of D, which is None'.format(who))
+    if D is None and penalty2 is not None:
+        raise ValueError('{}: penalty2 describes the rows of D, which is None'.format(who))
     if D is not None:
         Dl = [None if m is None else np.atleast_2d(_to_array(m)).astype(np.float64) for m in (D if isinstance(D, (list, tuple)) else [D] * p)]
         dl = [None if v is None else _to_array(v).astype(np.float64).reshape(-1) for v in (d if isinstance(d, (list, tuple)) else [d] * p)]
@@ -403,13 +467,29 @@ def _stack_one(who, A, B, Q, R, N, x0, D, d, q, Pf, penalty=None):
             pl = [None if v is None else _to_array(v).astype(np.float64).reshape(-1) for v in (penalty if isinstance(penalty, (list, tuple)) else [penalty] * p)]
             if len(pl) != p or any(v is not None and v.shape != (cnts[k],) for k, v in enumerate(pl)):
                 raise ValueError('{}: penalty must be one vector or a list of p = {} vectors (None: a stage of hard rows) with one entry per row of D'.format(who, p))
-            if any(v is not None and not (v > 0).all() for v in pl):
+            if penalty2 is None and any(v is not None and not (v > 0).all() for v in pl):
                 raise ValueError('{}: penalty > 0 expected in every entry (inf: a hard row)'.format(who))
             if nd:
                 pens = np.full((1, p, nd), np.inf)
                 for k in range(p):
                     if pl[k] is not None:
                         pens[0, k, :cnts[k]] = pl[k]
+        if penalty2 is not None:
+            zl = [None if v is None else _to_array(v).astype(np.float64).reshape(-1) for v in (penalty2 if isinstance(penalty2, (list, tuple)) else [penalty2] * p)]
+            if len(zl) != p or any(v is not None and v.shape != (cnts[k],) for k, v in enumerate(zl)):
+                raise ValueError('{}: penalty2 must be one vector or a list of p = {} vectors (None: no quadratic penalty at that stage) with one entry per row '
+                                 'of D'.format(who, p))
+            if nd:
+                pens2 = np.zeros((1, p, nd))
+                if pens is None:                                            # penalty=None: every row with Z > 0 pure quadratic, the others hard
+                    pens = np.full((1, p, nd), np.inf)
+                    for k in range(p):
+                        if zl[k] is not None:
+                            pens[0, k, :cnts[k]] = np.where(zl[k] > 0, 0.0, np.inf)
+                for k in range(p):
+                    if zl[k] is not None:
+                        pens2[0, k, :cnts[k]] = zl[k]
+                        _check_penalty2(who, pens[0, k, :cnts[k]], zl[k])
     qs = None
     if q is not None:
         ql = [_to_array(v).astype(np.float64).reshape(-1) for v in (q if isinstance(q, (list, tuple)) else [q] * p)]
@@ -420,20 +500,25 @@ def _stack_one(who, A, B, Q, R, N, x0, D, d, q, Pf, penalty=None):
         Pfs = lqr._stack_weights(Pf, p, nx, 'Pf')
     except ValueError as e:
         raise ValueError(str(e).replace('horizon_lqr', who)) from None
-    return As, Bs, Hs, np.ascontiguousarray(x[None, None]), dict(D=Ds, d=ds, ndcnt=cnt, q=qs, Pf=Pfs, penalty=pens)
+    out = dict(D=Ds, d=ds, ndcnt=cnt, q=qs, Pf=Pfs, penalty=pens)
+    if penalty2 is not None:
+        out['penalty2'] = pens2
+    return As, Bs, Hs, np.ascontiguousarray(x[None, None]), out
 
 
+@_keyword_penalty2
 def mpc_step(A, B, Q, R, N, x0, horizon, phase0=0, D=None, d=None, q=None, Pf=None, tol=TOL, max_iter=MAX_ITER, offset=None, qf=None, terminal_rhs=None, penalty=None,
-             J=None, r=None, terminal=None):
+             J=None, r=None, terminal=None, penalty2=None):
     """One MPC step of one model in the reference's calling style: A, B, Q, R, N (the cross term) single matrices (p = 1) or lists of length p as in horizon_lqr,
     D, d the rows D_k [x; u] <= d_k (single arrays or lists of p; None entries: no rows at that stage), q, Pf likewise.  Returns (u0, X [horizon+1,nx],
     U [horizon,nu], lam [horizon,nd], info dict).  penalty: the weights of the soft rows, one vector (every stage) or a list of p vectors, one entry per row of
     D_k; np.inf entries and None stages are hard.  With it info gains 'eps' [horizon,nd] (the slacks) and 'nviol'.  J, r: the equality rows J_k [x; u] = r_k
     (single arrays or lists of p, None entries: no rows at that stage; r None: zero); terminal: 'constraint' (x_N = 0), one matrix Tx [nt,nx] or a list of p
     (Tx x_N = 0).  With them info gains 'nu' [horizon,ne], 'nu_term' [nt] and 'eres'.  offset, qf, terminal_rhs: the vectors of the affine problem
-    (mpc_qp_batch), one vector each or a list of p.  RuntimeError when the solve did not converge (an infeasible problem)."""
+    (mpc_qp_batch), one vector each or a list of p.  penalty2: the quadratic weights of the slacks (mpc_qp_batch), one vector or a list of p vectors like
+    penalty; without penalty the rows with Z > 0 are pure quadratic and the others hard.  RuntimeError when the solve did not converge (an infeasible problem)."""
     who = 'mpc_step'
-    As, Bs, Hs, X0, kw = _stack_one(who, A, B, Q, R, N, x0, D, d, q, Pf, penalty)
+    As, Bs, Hs, X0, kw = _stack_one(who, A, B, Q, R, N, x0, D, d, q, Pf, penalty, penalty2)
     kw.update(_stack_eq(who, As.shape[1], As.shape[2], As.shape[2] + Bs.shape[3], J, r, terminal))
     kw.update(_stack_affine(who, As.shape[1], As.shape[2], Bs.shape[3], kw['terminal'], offset, qf, terminal_rhs))
     res = mpc_qp_batch(As, Bs, Hs, X0, horizon, phase0, tol=tol, max_iter=max_iter, **kw)
@@ -443,17 +528,18 @@ def mpc_step(A, B, Q, R, N, x0, horizon, phase0=0, D=None, d=None, q=None, Pf=No
     return res['u0'][0, 0], res['X'][0, 0], res['U'][0, 0], res['lam'][0, 0], {k: res[k][0, 0] for k in INFO_FIELDS + ('nact', 'hres') + (('eps', 'nviol') if 'eps' in res else ()) + (('nu', 'nu_term', 'eres') if 'nu' in res else ())}
 
 
+@_keyword_penalty2
 def mpc_closed_loop_sim(A, B, Q, R, N, x0, horizon, steps, phase0=0, D=None, d=None, q=None, Pf=None, tol=TOL, max_iter=MAX_ITER, offset=None, qf=None,
-                        terminal_rhs=None, plant=None, disturbance=None, penalty=None, J=None, r=None, terminal=None):
+                        terminal_rhs=None, plant=None, disturbance=None, penalty=None, J=None, r=None, terminal=None, penalty2=None):
     """The reference's closed_loop_sim with the inequality-constrained tracking MPC in the loop and the linear plant, one model in the calling style of mpc_step.
     Returns the reference's log: {'x': steps + 1 states, 'u': steps inputs, 'l': steps stage costs 1/2 z' H_k z + q_k' z, 'h': steps arrays d_k - D_k [x_t; u_t]
     (>= 0 when the rows hold; empty at a stage without rows)} and 'iters', 'nact'.  With penalty (as in mpc_step) 'h' stays d - D z (negative on a violated soft
     row), 'usc' holds the slack of the applied step, max(0, D z - d) on the soft rows and 0 on the hard ones (the reference's usc), and 'nviol' the count of the
     solver.  With J, r, terminal (as in mpc_step) the log gains 'eres': max|J_k [x_t; u_t] - r_k| of every step.  offset, qf, terminal_rhs as in mpc_step; plant = (Ap, Bp) or (Ap, Bp, cp), each a single
     array or a list of p, and disturbance [steps, nx]: the plant of the loop, x_{t+1} = Ap_k x_t + Bp_k u_t + cp_k + W_t (mpc_closed_loop_batch).
-    RuntimeError when a step did not converge."""
+    penalty2 as in mpc_step: 'usc' covers the rows of both kinds (L1, L1 + L2 and pure quadratic).  RuntimeError when a step did not converge."""
     who = 'mpc_closed_loop_sim'
-    As, Bs, Hs, X0, kw = _stack_one(who, A, B, Q, R, N, x0, D, d, q, Pf, penalty)
+    As, Bs, Hs, X0, kw = _stack_one(who, A, B, Q, R, N, x0, D, d, q, Pf, penalty, penalty2)
     kw.update(_stack_eq(who, As.shape[1], As.shape[2], As.shape[2] + Bs.shape[3], J, r, terminal))
     kw.update(_stack_affine(who, As.shape[1], As.shape[2], Bs.shape[3], kw['terminal'], offset, qf, terminal_rhs, plant, disturbance, steps))
     res = mpc_closed_loop_batch(As, Bs, Hs, X0, horizon, steps, phase0, tol=tol, max_iter=max_iter, **kw)
@@ -487,7 +573,7 @@ def about_reference(A, B, H, xref, uref, q=None, Pf=None, D=None, d=None, J=None
         offset_k = xref_{(k+1) % p} - A_k xref_k - B_k uref_k       (zero when the reference is a trajectory of the model),
         q_k - H_k wref_k,   d_k + D_k wref_k,   r_k + J_k wref_k,   qf_k = -Pf_k xref_k,   terminal_rhs_k = Tx_k xref_k  (xref_k for terminal='constraint').
     Returns a dict with offset, q, and, where the argument is given, Pf, qf, D, d, J, r, terminal, terminal_rhs: pass it as **kwargs next to A, B, H and the
-    ABSOLUTE X0 (and ndcnt, necnt, penalty, which do not change).  The solution is the deviation solution plus the reference with the same multipliers; the
+    ABSOLUTE X0 (and ndcnt, necnt, penalty, penalty2, which do not change: penalty2 passes through like penalty).  The solution is the deviation solution plus the reference with the same multipliers; the
     cost differs by a constant.  Host-side numpy or torch (all arguments of one kind), no kernel."""
     who = 'about_reference'
     Tx = terminal if hasattr(terminal, 'shape') else None
