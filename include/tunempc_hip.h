@@ -402,7 +402,8 @@ int tmpc_closed_loop_batch_device(int nb, int p, int nx, int mb, int nr, int ng,
  *     min  sum_{j<N} (1/2 z_j' H_k z_j + q_k' z_j) + 1/2 x_N' Pf_{k_N} x_N,   z_j = [x_j; u_j],   k = k_j = (k0 + j) mod p,
  *     s.t. x_{j+1} = A_k x_j + B_k u_j,  x_0 given,   D_k z_j <= d_k (first ndcnt_k rows of the stage),   j = 0 .. N-1,
  * solved at the steps t = 0 .. T-1 from the phase (k0 + t) mod p; u_0 is applied and x <- A_k x + B_k u_0 (the linear plant), one launch for the whole batch.
- * Not served (there are no arguments for them): warm starts between steps, the nonlinear plant, nt > nx.
+ * Not served (there are no arguments for them): nt > nx; the nonlinear plant inside the launch (a caller steps it with one launch per step and a shifted guess).
+ * Warm starts between the steps and from a guess: the tmpc_mpc_qp_warm_batch_* entries below.
  * Soft rows (exact L1 slack penalties, the reference's `usc`): the tmpc_mpc_qp_soft_batch_* entries below.  Equality rows J z = r and the terminal
  * constraint Tx x_N = 0 (the reference's g and p_operator): the tmpc_mpc_qp_eq_batch_* entries below.  The affine problem (a dynamics offset, a linear
  * terminal cost, a terminal right-hand side, a plant that is not the model, a disturbance): the tmpc_mpc_qp_aff_batch_* entries below.  Quadratic slack
@@ -539,6 +540,43 @@ int tmpc_mpc_qp_quad_batch_device(int nb, int p, int nx, int mb, int nd, int N, 
                                   const double* r, const int32_t* necnt, int nt, const double* Tx, double* Nu, double* NuT, double* eres, const double* offset,
                                   const double* qf, const double* terminal_rhs, const double* Ap, const double* Bp, const double* cp, const double* W,
                                   const double* penalty2);
+
+/* The same step and loop WARM-STARTED (the reference's Pmpc.step always starts from its shifted previous solution): the 51 arguments of the quad entries, then
+ *   warm_flags: bit 0 every step t > 0 of the loop starts from the shifted iterate of step t - 1; bit 1 step 0 starts from the guess below; bit 2 (only with
+ *               bit 1) the guess is shifted by one stage first (it comes from the previous phase);  0: the quad entry runs (the same bits), warmlog is zero;
+ *   warm_floor: delta > 0 of the floors (1e-2 is the default of the Python calls);
+ *   the guess, exactly with bit 1, Xg and Ug at the least, the others NULL where the problem has none (NULL: zeros): Xg [nb][ns][N+1][nx], Ug [nb][ns][N][mb],
+ *               Lamg [nb][ns][N][nd], Eg [nb][ns][N][nd] (only with penalty), Nug [nb][ns][N][ne], NuTg [nb][ns][nt] -- what an earlier call returned as Xol,
+ *               Uol, Lam, Eol, Nu, NuT;
+ *   warmlog int32 [nb][T][ns], optional, time-major: 0 the step started cold, 1 the warm start delivered it, 2 the warm attempt failed and the cold restart
+ *               delivered it, -1 from a failed step on.
+ * The rule (tmpc_mpc_qp.h; tests/mpc_qp_warm_reference.py states the same one).  Shift: new stage j takes old stage j + 1 for j <= N - 2, x_0 is the measured
+ * state, u_{N-1} repeats the old last input, x_N = A_k x_{N-1} + B_k u_{N-1} (+ c_k) at the phase of the new last stage; multipliers and slacks shift the
+ * same way, the new last stage gets zeros before the floors, nu_T is kept.  Without a shift everything is as given and x_0 is replaced.  Floors: a hard row
+ * takes s = max(d - D z, delta), lam = max(lam, delta); an L1 or L1 + L2 row e = max(e, delta), lam = clip(lam, delta, c + Z e - delta),
+ * nu = c + Z e - lam (lam = nu = (c + Z e) / 2 when c + Z e < 2 delta), s = max(d - D z + e, delta); a pure quadratic row lam = max(lam, delta),
+ * s = max(d - D z + lam / Z, delta); equality and terminal multipliers are free.  s and nu are derived, never read.  Fallbacks: an instance whose guess holds
+ * a non-finite entry starts cold (a failed predecessor returns NaN); a warm-started step that ends with status 1 or 2 is solved again from the cold start
+ * within the step and iters counts both attempts, so an infeasible instance costs two runs of max_iter; status 3 is not retried.  The kernels are WARM
+ * instantiations beside each of the eight, with their LDS layout and workspace.
+ * TMPC_E_ARG, besides the above: warm_flags outside 0 .. 7 or bit 2 without bit 1; guess arrays without bit 1, or bit 1 without Xg and Ug; Lamg with nd = 0,
+ * Eg without penalty, Nug with ne = 0, NuTg with nt = 0; warm_floor <= 0, non-finite or NaN. */
+int tmpc_mpc_qp_warm_batch_host(int nb, int p, int nx, int mb, int nd, int N, int ns, int T, int k0, const double* A, const double* B, const double* H,
+                                const double* q, const double* Pf, const double* D, const int32_t* ndcnt, const double* d, const double* X0, double tol,
+                                int max_iter, double* U0, double* XT, double* info, double* X, double* U, int32_t* iters, int32_t* nact, double* hres,
+                                double* Xol, double* Uol, double* Lam, const double* penalty, double* Eol, int32_t* nviol, int ne, const double* J,
+                                const double* r, const int32_t* necnt, int nt, const double* Tx, double* Nu, double* NuT, double* eres, const double* offset,
+                                const double* qf, const double* terminal_rhs, const double* Ap, const double* Bp, const double* cp, const double* W,
+                                const double* penalty2, int warm_flags, double warm_floor, const double* Xg, const double* Ug, const double* Lamg,
+                                const double* Eg, const double* Nug, const double* NuTg, int32_t* warmlog);
+int tmpc_mpc_qp_warm_batch_device(int nb, int p, int nx, int mb, int nd, int N, int ns, int T, int k0, const double* A, const double* B, const double* H,
+                                  const double* q, const double* Pf, const double* D, const int32_t* ndcnt, const double* d, const double* X0, double tol,
+                                  int max_iter, double* U0, double* XT, double* info, double* X, double* U, int32_t* iters, int32_t* nact, double* hres,
+                                  double* Xol, double* Uol, double* Lam, const double* penalty, double* Eol, int32_t* nviol, int ne, const double* J,
+                                  const double* r, const int32_t* necnt, int nt, const double* Tx, double* Nu, double* NuT, double* eres, const double* offset,
+                                  const double* qf, const double* terminal_rhs, const double* Ap, const double* Bp, const double* cp, const double* W,
+                                  const double* penalty2, int warm_flags, double warm_floor, const double* Xg, const double* Ug, const double* Lamg,
+                                  const double* Eg, const double* Nug, const double* NuTg, int32_t* warmlog);
 
 /* Accumulated hipEvent timings since the last call (ms) when TMPC_FLAG_PROFILE is set, 16 doubles:
  * out[0] stage_pre+ctrl, [1] schur assembly, [2] block factorisation (all kernels of tmpc_cr.h's factor phase), [3] predictor

@@ -28,6 +28,7 @@ EXPORTS = [
     'tmpc_closed_loop_batch_host', 'tmpc_closed_loop_batch_device', 'tmpc_mpc_qp_batch_host', 'tmpc_mpc_qp_batch_device',
     'tmpc_mpc_qp_soft_batch_host', 'tmpc_mpc_qp_soft_batch_device', 'tmpc_mpc_qp_eq_batch_host', 'tmpc_mpc_qp_eq_batch_device',
     'tmpc_mpc_qp_aff_batch_host', 'tmpc_mpc_qp_aff_batch_device', 'tmpc_mpc_qp_quad_batch_host', 'tmpc_mpc_qp_quad_batch_device',
+    'tmpc_mpc_qp_warm_batch_host', 'tmpc_mpc_qp_warm_batch_device',
     'tmpc_last_error', 'tmpc_version',
 ]
 # ... and in include/tunempc_hip_debug.h (unit-test / diagnostic entries)
@@ -171,6 +172,10 @@ def load_library():
     lib.tmpc_mpc_qp_quad_batch_host.argtypes = lib.tmpc_mpc_qp_aff_batch_host.argtypes + [dp]
     lib.tmpc_mpc_qp_quad_batch_device.restype = C.c_int
     lib.tmpc_mpc_qp_quad_batch_device.argtypes = lib.tmpc_mpc_qp_aff_batch_device.argtypes + [vp]
+    lib.tmpc_mpc_qp_warm_batch_host.restype = C.c_int
+    lib.tmpc_mpc_qp_warm_batch_host.argtypes = lib.tmpc_mpc_qp_quad_batch_host.argtypes + [C.c_int, C.c_double] + [dp] * 6 + [ip]
+    lib.tmpc_mpc_qp_warm_batch_device.restype = C.c_int
+    lib.tmpc_mpc_qp_warm_batch_device.argtypes = lib.tmpc_mpc_qp_quad_batch_device.argtypes + [C.c_int, C.c_double] + [vp] * 7
     lib.tmpc_get_profile.restype = C.c_int
     lib.tmpc_get_profile.argtypes = [vp, dp]
     lib.tmpc_get_trace.restype = C.c_int
@@ -961,14 +966,15 @@ def _mpc_qp_eq_terminal(Tx, nx):
     return int(Tx.shape[2]), Tx, int(Tx.shape[2])
 
 
-_MPC_QP_LEVELS = {'hard': '', 'soft': 'soft_', 'eq': 'eq_', 'aff': 'aff_', 'quad': 'quad_'}
+_MPC_QP_LEVELS = {'hard': '', 'soft': 'soft_', 'eq': 'eq_', 'aff': 'aff_', 'quad': 'quad_', 'warm': 'warm_'}
 
 
 def _mpc_qp_call(level, kind, A, B, H, q, Pf, D, ndcnt, d, X0, N, T, k0, tol, max_iter, return_traj, return_ol, penalty=None, J=None, r=None, necnt=None,
-                 Tx=None, aff=None, penalty2=None):
-    """The ten MPC QP entries: tmpc_mpc_qp_<level>batch_<host or device> of the level 'hard', 'soft', 'eq', 'aff' or 'quad' on validated, contiguous arrays of `kind`
+                 Tx=None, aff=None, penalty2=None, warm=None):
+    """The twelve MPC QP entries: tmpc_mpc_qp_<level>batch_<host or device> of the level 'hard', 'soft', 'eq', 'aff', 'quad' or 'warm' on validated, contiguous arrays of `kind`
     (_HostArrays: numpy, _DeviceArrays: torch tensors of one GPU).  Allocates the outputs, passes the 31 common arguments and the tails of the level (soft:
-    penalty, Eol, nviol; eq: the rows and Nu, NuT, eres; aff: the seven arrays; quad: penalty2), an absent or empty array as NULL, and returns the dict of the level.  The
+    penalty, Eol, nviol; eq: the rows and Nu, NuT, eres; aff: the seven arrays; quad: penalty2; warm = (flags, floor, Xg, Ug, Lamg, Eg, Nug, NuTg): these and
+    warmlog), an absent or empty array as NULL, and returns the dict of the level (warm: with warmlog [nb,ns,T] int32).  The
     library stores the logs time-major: X, U and the per-step logs are permuted views, nothing is copied."""
     lib = load_library()
     xp = kind(A)
@@ -978,7 +984,7 @@ def _mpc_qp_call(level, kind, A, B, H, q, Pf, D, ndcnt, d, X0, N, T, k0, tol, ma
     nd = 0 if D is None else D.shape[2]
     ne = 0 if J is None else J.shape[2]
     nt, Txa, ntr = _mpc_qp_eq_terminal(Tx, nx)
-    eq = level in ('eq', 'aff', 'quad')
+    eq = level in ('eq', 'aff', 'quad', 'warm')
     soft = level == 'soft' or (eq and penalty is not None)                  # (the eq level without penalty passes Eol = nviol = NULL)
     traj = lambda *sh: xp.f64(*sh) if return_traj else None
     ol = lambda *sh: xp.f64(*sh) if return_ol else None
@@ -996,10 +1002,13 @@ def _mpc_qp_call(level, kind, A, B, H, q, Pf, D, ndcnt, d, X0, N, T, k0, tol, ma
         args += [ptr(penalty), ptr(Eol), ptr(nviol)]
     if eq:
         args += [ne, rows(J, ne), rows(r, ne), rows(necnt, ne), nt, ptr(Txa), ptr(Nu), ptr(NuT), ptr(eres)]
-    if level in ('aff', 'quad'):
+    if level in ('aff', 'quad', 'warm'):
         args += [ptr(a) for a in (aff if aff is not None else (None,) * 7)]
-    if level == 'quad':
+    if level in ('quad', 'warm'):
         args += [ptr(penalty2)]
+    if level == 'warm':
+        warmlog = xp.i32(nb, T, ns)
+        args += [int(warm[0]), float(warm[1])] + [None if a is None else ptr(a) for a in warm[2:8]] + [ptr(warmlog)]
     rc = xp.call(getattr(lib, name), args)
     if rc == -1:      # TMPC_E_ARG: the library's message names the argument
         raise ValueError(lib.tmpc_last_error().decode())
@@ -1010,6 +1019,8 @@ def _mpc_qp_call(level, kind, A, B, H, q, Pf, D, ndcnt, d, X0, N, T, k0, tol, ma
         out.update(Nu=Nu, NuT=NuT, eres=tr3(eres))
     if soft:
         out.update(Eol=Eol, nviol=tr3(nviol))
+    if level == 'warm':
+        out['warmlog'] = tr3(warmlog)
     return out
 
 
@@ -1091,3 +1102,17 @@ def mpc_qp_quad_batch_device(A, B, H, q, Pf, D, ndcnt, d, penalty, J, r, necnt, 
     """tmpc_mpc_qp_quad_batch_device on validated, contiguous torch tensors of one GPU -> the dict of mpc_qp_quad_batch_host with torch tensors."""
     return _mpc_qp_call('quad', _DeviceArrays, A, B, H, q, Pf, D, ndcnt, d, X0, N, T, k0, tol, max_iter, return_traj, return_ol, penalty, J, r, necnt, Tx,
                         None if aff is None else tuple(aff), penalty2)
+
+
+def mpc_qp_warm_batch_host(A, B, H, q, Pf, D, ndcnt, d, penalty, J, r, necnt, Tx, aff, penalty2, warm, X0, N, T, k0, tol, max_iter, return_traj, return_ol):
+    """tmpc_mpc_qp_warm_batch_host on validated, contiguous numpy arrays: the arguments of mpc_qp_quad_batch_host (penalty, penalty2, aff None where the call
+    has none) and warm = (flags, floor, Xg, Ug, Lamg, Eg, Nug, NuTg), the guess arrays None or arrays -> the dict of mpc_qp_eq_batch_host with warmlog
+    [nb,ns,T] int32 (0 cold, 1 warm, 2 the cold restart of a failed warm attempt, -1 from a failed step on)."""
+    return _mpc_qp_call('warm', _HostArrays, A, B, H, q, Pf, D, ndcnt, d, X0, N, T, k0, tol, max_iter, return_traj, return_ol, penalty, J, r, necnt, Tx,
+                        None if aff is None else tuple(aff), penalty2, tuple(warm))
+
+
+def mpc_qp_warm_batch_device(A, B, H, q, Pf, D, ndcnt, d, penalty, J, r, necnt, Tx, aff, penalty2, warm, X0, N, T, k0, tol, max_iter, return_traj, return_ol):
+    """tmpc_mpc_qp_warm_batch_device on validated, contiguous torch tensors of one GPU -> the dict of mpc_qp_warm_batch_host with torch tensors."""
+    return _mpc_qp_call('warm', _DeviceArrays, A, B, H, q, Pf, D, ndcnt, d, X0, N, T, k0, tol, max_iter, return_traj, return_ol, penalty, J, r, necnt, Tx,
+                        None if aff is None else tuple(aff), penalty2, tuple(warm))

@@ -2206,14 +2206,14 @@ int tmpc_closed_loop_batch_host(int nb, int p, int nx, int mb, int nr, int ng, i
 
 // The inequality-constrained MPC step and closed loop (tmpc_mpc_qp.h): one workgroup per instance (problem, initial state), min(instances, MQ_SLOTS) workgroups
 // loop over the instances, each with its slot of the workspace.
-// The ten entries (hard, soft, eq, aff, quad; host and device) differ in their argument lists only.  An entry writes its arguments into an MpcQpCall (what it has no
+// The twelve entries (hard, soft, eq, aff, quad, warm; host and device) differ in their argument lists only.  An entry writes its arguments into an MpcQpCall (what it has no
 // argument for stays null / zero) and hands the record to mpc_qp_host or mpc_qp_device.  Either checks it once under the entry's name (mpc_qp_validate), reads
 // the kernel off it with its LDS and workspace sizes (mpc_qp_kind), zeroes the outputs that this kernel does not write (mpc_qp_zero_unwritten) and launches
 // (mpc_qp_launch); the host path stages every array of the record through one device buffer.  No entry calls another.
 static_assert(MQ_INFO == TMPC_MPC_QP_INFO, "tunempc_hip.h: info stride of the MPC QP entries");
 constexpr long long MQ_WS_CAP_BYTES = 1LL << 30;      // the workspace of a launch: fewer slots beyond this (one slot at the least)
 
-// One call: the arguments of the quad entries (the longest list) in their order; nt as the caller gave it (-1: x_N = 0 without Tx, nx rows).  The pointers are
+// One call: the arguments of the warm entries (the longest list) in their order; nt as the caller gave it (-1: x_N = 0 without Tx, nx rows).  The pointers are
 // the caller's, host or device by the path; mpc_qp_host launches a copy that holds the device images.
 struct MpcQpCall {
   const char* who;
@@ -2226,16 +2226,20 @@ struct MpcQpCall {
   double* Nu = nullptr; double* NuT = nullptr; double* eres = nullptr;
   MpcQpAff aff = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};                                                      // the aff entries
   const double* penalty2 = nullptr;                                                                                                    // the quad entries
+  int warm_flags = 0; double warm_floor = 0.0;                                                                                         // the warm entries
+  const double* gX = nullptr; const double* gU = nullptr; const double* gLam = nullptr; const double* gEps = nullptr; const double* gNu = nullptr;
+  const double* gNuT = nullptr; int32_t* warmlog = nullptr;
+  bool warm_entry = false;                          // set by the warm entries: only they check the warm arguments
   int ntk() const { return nt < 0 ? nx : nt; }      // terminal rows of the kernel
 };
 #define MPC_QP_ARGS31 nb, p, nx, mb, nd, N, ns, T, k0, A, B, H, q, Pf, D, ndcnt, d, X0, tol, max_iter, U0, XT, info, X, U, iters, nact, hres, Xol, Uol, Lam
 
 // The kernel of a call: SOFT with a penalty; EQ with equality rows, terminal rows or an affine array; AFF (an instantiation of the two EQ kernels only) with an
 // affine array; QUAD (an instantiation of the plain SOFT kernel and of the SOFT AFF kernel only, the latter for every call with rows or an affine array)
-// with a penalty2.  Sizes in doubles: the LDS of the hard layout, of the soft layout (the hard one without penalty) and of the kernel that runs -- the layouts
+// with a penalty2; WARM (an instantiation beside each of the eight) with bit 0 or bit 1 of warm_flags.  Sizes in doubles: the LDS of the hard layout, of the soft layout (the hard one without penalty) and of the kernel that runs -- the layouts
 // nest, the three LDS tests of mpc_qp_validate tell which part no longer fits --, and the workspace per slot.  Row capacities enter the LDS sizes clamped to
 // 65536 (no 32-bit overflow before they are refused; a call that passes the checks is far below).
-struct MpcQpKind { bool soft, eq, aff, quad; long long lds_hard, lds_soft, lds, ws; };
+struct MpcQpKind { bool soft, eq, aff, quad, warm; long long lds_hard, lds_soft, lds, ws; };
 static bool mpc_qp_aff_any(const MpcQpAff& a) { return a.c || a.qf || a.t || a.Ap || a.Bp || a.cp || a.W; }
 static MpcQpKind mpc_qp_kind(const MpcQpCall& c) {
   MpcQpKind k;
@@ -2243,6 +2247,7 @@ static MpcQpKind mpc_qp_kind(const MpcQpCall& c) {
   k.quad = k.soft && c.penalty2 != nullptr;
   k.aff = mpc_qp_aff_any(c.aff);
   k.eq = c.ne > 0 || c.nt != 0 || k.aff;
+  k.warm = (c.warm_flags & 3) != 0;
   const int nd = c.nd < 65536 ? c.nd : 65536, ne = c.ne < 65536 ? c.ne : 65536;
   k.lds = k.lds_soft = k.lds_hard = mpc_qp_lds(c.nx, c.mb, nd).total;
   k.ws = mpc_qp_ws_doubles(c.nx, c.mb, c.nd, c.N);
@@ -2335,6 +2340,28 @@ static int mpc_qp_validate(const MpcQpCall& c, MpcQpKind* kind) {
     snprintf(g_err, sizeof(g_err), "%s: bad argument (the plant's Ap and Bp come together; got %s without %s)", who, c.aff.Ap ? "Ap" : "Bp", c.aff.Ap ? "Bp" : "Ap");
     return TMPC_E_ARG;
   }
+  // the warm start: flags within bits 0 .. 2, a shift only of a guess, the guess exactly with bit 1 (X and U at the least), a floor > 0
+  if (c.warm_entry) {
+    const bool any = c.gX || c.gU || c.gLam || c.gEps || c.gNu || c.gNuT;
+    if (c.warm_flags < 0 || c.warm_flags > 7 || ((c.warm_flags & 4) && !(c.warm_flags & 2))) {
+      snprintf(g_err, sizeof(g_err), "%s: bad argument (warm_flags: bit 0 warm loop, bit 1 a guess is given, bit 2 (only with bit 1) the guess is shifted; got %d)",
+               who, c.warm_flags);
+      return TMPC_E_ARG;
+    }
+    if (((c.warm_flags & 2) != 0) != any || ((c.warm_flags & 2) && (!c.gX || !c.gU))) {
+      snprintf(g_err, sizeof(g_err), "%s: bad argument (the guess arrays come exactly with bit 1 of warm_flags, Xg and Ug at the least; got warm_flags = %d)", who,
+               c.warm_flags);
+      return TMPC_E_ARG;
+    }
+    if ((c.gLam && nd < 1) || (c.gEps && !c.penalty) || (c.gNu && ne < 1) || (c.gNuT && nt == 0)) {
+      snprintf(g_err, sizeof(g_err), "%s: bad argument (Lamg only with rows, Eg only with penalty, Nug only with equality rows, NuTg only with terminal rows)", who);
+      return TMPC_E_ARG;
+    }
+    if (!(c.warm_floor > 0.0 && c.warm_floor < INFINITY)) {
+      snprintf(g_err, sizeof(g_err), "%s: bad argument (warm_floor > 0 and finite; got %g)", who, c.warm_floor);
+      return TMPC_E_ARG;
+    }
+  }
   *kind = k;
   return TMPC_OK;
 }
@@ -2368,18 +2395,21 @@ static int mpc_qp_host_ranges(const char* who, size_t nb, size_t p, const int32_
   return TMPC_OK;
 }
 
-// The outputs that the kernel of a call does not write -- Eol and nviol without SOFT, eres without EQ; Nu and NuT are empty then -- are zero by the header:
+// The outputs that the kernel of a call does not write -- Eol and nviol without SOFT, eres without EQ; Nu and NuT are empty then; warmlog without WARM (every
+// step cold) -- are zero by the header:
 // zero(pointer, bytes) on each that is given; mpc_qp_kernel_call takes them out of the record that the kernel gets.
 static int mpc_qp_zero_unwritten(const MpcQpCall& c, const MpcQpKind& k, hipError_t (*zero)(void*, size_t)) {
   const size_t sn = (size_t)c.nb * c.ns;
   if (!k.soft && c.Eol && c.nd > 0) HIPCHK(zero(c.Eol, sn * c.N * c.nd * 8));
   if (!k.soft && c.nviol) HIPCHK(zero(c.nviol, sn * c.T * sizeof(int32_t)));
   if (!k.eq && c.eres) HIPCHK(zero(c.eres, sn * c.T * 8));
+  if (!k.warm && c.warmlog) HIPCHK(zero(c.warmlog, sn * c.T * sizeof(int32_t)));
   return TMPC_OK;
 }
 static MpcQpCall mpc_qp_kernel_call(MpcQpCall c, const MpcQpKind& k) {
   if (!k.soft) { c.Eol = nullptr; c.nviol = nullptr; }
   if (!k.eq) { c.Nu = nullptr; c.NuT = nullptr; c.eres = nullptr; }
+  if (!k.warm) c.warmlog = nullptr;
   return c;
 }
 
@@ -2392,7 +2422,13 @@ static int mpc_qp_launch(const MpcQpCall& c, const MpcQpKind& k) {
   static const Kernel kernels[3][2] = {{mpc_qp_kernel<false, false, false>(), mpc_qp_kernel<true, false, false>()},      // [eq + aff][soft]
                                        {mpc_qp_kernel<false, true, false>(), mpc_qp_kernel<true, true, false>()},
                                        {mpc_qp_kernel<false, true, true>(), mpc_qp_kernel<true, true, true>()}};
-  const Kernel kern = k.quad ? quad_kernels[(int)k.eq] : kernels[(int)k.eq + (int)k.aff][(int)k.soft];
+  // the WARM instantiations: one beside each of the eight, so a warm call runs at the occupancy of its cold call
+  static const Kernel warm_quad_kernels[2] = {k_mpc_qp<true, false, false, true, true>, k_mpc_qp<true, true, true, true, true>};
+  static const Kernel warm_kernels[3][2] = {{k_mpc_qp<false, false, false, false, true>, k_mpc_qp<true, false, false, false, true>},
+                                            {k_mpc_qp<false, true, false, false, true>, k_mpc_qp<true, true, false, false, true>},
+                                            {k_mpc_qp<false, true, true, false, true>, k_mpc_qp<true, true, true, false, true>}};
+  const Kernel kern = k.warm ? (k.quad ? warm_quad_kernels[(int)k.eq] : warm_kernels[(int)k.eq + (int)k.aff][(int)k.soft])
+                             : (k.quad ? quad_kernels[(int)k.eq] : kernels[(int)k.eq + (int)k.aff][(int)k.soft]);
   const long long ninst = (long long)c.nb * c.ns, per = k.ws * 8;
   long long slots = ninst < MQ_SLOTS ? ninst : MQ_SLOTS;
   if (slots * per > MQ_WS_CAP_BYTES) slots = MQ_WS_CAP_BYTES / per;
@@ -2404,7 +2440,7 @@ static int mpc_qp_launch(const MpcQpCall& c, const MpcQpKind& k) {
   hipLaunchKernelGGL(kern, dim3((unsigned)slots), dim3(LQR_NT), (size_t)k.lds * sizeof(double), 0, c.p, c.nx, c.mb, c.nd, lcw, c.N, c.ns, c.T, c.k0, ninst, c.A, c.B,
                      c.H, c.q, c.Pf, c.D, (const int*)c.ndcnt, c.d, c.X0, c.tol, c.max_iter, (double*)g_mpc_qp_ws.p, c.U0, c.XT, c.info, c.X, c.U, (int*)c.iters,
                      (int*)c.nact, c.hres, c.Xol, c.Uol, c.Lam, c.penalty, c.Eol, (int*)c.nviol, c.ne, c.J, c.r, (const int*)c.necnt, c.ntk(), c.Tx, c.Nu, c.NuT,
-                     c.eres, c.aff, c.penalty2);
+                     c.eres, c.aff, c.penalty2, MpcQpWarm{c.warm_flags, c.warm_floor, c.gX, c.gU, c.gLam, c.gEps, c.gNu, c.gNuT, (int*)c.warmlog});
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(0));
   return TMPC_OK;
@@ -2458,6 +2494,8 @@ static int mpc_qp_host(const MpcQpCall& c) {
     place(dc.aff.c, st * nx * 8, false); place(dc.aff.qf, st * nx * 8, false); place(dc.aff.t, st * ntk * 8, false); place(dc.aff.Ap, st * nx * nx * 8, false);
     place(dc.aff.Bp, st * nx * mb * 8, false); place(dc.aff.cp, st * nx * 8, false); place(dc.aff.W, cS * nx * 8, false);
     place(dc.penalty2, st * nd * 8, false);
+    place(dc.gX, sn * (N + 1) * nx * 8, false); place(dc.gU, sn * N * mb * 8, false); place(dc.gLam, sn * N * nd * 8, false); place(dc.gEps, sn * N * nd * 8, false);
+    place(dc.gNu, sn * N * ne * 8, false); place(dc.gNuT, sn * ntk * 8, false); place(dc.warmlog, cS * sizeof(int32_t), true);
   };
   arrays();
   HIPCHK(g_mpc_qp_scratch.reserve(total + 8));
@@ -2561,6 +2599,32 @@ int tmpc_mpc_qp_quad_batch_host(int nb, int p, int nx, int mb, int nd, int N, in
                                 const double* penalty2) {
   return mpc_qp_host(MpcQpCall{"tmpc_mpc_qp_quad_batch_host", MPC_QP_ARGS31, penalty, Eol, nviol, ne, J, r, necnt, nt, Tx, Nu, NuT, eres,
                                {offset, qf, terminal_rhs, Ap, Bp, cp, W}, penalty2});
+}
+
+// Warm starts (tmpc_mpc_qp.h, the WARM instantiations): the 51 arguments of the quad entries, then warm_flags, warm_floor, the guess Xg, Ug, Lamg, Eg, Nug,
+// NuTg and warmlog.  warm_flags = 0: the kernel of the quad entry with the same arguments (the same bits), warmlog zero.
+int tmpc_mpc_qp_warm_batch_device(int nb, int p, int nx, int mb, int nd, int N, int ns, int T, int k0, const double* A, const double* B, const double* H,
+                                  const double* q, const double* Pf, const double* D, const int32_t* ndcnt, const double* d, const double* X0, double tol,
+                                  int max_iter, double* U0, double* XT, double* info, double* X, double* U, int32_t* iters, int32_t* nact, double* hres,
+                                  double* Xol, double* Uol, double* Lam, const double* penalty, double* Eol, int32_t* nviol, int ne, const double* J,
+                                  const double* r, const int32_t* necnt, int nt, const double* Tx, double* Nu, double* NuT, double* eres, const double* offset,
+                                  const double* qf, const double* terminal_rhs, const double* Ap, const double* Bp, const double* cp, const double* W,
+                                  const double* penalty2, int warm_flags, double warm_floor, const double* Xg, const double* Ug, const double* Lamg,
+                                  const double* Eg, const double* Nug, const double* NuTg, int32_t* warmlog) {
+  return mpc_qp_device(MpcQpCall{"tmpc_mpc_qp_warm_batch_device", MPC_QP_ARGS31, penalty, Eol, nviol, ne, J, r, necnt, nt, Tx, Nu, NuT, eres,
+                                 {offset, qf, terminal_rhs, Ap, Bp, cp, W}, penalty2, warm_flags, warm_floor, Xg, Ug, Lamg, Eg, Nug, NuTg, warmlog, true});
+}
+
+int tmpc_mpc_qp_warm_batch_host(int nb, int p, int nx, int mb, int nd, int N, int ns, int T, int k0, const double* A, const double* B, const double* H,
+                                const double* q, const double* Pf, const double* D, const int32_t* ndcnt, const double* d, const double* X0, double tol,
+                                int max_iter, double* U0, double* XT, double* info, double* X, double* U, int32_t* iters, int32_t* nact, double* hres,
+                                double* Xol, double* Uol, double* Lam, const double* penalty, double* Eol, int32_t* nviol, int ne, const double* J,
+                                const double* r, const int32_t* necnt, int nt, const double* Tx, double* Nu, double* NuT, double* eres, const double* offset,
+                                const double* qf, const double* terminal_rhs, const double* Ap, const double* Bp, const double* cp, const double* W,
+                                const double* penalty2, int warm_flags, double warm_floor, const double* Xg, const double* Ug, const double* Lamg,
+                                const double* Eg, const double* Nug, const double* NuTg, int32_t* warmlog) {
+  return mpc_qp_host(MpcQpCall{"tmpc_mpc_qp_warm_batch_host", MPC_QP_ARGS31, penalty, Eol, nviol, ne, J, r, necnt, nt, Tx, Nu, NuT, eres,
+                               {offset, qf, terminal_rhs, Ap, Bp, cp, W}, penalty2, warm_flags, warm_floor, Xg, Ug, Lamg, Eg, Nug, NuTg, warmlog, true});
 }
 #undef MPC_QP_ARGS31
 

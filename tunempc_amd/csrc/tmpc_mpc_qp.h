@@ -5,7 +5,8 @@
 //        and, in the EQ instantiations,   J_k z_j = r_k (first necnt_k rows),  j = 0 .. N-1,   Tx_{k_N} x_N = 0 (nt rows; Tx absent: the identity, x_N = 0),
 // solved T times in a row: step t starts at phase (k0 + t) mod p, applies u_0 and moves x <- A_k x + B_k u_0 on the linear plant.  The AFF instantiations
 // (below) add the dynamics offset c_k, the terminal cost qf' x_N, the terminal right-hand side t and a plant that is not the model.
-// The QUAD instantiations (below) add quadratic slack penalties.  Not served: warm starts between the steps, the nonlinear plant, nt > nx.
+// The QUAD instantiations (below) add quadratic slack penalties, the WARM instantiations (below) warm starts between the steps and from a guess.
+// Not served: nt > nx; the nonlinear plant is served one launch per step (tunempc_amd.mpc_qp.mpc_closed_loop_plant), not inside the launch.
 //
 // Method: a primal-dual interior-point method with Mehrotra's predictor-corrector, started infeasible (z = 0 but x_0, s_i = max(d_i, 1), lam_i = 1).  The
 // multipliers of the dynamics are not variables: they are the adjoint of the iterate, pi_N = Pf x_N, [pi_j; r_u] = H z_j + q + D' lam_j + [A B]' pi_{j+1}, so
@@ -106,6 +107,18 @@
 // Instantiated twice: <true, false, false, true> for calls without equality, terminal or affine arguments, <true, true, true, true> for the rest (null
 // pointers, ne = nt = 0 where there is none).  With QUAD = false the six instantiations are what they were, statement by statement: every statement of QUAD
 // stands behind `if (QUAD)` or is a value selected by it at compile time.
+//
+// Warm starts (the WARM instantiations, one beside each of the eight; WARM is the fifth template parameter).  The reference's Pmpc.step always starts from its
+// shifted previous solution; here WARM replaces the start of a step -- the block that fills Z, S, L, E, NU, NUe, NUT -- and nothing else of the iteration.
+// The rule (shift by one stage, floors by row kind, fallbacks) is stated at that block and in tests/mpc_qp_warm_reference.py.  In the loop the slot's
+// workspace holds the converged iterate of step t - 1 and is shifted in place; at t = 0 the guess arrays are read (MpcQpWarm).  One pass over the stages
+// computes D z (and x_N) for the floors with mq_fetch and the LDS slots of the iteration: no LDS and no workspace of its own.  Fallbacks: a guess with a
+// non-finite entry starts cold; a warm attempt that ends with status 1 or 2 is solved again from the cold start within the step (iters counts both attempts,
+// an infeasible instance costs two runs of max_iter); status 3 is not retried.  The failed attempt stays in the figures of info as well: iters_total and
+// iters_max take the sum of both attempts (iters_max may exceed max_iter after a restart), pivmin the smallest pivot of either.  Every decision is taken on
+// block-reduced values.  The per-step log
+// warmlog [nb][T][ns]: 0 cold, 1 the warm start delivered, 2 the cold restart delivered, -1 from a failed step on.  With WARM = false the eight
+// instantiations are what they were, statement by statement: every statement of WARM stands behind `if (WARM)`.
 #pragma once
 #include "tmpc_closed_loop.h"
 
@@ -196,6 +209,12 @@ __host__ __device__ inline MpcQpEqLds mpc_qp_quad_eq_layout(int nx, int mb, int 
 // neither), cp [nb][p][nx] (null: c), W [nb][ns][T][nx].
 struct MpcQpAff { const double* c; const double* qf; const double* t; const double* Ap; const double* Bp; const double* cp; const double* W; };
 
+// The arguments of the WARM instantiations.  flags: bit 0 every step t > 0 of the loop starts from the shifted iterate of step t - 1, bit 1 step 0 starts
+// from the guess, bit 2 the guess is shifted by one stage first.  floor: delta of the floors.  The guess, each or null (null: zeros): X [nb][ns][N+1][nx],
+// U [nb][ns][N][mb], Lam, Eps [nb][ns][N][nd], Nu [nb][ns][N][ne], NuT [nb][ns][nt] (what an earlier call returned as Xol, Uol, Lam, Eol, Nu, NuT).
+// log int [nb][T][ns] or null: 0 cold, 1 the warm start delivered the step, 2 the warm attempt failed and the cold restart delivered, -1 from a failed step on.
+struct MpcQpWarm { int flags; double floor; const double* X; const double* U; const double* Lam; const double* Eps; const double* Nu; const double* NuT; int* log; };
+
 // (QUAD) Opens every block of statements that only a row with Z > 0 takes.  The compiler may not move an empty volatile statement, so such a block stays a
 // block of its own: it is not merged into the soft row's statements beside it, which are then compiled as they are in the SOFT instantiation -- what the
 // promise "a row with Z = 0 gives the bits of the soft kernel" rests on (products and sums are fused within a block).
@@ -241,9 +260,12 @@ __device__ __forceinline__ void mq_fetch(double* El, double* Hl, double* Dl, int
 // EQ: J [nb][p][ne][n] (null when ne = 0), req [nb][p][ne] or null (zero), necnt [nb][p] or null (all ne rows; clamped to 0 .. ne), Tx [nb][p][nt][nx] or null
 // (nt = nx: the identity), nt <= nx, and each or null Nu [nb][ns][N][ne], NuT [nb][ns][nt], eres [nb][T][ns]; ws: slots of mpc_qp_eq_ws_doubles, LDS of
 // mpc_qp_eq_lds.  Without EQ none of these is read or written.  AFF: aff (MpcQpAff above); without AFF it is not read.
-// QUAD: pen2g [nb][p][nd] (penalty2 beside penalty); without QUAD it is not read.
-template <bool SOFT, bool EQ, bool AFF, bool QUAD>
-__global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd, int lcw, int N, int ns, int T, int k0, long long ninst,
+// QUAD: pen2g [nb][p][nd] (penalty2 beside penalty); without QUAD it is not read.  WARM: wm (MpcQpWarm above); without WARM it is not read.
+// (WARM) the second launch bound, waves per SIMD the compiler has to leave room for: 0 (no bound: the other fifteen instantiations carry no attribute for
+// it, as before) but for the WARM instantiation of the plain soft kernel, whose cold twin runs two waves per SIMD at 246 registers: its few registers over 256 go to scratch instead of halving the occupancy.
+#define MQ_WAVES(SOFT, EQ, QUAD, WARM) (((WARM) && (SOFT) && !(EQ) && !(QUAD)) ? 2 : 0)
+template <bool SOFT, bool EQ, bool AFF, bool QUAD, bool WARM = false>
+__global__ void __launch_bounds__(LQR_NT, MQ_WAVES(SOFT, EQ, QUAD, WARM)) k_mpc_qp(int p, int nx, int mb, int nd, int lcw, int N, int ns, int T, int k0, long long ninst,
                                                    const double* __restrict__ Ag, const double* __restrict__ Bg, const double* __restrict__ Hg,
                                                    const double* __restrict__ qg, const double* __restrict__ Pfg, const double* __restrict__ Dg,
                                                    const int* __restrict__ ndcntg, const double* __restrict__ dg, const double* __restrict__ X0g, double tol,
@@ -253,7 +275,8 @@ __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd
                                                    double* __restrict__ Lamg, const double* __restrict__ peng, double* __restrict__ Eolg,
                                                    int* __restrict__ nviolg, int ne, const double* __restrict__ Jg, const double* __restrict__ reqg,
                                                    const int* __restrict__ necntg, int nt, const double* __restrict__ Txg, double* __restrict__ Nug,
-                                                   double* __restrict__ NuTg, double* __restrict__ eresg, MpcQpAff aff, const double* __restrict__ pen2g) {
+                                                   double* __restrict__ NuTg, double* __restrict__ eresg, MpcQpAff aff, const double* __restrict__ pen2g,
+                                                   MpcQpWarm wm) {
   static_assert(EQ || !AFF, "the AFF instantiations are EQ instantiations");
   static_assert(SOFT || !QUAD, "the QUAD instantiations are SOFT instantiations");
   extern __shared__ __attribute__((aligned(16))) double lds[];
@@ -327,6 +350,7 @@ __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd
       const int k0s = (k0 + t % p) % p;
       int its = 0, nact = -1, nviol = -1;
       double hres = qnan, eres = qnan;
+      int wcode = -1;                                                        // (WARM) the step's entry of the log
       if (status == MQ_OK) {                                                 // (uniform: status is the same in every thread)
         // ---- start of the step: z = 0 but x_0, s = max(d, 1), lam = 1, no direction
         int mt = 0;
@@ -340,6 +364,114 @@ __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd
         // (QUAD) zq_at(e): Z of entry e, pure_at(e): entry e is a pure quadratic row (c = 0: one pair, soft_at is false)
         auto zq_at = [&](int e) { const int j = e / nd, i = e - j * nd, k = (k0s + j % p) % p; return pen2[k * nd + i]; };
         auto pure_at = [&](int e) { const int j = e / nd, i = e - j * nd, k = (k0s + j % p) % p; return i < rows_of(k) && pen[k * nd + i] == 0.0; };
+        // (WARM) warm_now: this attempt starts warm (block-uniform).  In the loop the slot holds the converged iterate of step t - 1; at t = 0 the guess is
+        // taken when every entry of it is finite (a failed predecessor returns NaN).  its_warm: the iterations of a warm attempt that failed.
+        bool warm_now = false, retried = false;
+        int its_warm = 0;
+        if (WARM) {
+          warm_now = t > 0 ? (wm.flags & 1) != 0 : (wm.flags & 2) != 0;
+          if (t == 0 && warm_now) {
+            const size_t gi = b * ns + si;
+            auto fin = [](double v) { return fabs(v) < INFINITY; };
+            double bad = 0.0;
+            for (int e = tid; e < (N + 1) * nx; e += LQR_NT) if (!fin(wm.X[gi * (N + 1) * nx + e])) bad = 1.0;
+            for (int e = tid; e < N * mb; e += LQR_NT) if (!fin(wm.U[gi * N * mb + e])) bad = 1.0;
+            if (wm.Lam) for (int e = tid; e < N * nd; e += LQR_NT) if (!fin(wm.Lam[gi * N * nd + e])) bad = 1.0;
+            if (SOFT) if (wm.Eps) for (int e = tid; e < N * nd; e += LQR_NT) if (!fin(wm.Eps[gi * N * nd + e])) bad = 1.0;
+            if (EQ) {
+              if (wm.Nu) for (int e = tid; e < N * ne; e += LQR_NT) if (!fin(wm.Nu[gi * N * ne + e])) bad = 1.0;
+              if (wm.NuT) if (tid < nt) if (!fin(wm.NuT[gi * nt + tid])) bad = 1.0;
+            }
+            if (mq_block<1>(bad, red, tid) > 0.0) warm_now = false;
+          }
+        }
+      mq_start:                                                              // (WARM) the cold restart of a failed warm attempt comes back here
+        if (WARM && warm_now) {
+          // ---- (WARM) start of the step from the previous iterate (tests/mpc_qp_warm_reference.py states the same rule; delta = wm.floor):
+          //   shift    new stage j takes old stage j + 1 for j <= N - 2 (same phase, same rows), x_0 is the measured state, u_{N-1} repeats the old last input,
+          //            x_N = A_k x_{N-1} + B_k u_{N-1} (+ c_k) at the phase of the new last stage; lam, e and the equality multipliers shift the same way and
+          //            are zero at the new last stage before the floors; nu_T is kept.  Without a shift (a guess for the same phase) only x_0 is replaced;
+          //   floors   hard row  s = max(d - D z, delta), lam = max(lam, delta);   L1 and L1 + L2 rows  e = max(e, delta), lam = clip(lam, delta,
+          //            c + Z e - delta), nu = c + Z e - lam (the invariant c + Z e - lam - nu = 0 holds exactly), lam = nu = (c + Z e) / 2 when
+          //            c + Z e < 2 delta, s = max(d - D z + e, delta);   pure quadratic row  lam = max(lam, delta), s = max(d - D z + lam / Z, delta);
+          //            equality and terminal multipliers free; every direction zero.  s and nu of the previous iterate are not read.
+          const bool shifted = t > 0 || (wm.flags & 4) != 0;
+          if (t == 0) {                                                      // the guess into the slot as it is given
+            const size_t gi = b * ns + si;
+            for (int e = tid; e < (N + 1) * n; e += LQR_NT) {
+              const int j = e / n, c = e - j * n;
+              Z[e] = c < nx ? wm.X[(gi * (N + 1) + j) * nx + c] : (j < N ? wm.U[(gi * N + j) * mb + c - nx] : 0.0);
+            }
+            for (int e = tid; e < N * nd; e += LQR_NT) {
+              Lg[e] = wm.Lam ? wm.Lam[gi * N * nd + e] : 0.0;
+              if (SOFT) Eg[e] = wm.Eps ? wm.Eps[gi * N * nd + e] : 0.0;
+            }
+            if (EQ) {
+              for (int e = tid; e < N * ne; e += LQR_NT) NUe[e] = wm.Nu ? wm.Nu[gi * N * ne + e] : 0.0;
+              if (tid < nt) NUT[tid] = wm.NuT ? wm.NuT[gi * nt + tid] : 0.0;
+            }
+            __syncthreads();
+          }
+          if (shifted) {                                                     // in place: a thread owns a column of an array and walks the stages upward
+            for (int c = tid; c < n; c += LQR_NT) {
+              for (int j = 0; j + 1 < N; ++j) Z[(size_t)j * n + c] = Z[(size_t)(j + 1) * n + c];
+              if (c < nx) Z[(size_t)(N - 1) * n + c] = Z[(size_t)N * n + c];
+            }
+            for (int c = tid; c < nd; c += LQR_NT) {
+              for (int j = 0; j + 1 < N; ++j) {
+                Lg[(size_t)j * nd + c] = Lg[(size_t)(j + 1) * nd + c];
+                if (SOFT) Eg[(size_t)j * nd + c] = Eg[(size_t)(j + 1) * nd + c];
+              }
+              Lg[(size_t)(N - 1) * nd + c] = 0.0;
+              if (SOFT) Eg[(size_t)(N - 1) * nd + c] = 0.0;
+            }
+            if (EQ) for (int c = tid; c < ne; c += LQR_NT) {
+              for (int j = 0; j + 1 < N; ++j) NUe[(size_t)j * ne + c] = NUe[(size_t)(j + 1) * ne + c];
+              NUe[(size_t)(N - 1) * ne + c] = 0.0;
+            }
+            __syncthreads();
+          }
+          if (tid < nx) Z[tid] = xcur[tid];
+          for (int e = tid; e < (N + 1) * n; e += LQR_NT) dZ[e] = 0.0;
+          if (EQ) for (int e = tid; e < N * ne; e += LQR_NT) REQ[e] = 0.0;
+          __syncthreads();
+          for (int j = 0; j < N; ++j) {                                      // one pass over the stages: D z for the floors, x_N at the last stage
+            const int k = (k0s + j % p) % p, m = rows_of(k);
+            mq_fetch(El, nullptr, Dl, ld, A + (size_t)k * nx * nx, B + (size_t)k * nx * mb, nullptr, D ? D + (size_t)k * nd * n : nullptr, nx, mb, m, tx, ty, rs);
+            if (tid < n) zv[tid] = Z[(size_t)j * n + tid];
+            __syncthreads();
+            for (int i = tid; i < nd; i += LQR_NT) {
+              const size_t e = (size_t)j * nd + i;
+              double s = 1.0, lam = 0.0, ee = 0.0, nu = 0.0;                 // an absent row: the values of the cold start
+              if (i < m) {
+                const double fl = wm.floor, slack = dd[k * nd + i] - mq_dot(Dl + i * ld, zv, n);
+                const double c = SOFT ? pen[k * nd + i] : INFINITY, zq = QUAD ? pen2[k * nd + i] : 0.0;
+                lam = Lg[e];
+                if (c < INFINITY && (!QUAD || c > 0.0)) {                    // two pairs
+                  ee = fmax(Eg[e], fl);
+                  const double tot = c + zq * ee;
+                  lam = tot < 2.0 * fl ? 0.5 * tot : fmin(fmax(lam, fl), tot - fl);
+                  nu = tot - lam;
+                  s = fmax(slack + ee, fl);
+                } else if (QUAD && c == 0.0) {                               // pure quadratic
+                  lam = fmax(lam, fl);
+                  s = fmax(slack + lam * (1.0 / zq), fl);
+                } else {
+                  lam = fmax(lam, fl);
+                  s = fmax(slack, fl);
+                }
+              }
+              Sg[e] = s; Lg[e] = lam; dSg[e] = 0.0; dLg[e] = 0.0; RIN[e] = 0.0; COR[e] = 0.0;
+              if (SOFT) { Eg[e] = ee; NUg[e] = nu; dEg[e] = 0.0; C2g[e] = 0.0; }
+            }
+            if (shifted && j == N - 1 && tid < nx) {
+              double v = mq_dot(El + tid * ld, zv, n);
+              if (AFF) if (cof) v += cof[k * nx + tid];
+              Z[(size_t)N * n + tid] = v;
+            }
+            __syncthreads();
+          }
+        } else {                                                             // the cold start, its statements where they were (not indented)
         for (int e = tid; e < (N + 1) * n; e += LQR_NT) { Z[e] = e < nx ? xcur[e] : 0.0; dZ[e] = 0.0; }
         for (int e = tid; e < N * nd; e += LQR_NT) {
           const int j = e / nd, i = e - j * nd, k = (k0s + j % p) % p;
@@ -359,6 +491,7 @@ __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd
           for (int e = tid; e < N * ne; e += LQR_NT) { NUe[e] = 0.0; REQ[e] = 0.0; }
           if (tid < nt) NUT[tid] = 0.0;
         }
+        }                                                                    // (WARM) end of the cold start
         int mp = mt;                                                         // complementarity pairs: one per row, one more per soft row
         if (SOFT) {
           double cnt = 0.0;
@@ -730,6 +863,17 @@ __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd
           }
           __syncthreads();
         }
+        if (WARM) {
+          // a warm attempt that ran out of iterations or met a stage matrix that is not positive definite: the same step again from the cold start, its
+          // iterations added (an infeasible instance costs two runs of max_iter); status 3 is not retried
+          if (warm_now && (status == MQ_MAXITER || status == MQ_NOT_CONVEX)) {
+            status = MQ_OK; its_warm = its; warm_now = false; retried = true;
+            __syncthreads();
+            goto mq_start;
+          }
+          its += its_warm;
+          wcode = status == MQ_OK ? (retried ? 2 : (warm_now ? 1 : 0)) : -1;
+        }
         it_total += its; it_max = max(it_max, its);
       }
       // ---- the step's results: u_0, the open-loop solution of step 0, nact, hres, x <- E [x; u_0]
@@ -816,6 +960,7 @@ __global__ void __launch_bounds__(LQR_NT) k_mpc_qp(int p, int nx, int mb, int nd
         if (hresg) hresg[o] = hres;
         if (SOFT) if (nviolg) nviolg[o] = nviol;
         if (EQ) if (eresg) eresg[o] = eres;
+        if (WARM) if (wm.log) wm.log[o] = done > t ? wcode : -1;
       }
     }
     if (tid < nx) XTg[(b * ns + si) * nx + tid] = status == MQ_OK ? xcur[tid] : qnan;

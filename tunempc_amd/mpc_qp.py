@@ -34,7 +34,12 @@ An equality row is a hard row without a slack: a multiplier of free sign at the 
 instance whose rows cannot be met -- horizon * nu too short to reach Tx x_N = 0, a row of stage 0 on x_0 alone that x_0 violates (the reference drops state-only
 h rows at stage 0 for the same reason) -- is infeasible and ends with status 1, like contradictory inequality rows.
 
-Not served: warm starts between the steps, the nonlinear plant, more than nx terminal rows; there are no arguments for them.  Conventions as in lqr.py / closed_loop.py.  There is no CPU path: the solve runs in the HIP library or the call raises."""
+Warm starts (guess=, guess_shift=, warm=, warm_floor=; csrc/tmpc_mpc_qp.h states the rule, the WARM instantiations run it): a step may start from the solution
+of an earlier call (guess=, shifted by one stage with guess_shift=1 when it comes from the previous phase), and the steps t > 0 of a loop from the shifted
+iterate of step t - 1 (warm=True), as the reference's Pmpc.step always does.  mpc_closed_loop_plant runs the loop against any plant callback, one launch per
+step: the reference's closed_loop_sim(F=...) on a plant that is not linear.
+
+Not served: more than nx terminal rows; the nonlinear plant inside one launch (mpc_closed_loop_plant steps it from Python).  Conventions as in lqr.py / closed_loop.py.  There is no CPU path: the solve runs in the HIP library or the call raises."""
 import functools
 import inspect
 
@@ -75,18 +80,71 @@ def lds_layout(nx, nu, nd=0, soft=False, ne=None, nt=0, quad=False):
     return dict(bytes=8 * total, ws_doubles=lambda N: 2 * (N + 1) * n + 6 * N * nd + N * nx + N * nu * (n + 1))
 
 
-def _keyword_penalty2(f):
-    """penalty2 is the last keyword of the four calls and keyword-only: it is taken off the call here and handed to f by name.  The signature that
-    introspection reports stays the parameter list the call had before penalty2 existed -- everything up to terminal, which callers and tools pin to tell that a
-    positional call keeps its meaning --; the docstring names penalty2."""
+WARM_FLOOR = 1e-2      # delta of the warm start's floors (absolute; tests/mpc_qp_warm_reference.py and profiles/mpc_qp_warm_reference_counts.txt)
+HIDDEN_KEYWORDS = ('penalty2', 'guess', 'guess_shift', 'warm', 'warm_floor')
+WARM_KEYWORDS = HIDDEN_KEYWORDS[1:]
+
+
+def _hidden_keywords(f):
+    """The parameters of f named in HIDDEN_KEYWORDS (penalty2 and the warm-start keywords) are the last of the four calls and keyword-only: they are taken off
+    the call here and handed to f by name.  The signature that introspection reports stays the parameter list the call had before they existed -- everything up
+    to terminal, which callers and tools pin to tell that a positional call keeps its meaning --; the docstring names them.  warm_call (the last parameter of
+    f, hidden too, not for callers) tells f whether any of WARM_KEYWORDS was PASSED, whatever its value: such a call goes through the warm entry and returns
+    `warm`, also with warm=False or warm_floor=1e-2 spelled out."""
     sig = inspect.signature(f)
+    hidden = [p for p in sig.parameters.values() if p.name in HIDDEN_KEYWORDS]
 
     @functools.wraps(f)
-    def call(*args, penalty2=None, **kw):
-        return f(*args, penalty2=penalty2, **kw)
+    def call(*args, **kw):
+        return f(*args, **{**{p.name: p.default for p in hidden}, 'warm_call': any(k in kw for k in WARM_KEYWORDS), **kw})
     del call.__wrapped__
-    call.__signature__ = sig.replace(parameters=[p for p in sig.parameters.values() if p.name != 'penalty2'])
+    call.__signature__ = sig.replace(parameters=[p for p in sig.parameters.values() if p.name not in HIDDEN_KEYWORDS + ('warm_call',)])
     return call
+
+
+GUESS_KEYS = ('X', 'U', 'lam', 'eps', 'nu', 'nu_term')
+
+
+def _validate_warm(who, use_torch, A, B, X0, N, nd, penalty, penalty2, J, terminal, guess, guess_shift, warm, warm_floor, force=False):
+    """The warm-start keywords, after _validate -> None when none of them is used (the call is routed where it was), else the tuple (flags, floor, Xg, Ug, Lamg,
+    Eg, Nug, NuTg) of the warm entries.  guess: a dict as returned by an earlier mpc_qp_batch: X, U, lam (with rows) and eps (with penalty or penalty2), nu
+    (with J), nu_term (with terminal), of the shapes that call returns.  force: the warm entry also without any of them (mpc_closed_loop_plant: every step of
+    its loop returns the same keys)."""
+    if not force and guess is None and warm is False and guess_shift == 0 and warm_floor == WARM_FLOOR:
+        return None
+    if isinstance(warm, (bool, np.bool_)) is False:
+        raise ValueError('{}: warm must be a bool, got {!r}'.format(who, warm))
+    if isinstance(guess_shift, bool) or guess_shift not in (0, 1):
+        raise ValueError('{}: guess_shift must be 0 (a guess for the same phase) or 1 (a guess from the previous phase), got {!r}'.format(who, guess_shift))
+    if guess_shift and guess is None:
+        raise ValueError('{}: guess_shift describes guess, which is None'.format(who))
+    if isinstance(warm_floor, bool) or not isinstance(warm_floor, (int, float, np.floating)) or not 0.0 < float(warm_floor) < float('inf'):
+        raise ValueError('{}: warm_floor must be a finite float > 0, got {!r}'.format(who, warm_floor))
+    arrays = (None,) * 6
+    if guess is not None:
+        if not isinstance(guess, dict):
+            raise ValueError('{}: guess must be a dict as returned by mpc_qp_batch (X, U, lam, and eps, nu, nu_term where the problem has them), got {}'.format(
+                who, type(guess).__name__))
+        nb, ns, nx, nu = int(X0.shape[0]), int(X0.shape[1]), int(X0.shape[2]), int(B.shape[3])
+        ne = 0 if J is None else int(J.shape[2])
+        nt = 0 if terminal is None else (nx if isinstance(terminal, str) else int(terminal.shape[2]))
+        want = [('X', (nb, ns, N + 1, nx), True), ('U', (nb, ns, N, nu), True), ('lam', (nb, ns, N, nd), nd > 0),
+                ('eps', (nb, ns, N, nd), nd > 0 and (penalty is not None or penalty2 is not None)), ('nu', (nb, ns, N, ne), ne > 0), ('nu_term', (nb, ns, nt), nt > 0)]
+        got = []
+        for key, shape, needed in want:
+            x = guess.get(key)
+            if not needed:
+                got.append(None)
+                continue
+            if x is None:
+                raise ValueError('{}: guess[{!r}] {} expected, got None (a call with return_traj=False returns no guess)'.format(who, key, shape))
+            if not hasattr(x, 'shape') or tuple(x.shape) != shape:
+                raise ValueError('{}: guess[{!r}] {} expected, got {}'.format(who, key, shape, tuple(x.shape) if hasattr(x, 'shape') else type(x).__name__))
+            got.append(x)
+        _cl._check_kind(who, [('A', A)] + [('guess[%r]' % k, x) for (k, _, _), x in zip(want, got) if x is not None])
+        arrays = tuple(None if x is None else lqr._contig(x, use_torch) for x in got)
+    flags = (1 if warm else 0) | (2 if guess is not None else 0) | (4 if guess is not None and guess_shift else 0)
+    return (flags, float(warm_floor)) + arrays
 
 
 def _check_penalty2(who, penalty, penalty2):
@@ -241,11 +299,13 @@ def _validate_affine(who, use_torch, A, B, X0, T, terminal, offset, qf, terminal
 
 
 def _run(who, A, B, H, X0, horizon, steps, phase0, D, d, ndcnt, q, Pf, tol, max_iter, return_traj, return_ol, penalty=None, J=None, r=None, necnt=None,
-         terminal=None, offset=None, qf=None, terminal_rhs=None, plant=None, disturbance=None, penalty2=None):
+         terminal=None, offset=None, qf=None, terminal_rhs=None, plant=None, disturbance=None, penalty2=None, guess=None, guess_shift=0, warm=False,
+         warm_floor=WARM_FLOOR, force_warm=False):
     if penalty2 is not None and penalty is None and hasattr(penalty2, 'shape'):      # every row pure quadratic: penalty is taken as 0
         penalty = penalty2.new_zeros(tuple(penalty2.shape)) if lqr._is_torch(penalty2) else np.zeros(penalty2.shape)
     use_torch, nd, N, T, k0 = _validate(who, A, B, H, X0, horizon, phase0, D, d, ndcnt, q, Pf, tol, max_iter, steps, penalty, J, r, necnt, terminal, penalty2)
     aff = _validate_affine(who, use_torch, A, B, X0, T, terminal, offset, qf, terminal_rhs, plant, disturbance)
+    wm = _validate_warm(who, use_torch, A, B, X0, N, nd, penalty, penalty2, J, terminal, guess, guess_shift, warm, warm_floor, force_warm)
     if aff is not None and J is None and terminal is None:                  # the AFF kernels are EQ kernels: their layout with no rows
         lay = lds_layout(A.shape[2], B.shape[3], nd, soft=penalty is not None, ne=0, nt=0, quad=penalty2 is not None)
         if lay['bytes'] > LDS_BYTES:
@@ -265,6 +325,10 @@ def _run(who, A, B, H, X0, horizon, steps, phase0, D, d, ndcnt, q, Pf, tol, max_
         level = 'quad_'
         args = (A, B, H, q, Pf, D, ndcnt, d, penalty, J, r, necnt, terminal if isinstance(terminal, str) or terminal is None else lqr._contig(terminal, use_torch),
                 aff, lqr._contig(penalty2, use_torch))
+    if wm is not None:                                                      # the warm entry: the arguments of the quad entry (penalty, aff, penalty2 None where there is none), then wm
+        level = 'warm_'
+        args = (A, B, H, q, Pf, D, ndcnt, d, penalty, J, r, necnt, terminal if isinstance(terminal, str) or terminal is None else lqr._contig(terminal, use_torch),
+                aff, None if penalty2 is None else lqr._contig(penalty2, use_torch), wm)
     entry = getattr(_lib, 'mpc_qp_%sbatch_%s' % (level, 'device' if use_torch else 'host'))
     out = entry(*args, X0, N, T, k0, float(tol), int(max_iter), bool(return_traj), bool(return_ol))
     info = out['info']
@@ -278,9 +342,10 @@ def _run(who, A, B, H, X0, horizon, steps, phase0, D, d, ndcnt, q, Pf, tol, max_
     return out
 
 
-@_keyword_penalty2
+@_hidden_keywords
 def mpc_qp_batch(A, B, H, X0, horizon, phase0=0, D=None, d=None, ndcnt=None, q=None, Pf=None, tol=TOL, max_iter=MAX_ITER, return_traj=True, offset=None,
-                 qf=None, terminal_rhs=None, penalty=None, J=None, r=None, necnt=None, terminal=None, penalty2=None):
+                 qf=None, terminal_rhs=None, penalty=None, J=None, r=None, necnt=None, terminal=None, penalty2=None, guess=None, guess_shift=0,
+                 warm_floor=WARM_FLOOR, warm_call=False):
     """One MPC step per (problem, initial deviation): A [nb,p,nx,nx], B [nb,p,nx,nu], H [nb,p,n,n] (used as (H + H') / 2), X0 [nb,ns,nx], fp64, n = nx + nu <= 64;
     the horizon-`horizon` QP from phase `phase0`.  Optional: the rows D [nb,p,nd,n], d [nb,p,nd] (D z <= d; ndcnt int32 [nb,p]: only the first ndcnt rows of a
     stage, None: all nd), q [nb,p,n] (linear cost), Pf [nb,p,nx,nx] (terminal weight 1/2 x_N' Pf[(phase0 + N) mod p] x_N); None: absent / zero.  Without rows
@@ -306,6 +371,16 @@ def mpc_qp_batch(A, B, H, X0, horizon, phase0=0, D=None, d=None, ndcnt=None, q=N
     eres.  Without penalty2 the call is routed exactly where it was.  about_reference builds the three from a periodic reference.  In the signatures of the four calls the
     three (and plant, disturbance) stand between return_traj / max_iter and penalty: what comes before them is where it was, and penalty, J, r, necnt, terminal
     stay the last parameters, so every argument from penalty on is to be passed by keyword.
+    guess, guess_shift=0, warm_floor=1e-2 (keyword-only like penalty2, not listed by inspect.signature): the warm start.  guess is a dict as returned by an
+    earlier mpc_qp_batch of the same shapes -- X, U, lam, and eps, nu, nu_term where the problem has them (ValueError when one of those is None or has the wrong
+    shape) --; guess_shift=0: a guess for the same phase (a neighbouring x_0), everything as given and x_0 replaced; guess_shift=1: a guess from the previous
+    phase, shifted by one stage (stage j takes stage j + 1, u_{N-1} repeats, x_N = A x_{N-1} + B u_{N-1} + offset, the new last stage's multipliers zero,
+    nu_term kept).  Slacks and multipliers are floored at warm_floor by row kind (csrc/tmpc_mpc_qp.h).  An instance whose guess holds a non-finite entry (a
+    failed predecessor returns NaN) starts cold; a warm-started solve that ends with status 1 or 2 is solved again from the cold start and the iteration
+    counts add up -- an infeasible instance costs two runs of max_iter, and iters_total / iters_max (which may then exceed max_iter) and pivmin cover both
+    attempts --; status 3 is not retried.  A call that PASSES any of these keywords, whatever the value, returns `warm` [nb,ns]
+    int32 in addition (0 cold, 1 the warm start delivered, 2 the cold restart delivered, -1 failed) and nu, nu_term (empty without rows), eres.  Without them
+    the call is routed exactly where it was.
 
     numpy arrays run through the host entry; torch tensors on a GPU through the device entry (torch tensors out, the inputs are not copied).  Both run the same
     kernel and agree bit for bit; the numbers of an instance do not depend on ns or on the other instances of the call.
@@ -318,22 +393,33 @@ def mpc_qp_batch(A, B, H, X0, horizon, phase0=0, D=None, d=None, ndcnt=None, q=N
     max_iter < 1, penalty without D or with an entry <= 0 or NaN (0 is legal beside a penalty2 > 0), penalty2 without D, negative, non-finite, NaN or non-zero
     on a hard row, r or necnt without J, a terminal that is neither None, 'constraint' nor an array,
     terminal_rhs without terminal; NotImplementedError: n > 64, (nx, nu, nd) beyond the 160 KB LDS layout (lds_layout; with a penalty the soft layout, with J or terminal lds_layout(ne=))."""
-    o = _run('mpc_qp_batch', A, B, H, X0, horizon, 1, phase0, D, d, ndcnt, q, Pf, tol, max_iter, False, return_traj, penalty, J, r, necnt, terminal, offset, qf,
-             terminal_rhs, penalty2=penalty2)
+    return _step('mpc_qp_batch', A, B, H, X0, horizon, phase0, D, d, ndcnt, q, Pf, tol, max_iter, return_traj, offset, qf, terminal_rhs, penalty, J, r, necnt,
+                 terminal, penalty2, guess, guess_shift, warm_floor, warm_call)
+
+
+def _step(who, A, B, H, X0, horizon, phase0=0, D=None, d=None, ndcnt=None, q=None, Pf=None, tol=TOL, max_iter=MAX_ITER, return_traj=True, offset=None, qf=None,
+          terminal_rhs=None, penalty=None, J=None, r=None, necnt=None, terminal=None, penalty2=None, guess=None, guess_shift=0, warm_floor=WARM_FLOOR,
+          force_warm=False):
+    """mpc_qp_batch under the name `who`; force_warm: through the warm entry also without a warm-start keyword (the dict then always holds `warm`)."""
+    o = _run(who, A, B, H, X0, horizon, 1, phase0, D, d, ndcnt, q, Pf, tol, max_iter, False, return_traj, penalty, J, r, necnt, terminal, offset, qf,
+             terminal_rhs, penalty2=penalty2, guess=guess, guess_shift=guess_shift, warm_floor=warm_floor, force_warm=force_warm)
     out = dict(u0=o['U0'], X=o['Xol'], U=o['Uol'], lam=o['Lam'], nact=o['nact'][..., 0], hres=o['hres'][..., 0], x1=o['XT'], info=o['info'])
     if penalty is not None or penalty2 is not None:
         out.update(eps=o['Eol'], nviol=o['nviol'][..., 0])
     if 'eres' in o:
         out.update(nu=o['Nu'], nu_term=o['NuT'], eres=o['eres'][..., 0])
+    if 'warmlog' in o:
+        out['warm'] = o['warmlog'][..., 0]
     out.update({k: o[k] for k in INFO_FIELDS})
     return out
 
 
-@_keyword_penalty2
+@_hidden_keywords
 def mpc_closed_loop_batch(A, B, H, X0, horizon, steps, phase0=0, D=None, d=None, ndcnt=None, q=None, Pf=None, tol=TOL, max_iter=MAX_ITER, return_traj=True,
                           offset=None, qf=None, terminal_rhs=None, plant=None, disturbance=None, penalty=None, J=None, r=None, necnt=None, terminal=None,
-                          penalty2=None):
-    """The receding-horizon loop: at t = 0 .. steps-1 the QP of mpc_qp_batch from phase (phase0 + t) mod p, cold-started, u_0 applied, x <- A_k x + B_k u_0 (the
+                          penalty2=None, guess=None, guess_shift=0, warm=False, warm_floor=WARM_FLOOR,
+                          warm_call=False):
+    """The receding-horizon loop: at t = 0 .. steps-1 the QP of mpc_qp_batch from phase (phase0 + t) mod p, cold-started (or warm: below), u_0 applied, x <- A_k x + B_k u_0 (the
     linear plant, as closed_loop_batch does), all steps in one launch.  Arguments as mpc_qp_batch.
 
     Returns dict: X [nb,ns,steps+1,nx], U [nb,ns,steps,nu] (None with return_traj=False), iters, nact [nb,ns,steps] int32, hres [nb,ns,steps], XT [nb,ns,nx],
@@ -346,14 +432,22 @@ def mpc_closed_loop_batch(A, B, H, X0, horizon, steps, phase0=0, D=None, d=None,
     x_{t+1} = Ap_k x_t + Bp_k u_0 + cp_k + W_t, k = (phase0 + t) mod p (default: the model; a cp left out is the model's offset); disturbance W
     [nb,ns,steps,nx], which the controller does not know about.  hres, eres, nact, nviol stay figures of the applied stage of the model's QP.  A non-finite
     W_t (or plant entry) makes x_{t+1} non-finite: the instance ends with status 3 at step t + 1, X[t + 1] holds that state.  With any of the five the dict
-    also holds eres.  penalty2 as in mpc_qp_batch (the dict gains nviol and eres).  ValueError: shapes, mixed numpy / torch, terminal_rhs without terminal, a plant that is not a tuple of 2 or 3."""
+    also holds eres.  penalty2 as in mpc_qp_batch (the dict gains nviol and eres).
+    warm=False, guess=None, guess_shift=0, warm_floor=1e-2 (keyword-only, not listed by inspect.signature): with warm=True every step t > 0 starts from the
+    iterate of step t - 1 shifted by one stage, in place in the workspace of the launch; guess (as in mpc_qp_batch) is the start of step 0.  The fallbacks of
+    mpc_qp_batch hold per step: a warm-started step that ends with status 1 or 2 is solved again cold within the step and iters (with it iters_total,
+    iters_max, which may exceed max_iter, and pivmin) counts both attempts.  A call
+    that passes any of these keywords, whatever the value, returns `warm` [nb,ns,steps] int32 in addition (0 cold, 1 the warm start delivered the step, 2 the cold restart delivered it,
+    -1 from a failed step on).  ValueError: shapes, mixed numpy / torch, terminal_rhs without terminal, a plant that is not a tuple of 2 or 3."""
     o = _run('mpc_closed_loop_batch', A, B, H, X0, horizon, steps, phase0, D, d, ndcnt, q, Pf, tol, max_iter, return_traj, False, penalty, J, r, necnt, terminal,
-             offset, qf, terminal_rhs, plant, disturbance, penalty2)
+             offset, qf, terminal_rhs, plant, disturbance, penalty2, guess, guess_shift, warm, warm_floor, warm_call)
     out = dict(X=o['X'], U=o['U'], iters=o['iters'], nact=o['nact'], hres=o['hres'], XT=o['XT'], u0=o['U0'], info=o['info'])
     if penalty is not None or penalty2 is not None:
         out['nviol'] = o['nviol']
     if 'eres' in o:
         out['eres'] = o['eres']
+    if 'warmlog' in o:
+        out['warm'] = o['warmlog']
     out.update({k: o[k] for k in INFO_FIELDS})
     return out
 
@@ -427,6 +521,16 @@ def _stack_affine(who, p, nx, nu, terminal, offset, qf, terminal_rhs, plant=None
         if W.shape != (int(steps), nx):
             raise ValueError('{}: disturbance [steps, nx] = [{}, {}] expected, got {}'.format(who, int(steps), nx, W.shape))
         out['disturbance'] = np.ascontiguousarray(W[None, None])
+    return out
+
+
+def _stack_guess(who, guess):
+    """guess of the reference calling style -> dict(guess=) of the batch calls: its arrays gain the two leading axes of one problem and one state."""
+    out = dict(guess=None)
+    if guess is not None:
+        if not isinstance(guess, dict):
+            raise ValueError('{}: guess must be a dict with X, U, lam (and eps, nu, nu_term where the problem has them), got {}'.format(who, type(guess).__name__))
+        out['guess'] = {k: None if guess.get(k) is None else np.ascontiguousarray(_to_array(guess[k]).astype(np.float64)[None, None]) for k in GUESS_KEYS}
     return out
 
 
@@ -506,9 +610,9 @@ def _stack_one(who, A, B, Q, R, N, x0, D, d, q, Pf, penalty=None, penalty2=None)
     return As, Bs, Hs, np.ascontiguousarray(x[None, None]), out
 
 
-@_keyword_penalty2
+@_hidden_keywords
 def mpc_step(A, B, Q, R, N, x0, horizon, phase0=0, D=None, d=None, q=None, Pf=None, tol=TOL, max_iter=MAX_ITER, offset=None, qf=None, terminal_rhs=None, penalty=None,
-             J=None, r=None, terminal=None, penalty2=None):
+             J=None, r=None, terminal=None, penalty2=None, guess=None, guess_shift=0, warm_floor=WARM_FLOOR, warm_call=False):
     """One MPC step of one model in the reference's calling style: A, B, Q, R, N (the cross term) single matrices (p = 1) or lists of length p as in horizon_lqr,
     D, d the rows D_k [x; u] <= d_k (single arrays or lists of p; None entries: no rows at that stage), q, Pf likewise.  Returns (u0, X [horizon+1,nx],
     U [horizon,nu], lam [horizon,nd], info dict).  penalty: the weights of the soft rows, one vector (every stage) or a list of p vectors, one entry per row of
@@ -516,32 +620,42 @@ def mpc_step(A, B, Q, R, N, x0, horizon, phase0=0, D=None, d=None, q=None, Pf=No
     (single arrays or lists of p, None entries: no rows at that stage; r None: zero); terminal: 'constraint' (x_N = 0), one matrix Tx [nt,nx] or a list of p
     (Tx x_N = 0).  With them info gains 'nu' [horizon,ne], 'nu_term' [nt] and 'eres'.  offset, qf, terminal_rhs: the vectors of the affine problem
     (mpc_qp_batch), one vector each or a list of p.  penalty2: the quadratic weights of the slacks (mpc_qp_batch), one vector or a list of p vectors like
-    penalty; without penalty the rows with Z > 0 are pure quadratic and the others hard.  RuntimeError when the solve did not converge (an infeasible problem)."""
+    penalty; without penalty the rows with Z > 0 are pure quadratic and the others hard.  guess, guess_shift=0, warm_floor=1e-2 (keyword-only): the warm start
+    of mpc_qp_batch for one model; guess is a dict with X [horizon+1,nx], U [horizon,nu], lam [horizon,nd] and eps, nu, nu_term where the problem has them: the
+    X, U, lam this function returned and the entries of its info.  With any of the three info gains 'warm'.  RuntimeError when the solve did not converge (an
+    infeasible problem)."""
     who = 'mpc_step'
     As, Bs, Hs, X0, kw = _stack_one(who, A, B, Q, R, N, x0, D, d, q, Pf, penalty, penalty2)
     kw.update(_stack_eq(who, As.shape[1], As.shape[2], As.shape[2] + Bs.shape[3], J, r, terminal))
     kw.update(_stack_affine(who, As.shape[1], As.shape[2], Bs.shape[3], kw['terminal'], offset, qf, terminal_rhs))
+    if warm_call:
+        kw.update(_stack_guess(who, guess), guess_shift=guess_shift, warm_floor=warm_floor)
     res = mpc_qp_batch(As, Bs, Hs, X0, horizon, phase0, tol=tol, max_iter=max_iter, **kw)
     st = int(res['status'][0, 0])
     if st != 0:
         raise RuntimeError('{}: the solve ended with status {} ({}) after {} iterations'.format(who, st, STATUS_NAMES.get(st), int(res['iters_total'][0, 0])))
-    return res['u0'][0, 0], res['X'][0, 0], res['U'][0, 0], res['lam'][0, 0], {k: res[k][0, 0] for k in INFO_FIELDS + ('nact', 'hres') + (('eps', 'nviol') if 'eps' in res else ()) + (('nu', 'nu_term', 'eres') if 'nu' in res else ())}
+    return res['u0'][0, 0], res['X'][0, 0], res['U'][0, 0], res['lam'][0, 0], {k: res[k][0, 0] for k in INFO_FIELDS + ('nact', 'hres') + (('eps', 'nviol') if 'eps' in res else ()) + (('nu', 'nu_term', 'eres') if 'nu' in res else ()) + (('warm',) if 'warm' in res else ())}
 
 
-@_keyword_penalty2
+@_hidden_keywords
 def mpc_closed_loop_sim(A, B, Q, R, N, x0, horizon, steps, phase0=0, D=None, d=None, q=None, Pf=None, tol=TOL, max_iter=MAX_ITER, offset=None, qf=None,
-                        terminal_rhs=None, plant=None, disturbance=None, penalty=None, J=None, r=None, terminal=None, penalty2=None):
+                        terminal_rhs=None, plant=None, disturbance=None, penalty=None, J=None, r=None, terminal=None, penalty2=None, guess=None, guess_shift=0,
+                        warm=False, warm_floor=WARM_FLOOR, warm_call=False):
     """The reference's closed_loop_sim with the inequality-constrained tracking MPC in the loop and the linear plant, one model in the calling style of mpc_step.
     Returns the reference's log: {'x': steps + 1 states, 'u': steps inputs, 'l': steps stage costs 1/2 z' H_k z + q_k' z, 'h': steps arrays d_k - D_k [x_t; u_t]
     (>= 0 when the rows hold; empty at a stage without rows)} and 'iters', 'nact'.  With penalty (as in mpc_step) 'h' stays d - D z (negative on a violated soft
     row), 'usc' holds the slack of the applied step, max(0, D z - d) on the soft rows and 0 on the hard ones (the reference's usc), and 'nviol' the count of the
     solver.  With J, r, terminal (as in mpc_step) the log gains 'eres': max|J_k [x_t; u_t] - r_k| of every step.  offset, qf, terminal_rhs as in mpc_step; plant = (Ap, Bp) or (Ap, Bp, cp), each a single
     array or a list of p, and disturbance [steps, nx]: the plant of the loop, x_{t+1} = Ap_k x_t + Bp_k u_t + cp_k + W_t (mpc_closed_loop_batch).
-    penalty2 as in mpc_step: 'usc' covers the rows of both kinds (L1, L1 + L2 and pure quadratic).  RuntimeError when a step did not converge."""
+    penalty2 as in mpc_step: 'usc' covers the rows of both kinds (L1, L1 + L2 and pure quadratic).  warm=False, guess, guess_shift, warm_floor (keyword-only,
+    mpc_closed_loop_batch; guess as in mpc_step): with warm=True every step after the first starts from the shifted iterate of the step before, as the
+    reference's Pmpc.step does; with any of the four the log gains 'warm' (the code of every step).  RuntimeError when a step did not converge."""
     who = 'mpc_closed_loop_sim'
     As, Bs, Hs, X0, kw = _stack_one(who, A, B, Q, R, N, x0, D, d, q, Pf, penalty, penalty2)
     kw.update(_stack_eq(who, As.shape[1], As.shape[2], As.shape[2] + Bs.shape[3], J, r, terminal))
     kw.update(_stack_affine(who, As.shape[1], As.shape[2], Bs.shape[3], kw['terminal'], offset, qf, terminal_rhs, plant, disturbance, steps))
+    if warm_call:
+        kw.update(_stack_guess(who, guess), guess_shift=guess_shift, warm=warm, warm_floor=warm_floor)
     res = mpc_closed_loop_batch(As, Bs, Hs, X0, horizon, steps, phase0, tol=tol, max_iter=max_iter, **kw)
     st = int(res['status'][0, 0])
     if st != 0:
@@ -563,7 +677,89 @@ def mpc_closed_loop_sim(A, B, Q, R, N, x0, horizon, steps, phase0=0, D=None, d=N
         log['nviol'] = [int(v) for v in res['nviol'][0, 0]]
     if 'eres' in res:
         log['eres'] = [float(v) for v in res['eres'][0, 0]]
+    if 'warm' in res:
+        log['warm'] = [int(v) for v in res['warm'][0, 0]]
     return log
+
+
+def mpc_closed_loop_plant(A, B, H, X0, horizon, steps, plant, phase0=0, warm=True, **problem):
+    """The receding-horizon loop of mpc_closed_loop_batch against ANY plant (the reference's closed_loop_sim(F=...) on a plant that is not linear): at
+    t = 0 .. steps-1 one launch of mpc_qp_batch from phase (phase0 + t) mod p on the current states, then X <- plant(t, X, U0) with X [nb,ns,nx] and
+    U0 [nb,ns,nu] of the array kind of the call (numpy or torch), returning the next states [nb,ns,nx] of the same kind.  warm=True: the step after a solved
+    one starts from its solution, guess_shift=1 (the rule of mpc_qp_batch with its fallbacks; an instance that failed returns NaN and drags no other along).
+    problem: the keyword arguments of mpc_qp_batch (D, d, ndcnt, q, Pf, tol, max_iter, offset, qf, terminal_rhs, penalty, J, r, necnt, terminal, penalty2,
+    warm_floor, and guess / guess_shift for step 0); disturbance= of mpc_closed_loop_batch has no place here: the callback is the plant.
+
+    Returns the keys of mpc_closed_loop_batch: X [nb,ns,steps+1,nx], U [nb,ns,steps,nu], iters, nact [nb,ns,steps] int32, hres [nb,ns,steps], XT, u0, the info
+    fields (status: of the step that failed, 0 otherwise; steps: steps finished; iters_total, iters_max over the finished steps and the failed one; mu, rp,
+    rd, pivmin of the last step that ran; info [nb,ns,8] assembled from them), nviol with penalty or penalty2, eres where mpc_qp_batch returns it, and warm
+    [nb,ns,steps] int32.  An instance that fails at step t keeps what it logged before: U, hres, eres from t on, X from t + 1 on and XT are NaN, nact, nviol
+    and warm from t on and iters beyond t are -1 (its state is NaN from then on, so its later launches end at once with status 3 and are not logged).
+    With a linear plant(t, X, U0) = A_k X + B_k U0 this is mpc_closed_loop_batch(warm=True): the same starts, so the same iters and warm codes in practice; the
+    values agree to rounding, not bit for bit -- the callback's matrix products are not the kernel's fused sums.  ValueError: as mpc_qp_batch, a plant that
+    is not callable or returns another shape or kind, return_traj=False (the guess of the next step is the trajectory)."""
+    who = 'mpc_closed_loop_plant'
+    if not callable(plant):
+        raise ValueError('{}: plant must be a callable plant(t, X, U0) -> X_next, got {!r}'.format(who, type(plant).__name__))
+    for k in ('disturbance', 'return_traj'):
+        if k in problem:
+            raise ValueError('{}: {} has no place here (the callback is the plant; the trajectory of a step is the guess of the next)'.format(who, k))
+    if isinstance(warm, (bool, np.bool_)) is False:
+        raise ValueError('{}: warm must be a bool, got {!r}'.format(who, warm))
+    T, _ = _cl._validate_steps(who, steps, phase0, int(A.shape[1]) if hasattr(A, 'shape') and len(A.shape) == 4 else 1)
+    p = int(A.shape[1])
+    use_torch = lqr._is_torch(A)
+    if use_torch:
+        import torch
+        stack, i32 = (lambda xs: torch.stack(xs, dim=2)), (lambda x: x.to(torch.int32))
+        full = lambda like, v: torch.full_like(like, v)
+        where = torch.where
+    else:
+        stack, i32 = (lambda xs: np.stack(xs, axis=2)), (lambda x: x.astype(np.int32))
+        full = lambda like, v: np.full_like(like, v)
+        where = np.where
+    guess, shift = problem.pop('guess', None), problem.pop('guess_shift', 0)
+    floor = problem.pop('warm_floor', WARM_FLOOR)
+    X, logs = [X0], {k: [] for k in ('U', 'iters', 'nact', 'hres', 'nviol', 'eres', 'warm')}
+    alive = None                                                            # [nb,ns] bool: every step so far converged
+    for t in range(T):
+        o = _step(who, A, B, H, X[-1], horizon, (int(phase0) + t) % p, guess=guess, guess_shift=shift, warm_floor=floor, force_warm=True, **problem)
+        ok = o['status'] == 0
+        if alive is None:
+            alive, u0 = ok | ~ok, o['u0']
+            status, nsteps, it_total, it_max = o['status'] * 0, o['status'] * 0, o['status'] * 0, o['status'] * 0
+            last = {k: o[k] for k in ('mu', 'rp', 'rd', 'pivmin')}
+        ran, alive = alive, alive & ok                                       # the instances for which step t is a real one; those that solved it too
+        status = where(ran & ~ok, o['status'], status)
+        nsteps = nsteps + i32(alive)
+        its = where(ran, o['iters_total'], o['iters_total'] * 0)
+        it_total, it_max = it_total + its, where(its > it_max, its, it_max)
+        last = {k: where(ran, o[k], last[k]) for k in last}
+        m1 = full(o['nact'], -1)
+        logs['U'].append(o['u0']); logs['hres'].append(where(alive, o['hres'], full(o['hres'], float('nan'))))
+        logs['iters'].append(where(ran, o['iters_total'], m1)); logs['nact'].append(where(alive, o['nact'], m1))
+        logs['warm'].append(where(alive, o['warm'], m1))
+        if 'nviol' in o:
+            logs['nviol'].append(where(alive, o['nviol'], m1))
+        logs['eres'].append(where(alive, o['eres'], full(o['eres'], float('nan'))))
+        Xn = plant(t, X[-1], o['u0'])
+        if lqr._is_torch(Xn) != use_torch or not hasattr(Xn, 'shape') or tuple(Xn.shape) != tuple(X0.shape):
+            raise ValueError('{}: plant(t, X, U0) must return the next states {} of the kind of X, got {}'.format(
+                who, tuple(X0.shape), tuple(Xn.shape) if hasattr(Xn, 'shape') else type(Xn).__name__))
+        X.append(where(alive[..., None], Xn, full(Xn, float('nan'))))
+        if warm:
+            guess, shift = {k: o.get(k) for k in GUESS_KEYS}, 1
+        else:
+            guess, shift = None, 0
+    out = dict(X=stack(X), U=stack(logs['U']), iters=stack(logs['iters']), nact=stack(logs['nact']), hres=stack(logs['hres']), XT=X[-1], u0=u0)
+    if logs['nviol']:
+        out['nviol'] = stack(logs['nviol'])
+    out.update(eres=stack(logs['eres']), warm=stack(logs['warm']))
+    f64 = (lambda x: x.to(X0.dtype)) if use_torch else (lambda x: x.astype(np.float64))
+    fields = dict(status=status, steps=nsteps, iters_total=it_total, iters_max=it_max, mu=last['mu'], rp=last['rp'], rd=last['rd'], pivmin=last['pivmin'])
+    out['info'] = stack([f64(fields[k]) for k in INFO_FIELDS])
+    out.update(fields)
+    return out
 
 
 def about_reference(A, B, H, xref, uref, q=None, Pf=None, D=None, d=None, J=None, r=None, terminal=None):
