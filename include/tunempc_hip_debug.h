@@ -88,13 +88,32 @@ int tmpc_debug_get_multipliers(tmpc_handle* h, int nb, int nr, double* phi, doub
  *   23 adjV   24 adjE [B,p,3,nx,nx] (adjoint pieces: G = T1 - T2, Psi, PhiH)   25 Z [B,p,dp]   26 prob [B,48] (per-problem scalars: 0 tau, 1 alpha, 2 s0, 3 x0,
  *   4 mu, 5 mu_t, 6 sigma mu, ...: the P_* enum of csrc/tmpc_common.h)   27 trace [B,80,10] (row i-1: iteration i as written by its k_ctrl_c: it, phase, mu, tau,
  *   pinf, dinf, ap, ad, stepn, shifts)
+ *   the direction of the iteration (pass 1: predictor, pass 2: final; a pass overwrites the one before):   28 dP [B,p,nx,nx]   29 dX1   30 dX2   31 dS1   32 dS2 [B,p,n,n]
+ *   33 c1   34 c2 [B,p,n,n] (Mehrotra term sym(dX dS S^-1) of pass 1)   35 L1i   36 L2i   37 LX1i   38 LX2i [B,p,n,n] (inverse Cholesky factors of S_r and X_r, lower
+ *   triangular, written by k_stage_pre)   39 Wm [B,p,4,n,n] (step-length matrices; slot 2r: L_r^-1 dS_r L_r^-T, slot 2r+1: LX_r^-1 dX_r LX_r^-T)   40 eigmin [B,p,4] (their
+ *   smallest eigenvalues, or the bound -1/theta of k_eigmin's pre-test)   41 TU [B,p,dp,2] (T^-1 U of the last factorisation)
  * A code whose array this handle does not have is TMPC_E_ARG. */
 int tmpc_debug_get_array(tmpc_handle* h, int which, uint64_t offset, uint64_t count, double* out);
+/* The integer state, LANE 0 ONLY like tmpc_debug_get_array: `count` ints from `offset` of iprob [B,24] (per problem: 0 phase (0 main, 1 centering, 2 done), 1 iterations,
+ * 5 I_NSHIFT, 9 I_SHIFT0, 12 I_REG, 13 I_CHORD, 19 I_LOWP, ...: the I_* enum of csrc/tmpc_common.h). */
+int tmpc_debug_get_iprob(tmpc_handle* h, uint64_t offset, uint64_t count, int32_t* out);
 
 /* With TMPC_DEBUG_FLAG_STOP_ASSEMBLED: stop at iteration k >= 1 instead of the first (the default, k = 1).  Iterations 1 .. k-1 run exactly as the solver runs them
  * (launch sequence: the flag turns graph replay and the persistent kernel off for the call); iteration k runs k_stage_pre, k_ctrl_a, the assembly and the pass-1
- * right-hand sides (k_stage_rhs, k_gather) and returns, so row k of the trace is not written yet.  Without the flag the value is not read. */
+ * right-hand sides (k_stage_rhs, k_gather) and returns, so row k of the trace is not written yet.  Without the flag the value is not read.
+ * The same as tmpc_debug_set_stop_point(h, k, TMPC_DEBUG_STOP_ASSEMBLED). */
 int tmpc_debug_set_stop_iteration(tmpc_handle* h, int k);
+/* ... and where inside iteration k (tests/test_gpu_step_kernels.py).  Iteration k runs as the solver runs it up to the point, then the call synchronises and returns:
+ *   ASSEMBLED    as above (the system unfactored, pass-1 right-hand sides gathered)
+ *   AFTER_PASS1  after k_ctrl_b: the predictor's solved W3, TU, Z, dP, dX / dS, Wm, eigmin, c1 / c2 and partial sums stand, P_SIGMU / P_CORR0 are written
+ *                (a centering iteration skips pass 1: only k_ctrl_b's back-off test has run)
+ *   BEFORE_STEP  pass 2 complete (final direction, Wm, eigmin), k_ctrl_c not run: the iterate has not moved, row k of the trace is not written
+ *   AFTER_STEP   after k_ctrl_c, k_update and k_ctrl_d: iteration k is complete, row k of the trace is written */
+#define TMPC_DEBUG_STOP_ASSEMBLED 0
+#define TMPC_DEBUG_STOP_AFTER_PASS1 1
+#define TMPC_DEBUG_STOP_BEFORE_STEP 2
+#define TMPC_DEBUG_STOP_AFTER_STEP 3
+int tmpc_debug_set_stop_point(tmpc_handle* h, int k, int point);
 
 /* Smallest eigenvalue of nmat symmetric n x n matrices (Householder tridiagonalisation + Sturm multisection). */
 int tmpc_debug_min_eig(tmpc_handle* h, int nmat, int n, const double* W, double* out);

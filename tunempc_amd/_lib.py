@@ -35,7 +35,7 @@ EXPORTS = [
 DEBUG_EXPORTS = [
     'tmpc_debug_gemm_nt', 'tmpc_debug_block_solve', 'tmpc_debug_cr_schedule', 'tmpc_debug_get_multipliers', 'tmpc_debug_get_array',
     'tmpc_debug_min_eig', 'tmpc_debug_min_eig_lane', 'tmpc_debug_factor_bench', 'tmpc_debug_block_factor',
-    'tmpc_debug_last_trsm_pairs', 'tmpc_debug_set_stop_iteration',
+    'tmpc_debug_last_trsm_pairs', 'tmpc_debug_set_stop_iteration', 'tmpc_debug_set_stop_point', 'tmpc_debug_get_iprob',
 ]
 FLAG_DEBUG_NO_DMA = 32      # tunempc_hip_debug.h: TMPC_DEBUG_FLAG_NO_DMA
 # mode bits of tmpc_debug_block_factor (tunempc_hip_debug.h)
@@ -100,6 +100,10 @@ def load_library():
     lib.tmpc_debug_get_array.argtypes = [vp, C.c_int, C.c_uint64, C.c_uint64, dp]
     lib.tmpc_debug_set_stop_iteration.restype = C.c_int
     lib.tmpc_debug_set_stop_iteration.argtypes = [vp, C.c_int]
+    lib.tmpc_debug_set_stop_point.restype = C.c_int
+    lib.tmpc_debug_set_stop_point.argtypes = [vp, C.c_int, C.c_int]
+    lib.tmpc_debug_get_iprob.restype = C.c_int
+    lib.tmpc_debug_get_iprob.argtypes = [vp, C.c_uint64, C.c_uint64, ip]
     lib.tmpc_convexify_con_batch_device.restype = C.c_int
     lib.tmpc_convexify_con_batch_device.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, C.c_double] + [vp] * 10 + [vp]
     lib.tmpc_convexify_step3_batch_device.restype = C.c_int
@@ -337,6 +341,17 @@ class HipConvexifier:
     def debug_set_stop_iteration(self, k):
         """With flags=8 (TMPC_DEBUG_FLAG_STOP_ASSEMBLED): stop at the assembled system of iteration k (default 1); tunempc_hip_debug.h."""
         _check(self.lib, self.lib.tmpc_debug_set_stop_iteration(self._h, int(k)), 'tmpc_debug_set_stop_iteration')
+
+    def debug_set_stop_point(self, k, point):
+        """With flags=8: stop inside iteration k at point 0 (assembled system), 1 (after pass 1 and k_ctrl_b), 2 (pass 2 complete, before k_ctrl_c) or
+        3 (iteration complete); tunempc_hip_debug.h: TMPC_DEBUG_STOP_*."""
+        _check(self.lib, self.lib.tmpc_debug_set_stop_point(self._h, int(k), int(point)), 'tmpc_debug_set_stop_point')
+
+    def debug_iprob(self, offset, count):
+        """`count` int32 from `offset` of the per-problem integer state of lane 0 (iprob [B,24]: the I_* enum of csrc/tmpc_common.h)."""
+        out = np.empty(int(count), np.int32)
+        _check(self.lib, self.lib.tmpc_debug_get_iprob(self._h, int(offset), int(count), _iptr(out)), 'tmpc_debug_get_iprob')
+        return out
 
     def debug_multipliers(self, nb, nr):
         out = [np.empty((nb, self.p, nr)) for _ in range(4)]

@@ -139,6 +139,7 @@ struct tmpc_handle {
   Opts opt;
   int flags;
   int stop_it;      // TMPC_DEBUG_FLAG_STOP_ASSEMBLED: the iteration whose assembled system the call stops at (tmpc_debug_set_stop_iteration; 1 = the first)
+  int stop_point;   // ... and where inside that iteration (tmpc_debug_set_stop_point: TMPC_DEBUG_STOP_*; 0 = with the assembled system)
   Lane lane[MAXL];
   void* slab;
   size_t slab_bytes;
@@ -871,7 +872,9 @@ static int run_chunk(tmpc_handle* h, Lane* ln, int nb, const double* dA, const d
     if (t3 && nfac > 0 && big) hipLaunchKernelGGL(k_t3_schur<true>, dim3(nfac * dm.p), dim3(256), t3_schur_lds, st, wf, dm);
     else if (t3 && nfac > 0) hipLaunchKernelGGL(k_t3_schur<false>, dim3(nfac * dm.p), dim3(256), t3_schur_lds, st, wf, dm);
     if (t3 && eq && nfac > 0) hipLaunchKernelGGL(k_t3_cross, dim3(nfac * dm.p), dim3(64), 0, st, wf, dm);
-    if ((h->flags & TMPC_DEBUG_FLAG_STOP_ASSEMBLED) && it + 1 >= h->stop_it) {   // debug (tunempc_hip_debug.h; tests/tools/step3_asm_check.py, tests/test_gpu_schur_assembly.py): stop with the assembled, unfactored system of iteration stop_it (default: the first) in the workspace
+    // debug (tunempc_hip_debug.h): this is the iteration the call stops in; stop_point says where (0: right here, with the assembled system)
+    const bool stop_here = (h->flags & TMPC_DEBUG_FLAG_STOP_ASSEMBLED) && it + 1 >= h->stop_it;
+    if (stop_here && h->stop_point == TMPC_DEBUG_STOP_ASSEMBLED) {   // debug (tunempc_hip_debug.h; tests/tools/step3_asm_check.py, tests/test_gpu_schur_assembly.py): stop with the assembled, unfactored system of iteration stop_it (default: the first) in the workspace
       if (big) hipLaunchKernelGGL(kb_stage_rhs, dim3(BP), dim3(256), 0, st, w, dm, 1);
       else TMPC_STAGE_LAUNCH(k_stage_rhs, slots_bytes(RHS_SLOTS), st, w, dm, 1);
       if (t3) hipLaunchKernelGGL(k_t3_rhs, dim3(BP), dim3(64), t3_lds, st, w, dm, 1);
@@ -928,7 +931,17 @@ static int run_chunk(tmpc_handle* h, Lane* ln, int nb, const double* dA, const d
       if (pass == 1) {
         hipLaunchKernelGGL(k_ctrl_b, dim3(active), dim3(64), 0, st, w, dm, reg_max);
         if (prof) HIPCHK(hipEventRecord(ln->ev[4], st));
+        if (stop_here && h->stop_point == TMPC_DEBUG_STOP_AFTER_PASS1) {      // debug: the predictor pass and k_ctrl_b's sigma mu stand in the workspace (tests/test_gpu_step_kernels.py)
+          HIPCHK(hipStreamSynchronize(st));
+          HIPCHK(hipGetLastError());
+          return TMPC_OK;
+        }
       } else {
+        if (stop_here && h->stop_point == TMPC_DEBUG_STOP_BEFORE_STEP) {      // debug: the final direction and its step-length eigenvalues, the iterate not moved yet
+          HIPCHK(hipStreamSynchronize(st));
+          HIPCHK(hipGetLastError());
+          return TMPC_OK;
+        }
         hipLaunchKernelGGL(k_ctrl_c, dim3(active), dim3(64), 0, st, w, dm, reg_max);
       }
     }
@@ -939,6 +952,11 @@ static int run_chunk(tmpc_handle* h, Lane* ln, int nb, const double* dA, const d
     if (dm.flags & DF_LOWP) HIPCHK(hipMemsetAsync(w.active + 4, 0, sizeof(int), st));
     hipLaunchKernelGGL(k_ctrl_d, dim3((nb + 63) / 64), dim3(64), 0, st, w, dm, o);
     if (prof) HIPCHK(hipEventRecord(ln->ev[5], st));
+    if (stop_here) {      // debug: TMPC_DEBUG_STOP_AFTER_STEP (the earlier points have returned): iteration stop_it is complete
+      HIPCHK(hipStreamSynchronize(st));
+      HIPCHK(hipGetLastError());
+      return TMPC_OK;
+    }
     }      // (!gexec)
     if (capturing) {
       hipGraph_t graph = nullptr;
@@ -1160,7 +1178,7 @@ static int create_handle(tmpc_handle** out, int chunk, int p, int nx, int mb, in
   h->opt.fast_exit = 0;
   h->opt.lowp_switch = TMPC_LOWP_SWITCH_DEFAULT;
   h->opt.chord_step = 10.0;       // centering: re-use the factorisation once the iterate moves by < 1/10 in the local norm (profiles/r2z_chord_default.txt: +3.7 %, same answers to 1e-10); tmpc_set_tuning(TMPC_TUNE_CHORD_STEP, 0) disables
-  h->flags = 0; h->stop_it = 1;
+  h->flags = 0; h->stop_it = 1; h->stop_point = 0;
   WS tmp;
   const size_t lane_bytes = carve(tmp, h->dm, nullptr, nullptr);
   h->slab_bytes = lane_bytes * nl;
@@ -1386,6 +1404,20 @@ int tmpc_debug_get_array(tmpc_handle* h, int which, uint64_t offset, uint64_t co
     case 25: src = ws.Z; break;
     case 26: src = ws.prob; break;
     case 27: src = ws.trace; break;
+    case 28: src = ws.dP; break;
+    case 29: src = ws.dX1; break;
+    case 30: src = ws.dX2; break;
+    case 31: src = ws.dS1; break;
+    case 32: src = ws.dS2; break;
+    case 33: src = ws.c1; break;
+    case 34: src = ws.c2; break;
+    case 35: src = ws.L1i; break;
+    case 36: src = ws.L2i; break;
+    case 37: src = ws.LX1i; break;
+    case 38: src = ws.LX2i; break;
+    case 39: src = ws.Wm; break;
+    case 40: src = ws.eigmin; break;
+    case 41: src = ws.TU; break;
     default: return TMPC_E_ARG;
   }
   if (!src) return TMPC_E_ARG;
@@ -1393,9 +1425,19 @@ int tmpc_debug_get_array(tmpc_handle* h, int which, uint64_t offset, uint64_t co
   return TMPC_OK;
 }
 
-int tmpc_debug_set_stop_iteration(tmpc_handle* h, int k) {
-  if (!h || k < 1) return TMPC_E_ARG;
-  h->stop_it = k;
+int tmpc_debug_get_iprob(tmpc_handle* h, uint64_t offset, uint64_t count, int32_t* out) {
+  if (!h || !out || !h->lane[0].ws.iprob) return TMPC_E_ARG;
+  static_assert(sizeof(int) == sizeof(int32_t), "iprob is read back as int32");
+  ON_DEVICE(h);
+  HIPCHK(hipMemcpy(out, h->lane[0].ws.iprob + offset, count * sizeof(int32_t), hipMemcpyDeviceToHost));
+  return TMPC_OK;
+}
+
+int tmpc_debug_set_stop_iteration(tmpc_handle* h, int k) { return tmpc_debug_set_stop_point(h, k, TMPC_DEBUG_STOP_ASSEMBLED); }
+
+int tmpc_debug_set_stop_point(tmpc_handle* h, int k, int point) {
+  if (!h || k < 1 || point < TMPC_DEBUG_STOP_ASSEMBLED || point > TMPC_DEBUG_STOP_AFTER_STEP) return TMPC_E_ARG;
+  h->stop_it = k; h->stop_point = point;
   return TMPC_OK;
 }
 
