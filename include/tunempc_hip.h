@@ -578,6 +578,42 @@ int tmpc_mpc_qp_warm_batch_device(int nb, int p, int nx, int mb, int nd, int N, 
                                   const double* penalty2, int warm_flags, double warm_floor, const double* Xg, const double* Ug, const double* Lamg,
                                   const double* Eg, const double* Nug, const double* NuTg, int32_t* warmlog);
 
+/* The local feedback gain of a SOLVED MPC step (tmpc_mpc_qp_gain.h): at a strictly complementary solution of the QP of tmpc_mpc_qp_*_batch the first input is
+ * locally affine in x_0, u_0(x_0 + dx) = u_0 - K0 dx, and K0 is the first gain of the equality-constrained LQ problem that keeps the active set.  One backward
+ * pass j = N-1 ... 0 over the stages k = (k0 + j) mod p per (problem, instance), the constraint-to-go stage of the horizon entry, so any active set is served
+ * (more active rows than inputs, rows on the state alone, dependent rows) and no row enters at a penalty weight.
+ * Inputs: nb, p, nx, mb, nd, ne, nt, N, ns, k0 and A, B, H, Pf, D, ndcnt, d, penalty, penalty2, J, necnt, Tx as in the MPC QP entries (H and Pf are used as
+ * their symmetric parts; penalty NULL: every row hard; penalty2 NULL: zero); terminal: 0 none, 1 x_N = 0, 2 the rows Tx [nb][p][nt][nx] of phase (k0 + N) mod p
+ * (orthonormalised by the compression of the stage); the solution X [nb][ns][N+1][nx], U [nb][ns][N][mb], Lam [nb][ns][N][nd], Eps [nb][ns][N][nd] (NULL: zero)
+ * as the QP entries return Xol, Uol, Lam, Eol; cls_in int32 [nb][ns][N][nd] or NULL; rank_tol as in the ctg entry.
+ * Class of row (j, i), with g = d_i - D_i z_j (cls_in replaces it; values other than 1, 2 count as 0, as does 2 on a row without penalty2):
+ *     hard row (penalty inf): s = g;  1 if lam > s, else 0.      pure quadratic (penalty 0, Z = penalty2 > 0): s = g + lam / Z;  2 if lam > s, else 0.
+ *     0 < penalty < inf: s = g + e, nu = penalty + Z e - lam;  0 if not lam > s; else, violated (e > nu): 2 if Z > 0, 0 if Z = 0; not violated: 1.
+ *     rows beyond ndcnt, and penalty 0 beside penalty2 0 (no row kind; s = g): 0.      0 free: the row drops out; 1 equality: D_i dz_j = 0; 2 quadratic: the stage Hessian gains Z_i D_i' D_i.
+ * The rows J_k (first necnt_k) and the terminal rows always hold.  q, r, offset, qf and terminal_rhs enter only through the solution.
+ * Outputs per (problem, instance): K0 [nb][ns][mb][nx], Pi0, Hn0 [nb][ns][nx][nx], cnt0 int32 [nb][ns], info [nb][ns][12] with the slots of the horizon entry
+ * (K0, Pi0 projected on Hn0 dx = 0, the directions in which the active set can be kept); optional (NULL: not written, the rest keeps its bits): cls int32
+ * [nb][ns][N][nd]; strict [nb][ns] = min over the complementarity pairs (lam, s) and, on two-pair rows, (e, nu) of |a - b| / max(|a|, |b|) -- near 1: the
+ * active set is unambiguous, near 0: a weakly active row, the derivative is one-sided and the result means nothing --; Kall [nb][ns][N][mb][nx], cntall int32
+ * [nb][ns][N]; dX [nb][ns][N+1][nx][nx], dU [nb][ns][N][mb][nx], the open-loop sensitivities Phi_0 = Pz_0, dU_j = -K_j Phi_j, Phi_{j+1} = (A - B K_j) Phi_j
+ * (together, and with Kall).  An instance whose solution holds a non-finite entry ends with status 3; with status >= 2 K0, Pi0, strict, dX, dU are NaN, Hn0
+ * zero, and the unfinished stages of Kall / cntall / cls hold NaN / -1 / -1.  One instance never affects another, and its numbers do not depend on ns.
+ * The host entry stages through device buffers and runs the same kernel.  Not returned: sensitivities of the multipliers.
+ * TMPC_E_ARG: sizes < 1 (nd, ne, nt < 0), k0 outside 0 .. p-1, terminal not 0 / 1 / 2 or 2 without Tx / with nt < 1, NULL A, B, H, X, U, outputs,
+ * nd > 0 without D, d or Lam, penalty2 without penalty, ne > 0 without J, dX without dU or Kall, rank_tol <= 0, (host entry) ndcnt / necnt out of range.
+ * TMPC_E_UNSUPPORTED (before the device is touched): terminal 2 with nt > nx, nx + mb > TMPC_LQR_NMAX, the layout of the ctg entry with ne + nd rows plus nd + 1 doubles beyond 160 KB,
+ * nb > 65535. */
+int tmpc_mpc_qp_gain_batch_host(int nb, int p, int nx, int mb, int nd, int ne, int nt, int N, int ns, int k0, int terminal, const double* A, const double* B,
+                                const double* H, const double* Pf, const double* D, const int32_t* ndcnt, const double* d, const double* penalty,
+                                const double* penalty2, const double* J, const int32_t* necnt, const double* Tx, const double* X, const double* U,
+                                const double* Lam, const double* Eps, const int32_t* cls_in, double rank_tol, double* K0, double* Pi0, double* Hn0,
+                                int32_t* cnt0, double* info, int32_t* cls, double* strict, double* Kall, int32_t* cntall, double* dX, double* dU);
+int tmpc_mpc_qp_gain_batch_device(int nb, int p, int nx, int mb, int nd, int ne, int nt, int N, int ns, int k0, int terminal, const double* A, const double* B,
+                                  const double* H, const double* Pf, const double* D, const int32_t* ndcnt, const double* d, const double* penalty,
+                                  const double* penalty2, const double* J, const int32_t* necnt, const double* Tx, const double* X, const double* U,
+                                  const double* Lam, const double* Eps, const int32_t* cls_in, double rank_tol, double* K0, double* Pi0, double* Hn0,
+                                  int32_t* cnt0, double* info, int32_t* cls, double* strict, double* Kall, int32_t* cntall, double* dX, double* dU);
+
 /* Accumulated hipEvent timings since the last call (ms) when TMPC_FLAG_PROFILE is set, 16 doubles:
  * out[0] stage_pre+ctrl, [1] schur assembly, [2] block factorisation (all kernels of tmpc_cr.h's factor phase), [3] predictor
  * pass, [4] corrector pass + update, [5] number of factorisation phases (= IPM iterations of the chunks), [6] total ms of the

@@ -28,7 +28,7 @@ EXPORTS = [
     'tmpc_closed_loop_batch_host', 'tmpc_closed_loop_batch_device', 'tmpc_mpc_qp_batch_host', 'tmpc_mpc_qp_batch_device',
     'tmpc_mpc_qp_soft_batch_host', 'tmpc_mpc_qp_soft_batch_device', 'tmpc_mpc_qp_eq_batch_host', 'tmpc_mpc_qp_eq_batch_device',
     'tmpc_mpc_qp_aff_batch_host', 'tmpc_mpc_qp_aff_batch_device', 'tmpc_mpc_qp_quad_batch_host', 'tmpc_mpc_qp_quad_batch_device',
-    'tmpc_mpc_qp_warm_batch_host', 'tmpc_mpc_qp_warm_batch_device',
+    'tmpc_mpc_qp_warm_batch_host', 'tmpc_mpc_qp_warm_batch_device', 'tmpc_mpc_qp_gain_batch_host', 'tmpc_mpc_qp_gain_batch_device',
     'tmpc_last_error', 'tmpc_version',
 ]
 # ... and in include/tunempc_hip_debug.h (unit-test / diagnostic entries)
@@ -180,6 +180,10 @@ def load_library():
     lib.tmpc_mpc_qp_warm_batch_host.argtypes = lib.tmpc_mpc_qp_quad_batch_host.argtypes + [C.c_int, C.c_double] + [dp] * 6 + [ip]
     lib.tmpc_mpc_qp_warm_batch_device.restype = C.c_int
     lib.tmpc_mpc_qp_warm_batch_device.argtypes = lib.tmpc_mpc_qp_quad_batch_device.argtypes + [C.c_int, C.c_double] + [vp] * 7
+    lib.tmpc_mpc_qp_gain_batch_host.restype = C.c_int
+    lib.tmpc_mpc_qp_gain_batch_host.argtypes = [C.c_int] * 11 + [dp] * 5 + [ip] + [dp] * 4 + [ip] + [dp] * 5 + [ip, C.c_double] + [dp] * 3 + [ip, dp, ip, dp, dp, ip, dp, dp]
+    lib.tmpc_mpc_qp_gain_batch_device.restype = C.c_int
+    lib.tmpc_mpc_qp_gain_batch_device.argtypes = [C.c_int] * 11 + [vp] * 17 + [C.c_double] + [vp] * 11
     lib.tmpc_get_profile.restype = C.c_int
     lib.tmpc_get_profile.argtypes = [vp, dp]
     lib.tmpc_get_trace.restype = C.c_int
@@ -1131,3 +1135,44 @@ def mpc_qp_warm_batch_device(A, B, H, q, Pf, D, ndcnt, d, penalty, J, r, necnt, 
     """tmpc_mpc_qp_warm_batch_device on validated, contiguous torch tensors of one GPU -> the dict of mpc_qp_warm_batch_host with torch tensors."""
     return _mpc_qp_call('warm', _DeviceArrays, A, B, H, q, Pf, D, ndcnt, d, X0, N, T, k0, tol, max_iter, return_traj, return_ol, penalty, J, r, necnt, Tx,
                         None if aff is None else tuple(aff), penalty2, tuple(warm))
+
+
+def _mpc_qp_gain_call(kind, A, B, H, Pf, D, ndcnt, d, penalty, penalty2, J, necnt, terminal, Tx, X, U, Lam, Eps, cls_in, N, k0, rank_tol, return_all):
+    """tmpc_mpc_qp_gain_batch_<host or device> on validated, contiguous arrays of `kind` (_HostArrays: numpy, _DeviceArrays: torch tensors of one GPU; fp64,
+    the counts and cls_in int32; an absent or empty array is passed as NULL; terminal 0 none / 1 x_N = 0 / 2 the rows Tx) -> dict K0 [nb,ns,nu,nx], Pi0, Hn0
+    [nb,ns,nx,nx], cnt0 int32 [nb,ns], info [nb,ns,12], cls int32 [nb,ns,N,nd], strict [nb,ns]; with return_all Kall [nb,ns,N,nu,nx], cntall int32 [nb,ns,N],
+    dX [nb,ns,N+1,nx,nx], dU [nb,ns,N,nu,nx]."""
+    lib = load_library()
+    xp = kind(A)
+    name = 'tmpc_mpc_qp_gain_batch_%s' % xp.entry
+    nb, p, nx, mb = B.shape
+    ns, N = X.shape[1], int(N)
+    nd = 0 if D is None else D.shape[2]
+    ne = 0 if J is None else J.shape[2]
+    nt = 0 if Tx is None else Tx.shape[2]
+    K0, Pi0, Hn0, cnt0, info = xp.f64(nb, ns, mb, nx), xp.f64(nb, ns, nx, nx), xp.f64(nb, ns, nx, nx), xp.i32(nb, ns), xp.zeros(nb, ns, LQR_CTG_INFO_STRIDE)
+    cls, strict = xp.i32(nb, ns, N, nd), xp.f64(nb, ns)
+    Kall, cntall, dX, dU = (xp.f64(nb, ns, N, mb, nx), xp.i32(nb, ns, N), xp.f64(nb, ns, N + 1, nx, nx), xp.f64(nb, ns, N, mb, nx)) if return_all else (None,) * 4
+    ptr = xp.ptr
+    rows = lambda a, cap: ptr(a) if cap else None
+    args = [nb, p, nx, mb, nd, ne, nt, N, ns, int(k0), int(terminal), ptr(A), ptr(B), ptr(H), ptr(Pf), rows(D, nd), rows(ndcnt, nd), rows(d, nd), rows(penalty, nd),
+            rows(penalty2, nd), rows(J, ne), rows(necnt, ne), ptr(Tx), ptr(X), ptr(U), rows(Lam, nd), rows(Eps, nd), rows(cls_in, nd), float(rank_tol)]
+    args += [ptr(a) for a in (K0, Pi0, Hn0, cnt0, info, cls, strict, Kall, cntall, dX, dU)]
+    rc = xp.call(getattr(lib, name), args)
+    if rc == -1:      # TMPC_E_ARG: the library's message names the argument
+        raise ValueError(lib.tmpc_last_error().decode())
+    _check_lqr(lib, rc, name)
+    out = dict(K0=K0, Pi0=Pi0, Hn0=Hn0, cnt0=cnt0, info=info, cls=cls, strict=strict)
+    if return_all:
+        out.update(Kall=Kall, cntall=cntall, dX=dX, dU=dU)
+    return out
+
+
+def mpc_qp_gain_batch_host(*args):
+    """tmpc_mpc_qp_gain_batch_host on numpy arrays: _mpc_qp_gain_call."""
+    return _mpc_qp_gain_call(_HostArrays, *args)
+
+
+def mpc_qp_gain_batch_device(*args):
+    """tmpc_mpc_qp_gain_batch_device on torch tensors of one GPU: _mpc_qp_gain_call; the inputs never leave HBM."""
+    return _mpc_qp_gain_call(_DeviceArrays, *args)

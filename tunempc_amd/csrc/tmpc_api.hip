@@ -35,6 +35,7 @@
 #include "tmpc_lqr_horizon.h"
 #include "tmpc_closed_loop.h"
 #include "tmpc_mpc_qp.h"
+#include "tmpc_mpc_qp_gain.h"
 #include "tmpc_dd.h"
 #include "tmpc_big.h"
 
@@ -2133,6 +2134,143 @@ int tmpc_horizon_lqr_batch_host(int nb, int p, int nx, int mb, int nr, int ng, i
   if (Kall) HIPCHK(hipMemcpy(Kall, dKa, cKa * 8, hipMemcpyDeviceToHost));
   if (cntall) HIPCHK(hipMemcpy(cntall, dCa, sp * N * sizeof(int32_t), hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(info, dI, cI * 8, hipMemcpyDeviceToHost));
+  return TMPC_OK;
+}
+
+// The local gain of a solved MPC step (tmpc_mpc_qp_gain.h): one backward pass per (problem, instance) at the active set of the solution, the stage and the LDS
+// layout of the ctg entry with ne + nd rows.  One record, one check, one launch; the host entry stages every array through one device buffer.
+static int mpc_qp_gain_check(const char* who, int nb, const MpcQpGainArgs& a, int ns) {
+  if (nb < 1 || a.p < 1 || a.nx < 1 || a.mb < 1 || a.N < 1 || ns < 1 || a.nd < 0 || a.ne < 0 || a.nt < 0 || !a.A || !a.B || !a.H || !a.X || !a.U || !a.K0 || !a.Pi0 ||
+      !a.Hn0 || !a.cnt0 || !a.info) {
+    snprintf(g_err, sizeof(g_err), "%s: bad argument (nb, p, nx, nu, N, ns >= 1, nd, ne, nt >= 0, non-null A, B, H, X, U, K0, Pi0, Hn0, cnt0, info)", who);
+    return TMPC_E_ARG;
+  }
+  if (a.k0 < 0 || a.k0 >= a.p) {
+    snprintf(g_err, sizeof(g_err), "%s: k0 = %d outside 0 .. p - 1 = %d", who, a.k0, a.p - 1);
+    return TMPC_E_ARG;
+  }
+  if (a.terminal < MQG_TERMINAL_NONE || a.terminal > MQG_TERMINAL_ROWS || (a.terminal == MQG_TERMINAL_ROWS && (!a.Tx || a.nt < 1))) {
+    snprintf(g_err, sizeof(g_err), "%s: bad argument (terminal 0 (none), 1 (x_N = 0) or 2 (rows: non-null Tx, nt >= 1); got terminal = %d, nt = %d)", who, a.terminal, a.nt);
+    return TMPC_E_ARG;
+  }
+  if (a.terminal == MQG_TERMINAL_ROWS && a.nt > a.nx) {
+    snprintf(g_err, sizeof(g_err), "%s: at most nx = %d terminal rows (got nt = %d)", who, a.nx, a.nt);
+    return TMPC_E_UNSUPPORTED;
+  }
+  if (a.nd > 0 && (!a.D || !a.d || !a.Lam)) {
+    snprintf(g_err, sizeof(g_err), "%s: bad argument (non-null D, d, Lam when nd = %d > 0)", who, a.nd);
+    return TMPC_E_ARG;
+  }
+  if (a.pen2 && !a.pen) {
+    snprintf(g_err, sizeof(g_err), "%s: bad argument (penalty2 stands beside penalty, which is NULL)", who);
+    return TMPC_E_ARG;
+  }
+  if (a.ne > 0 && !a.J) {
+    snprintf(g_err, sizeof(g_err), "%s: bad argument (non-null J when ne = %d > 0)", who, a.ne);
+    return TMPC_E_ARG;
+  }
+  if ((a.dX != nullptr) != (a.dU != nullptr) || (a.dX && !a.Kall)) {
+    snprintf(g_err, sizeof(g_err), "%s: bad argument (dX and dU come together and need Kall)", who);
+    return TMPC_E_ARG;
+  }
+  if (!(a.rank_tol > 0.0) || !(a.rank_tol < INFINITY)) {
+    snprintf(g_err, sizeof(g_err), "%s: bad argument (finite rank_tol > 0; got rank_tol = %g)", who, a.rank_tol);
+    return TMPC_E_ARG;
+  }
+  if (a.nx + a.mb > LQR_NMAX) {
+    snprintf(g_err, sizeof(g_err), "%s: the LQR recursions handle stage blocks up to nx + nu = %d (got %d)", who, LQR_NMAX, a.nx + a.mb);
+    return TMPC_E_UNSUPPORTED;
+  }
+  const long long bytes = (long long)mpc_qp_gain_lds_doubles(a.nx, a.mb, a.ne < 4096 ? a.ne : 4096, a.nd < 4096 ? a.nd : 4096) * (long long)sizeof(double);
+  if (bytes > LQR_LDS_BYTES) {
+    snprintf(g_err, sizeof(g_err), "%s: nx = %d, nu = %d with room for %d + %d rows per stage and a constraint-to-go needs %lld bytes of LDS (limit %d)", who,
+             a.nx, a.mb, a.ne, a.nd, bytes, LQR_LDS_BYTES);
+    return TMPC_E_UNSUPPORTED;
+  }
+  if (nb > 65535) {
+    snprintf(g_err, sizeof(g_err), "%s: at most 65535 problems per call (got %d)", who, nb);
+    return TMPC_E_UNSUPPORTED;
+  }
+  return TMPC_OK;
+}
+
+static int mpc_qp_gain_launch(int nb, int ns, MpcQpGainArgs a) {
+  const size_t lds_bytes = (size_t)mpc_qp_gain_lds_doubles(a.nx, a.mb, a.ne, a.nd) * sizeof(double);
+  HIPCHK(hipFuncSetAttribute((const void*)k_mpc_qp_gain, hipFuncAttributeMaxDynamicSharedMemorySize, LQR_LDS_BYTES));      // (the same value from every thread and call)
+  a.lcw = 0;
+  while ((1 << a.lcw) < a.nx + a.mb) ++a.lcw;
+  hipLaunchKernelGGL(k_mpc_qp_gain, dim3(ns, nb), dim3(LQR_NT), lds_bytes, 0, a);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(0));
+  return TMPC_OK;
+}
+
+#define MPC_QP_GAIN_RECORD                                                                                                                                  \
+  MpcQpGainArgs a{};                                                                                                                                        \
+  a.p = p; a.nx = nx; a.mb = mb; a.nd = nd; a.ne = ne; a.nt = nt; a.N = N; a.k0 = k0; a.terminal = terminal; a.A = A; a.B = B; a.H = H; a.Pf = Pf;          \
+  a.D = D; a.d = d; a.pen = penalty; a.pen2 = penalty2; a.J = J; a.Tx = Tx; a.X = X; a.U = U; a.Lam = Lam; a.Eps = Eps; a.ndcnt = (const int*)ndcnt;        \
+  a.necnt = (const int*)necnt; a.cls_in = (const int*)cls_in; a.rank_tol = rank_tol; a.K0 = K0; a.Pi0 = Pi0; a.Hn0 = Hn0; a.cnt0 = (int*)cnt0;              \
+  a.info = info; a.cls = (int*)cls; a.strict = strict; a.Kall = Kall; a.cntall = (int*)cntall; a.dX = dX; a.dU = dU
+
+int tmpc_mpc_qp_gain_batch_device(int nb, int p, int nx, int mb, int nd, int ne, int nt, int N, int ns, int k0, int terminal, const double* A, const double* B,
+                                  const double* H, const double* Pf, const double* D, const int32_t* ndcnt, const double* d, const double* penalty,
+                                  const double* penalty2, const double* J, const int32_t* necnt, const double* Tx, const double* X, const double* U,
+                                  const double* Lam, const double* Eps, const int32_t* cls_in, double rank_tol, double* K0, double* Pi0, double* Hn0,
+                                  int32_t* cnt0, double* info, int32_t* cls, double* strict, double* Kall, int32_t* cntall, double* dX, double* dU) {
+  MPC_QP_GAIN_RECORD;
+  const int rc = mpc_qp_gain_check("tmpc_mpc_qp_gain_batch_device", nb, a, ns);
+  if (rc != TMPC_OK) return rc;
+  return mpc_qp_gain_launch(nb, ns, a);
+}
+
+static thread_local EigScratch g_mpc_qp_gain_scratch;     // device images of the host entry, kept between calls and grown on demand
+
+int tmpc_mpc_qp_gain_batch_host(int nb, int p, int nx, int mb, int nd, int ne, int nt, int N, int ns, int k0, int terminal, const double* A, const double* B,
+                                const double* H, const double* Pf, const double* D, const int32_t* ndcnt, const double* d, const double* penalty,
+                                const double* penalty2, const double* J, const int32_t* necnt, const double* Tx, const double* X, const double* U,
+                                const double* Lam, const double* Eps, const int32_t* cls_in, double rank_tol, double* K0, double* Pi0, double* Hn0,
+                                int32_t* cnt0, double* info, int32_t* cls, double* strict, double* Kall, int32_t* cntall, double* dX, double* dU) {
+  const char* who = "tmpc_mpc_qp_gain_batch_host";
+  MPC_QP_GAIN_RECORD;
+  const int rc = mpc_qp_gain_check(who, nb, a, ns);
+  if (rc != TMPC_OK) return rc;
+  const size_t n = (size_t)nx + mb, st = (size_t)nb * p, si = (size_t)nb * ns;
+  if (ndcnt && nd > 0) for (size_t i = 0; i < st; ++i) if (ndcnt[i] < 0 || ndcnt[i] > nd) {
+    snprintf(g_err, sizeof(g_err), "%s: ndcnt[%zu][%zu] = %d outside 0 .. nd = %d", who, i / p, i % p, (int)ndcnt[i], nd);
+    return TMPC_E_ARG;
+  }
+  if (necnt && ne > 0) for (size_t i = 0; i < st; ++i) if (necnt[i] < 0 || necnt[i] > ne) {
+    snprintf(g_err, sizeof(g_err), "%s: necnt[%zu][%zu] = %d outside 0 .. ne = %d", who, i / p, i % p, (int)necnt[i], ne);
+    return TMPC_E_ARG;
+  }
+  // every array of the record, inputs then outputs, each with its size in bytes rounded up to 8: (host pointer, field of the device record, bytes)
+  struct Slot { const void* host; const void** dev; size_t bytes; bool out; };
+  const size_t i4 = sizeof(int32_t);
+  const Slot slots[] = {
+    {A, (const void**)&a.A, st * nx * nx * 8, false}, {B, (const void**)&a.B, st * nx * mb * 8, false}, {H, (const void**)&a.H, st * n * n * 8, false},
+    {Pf, (const void**)&a.Pf, st * nx * nx * 8, false}, {D, (const void**)&a.D, st * nd * n * 8, false}, {d, (const void**)&a.d, st * nd * 8, false},
+    {penalty, (const void**)&a.pen, st * nd * 8, false}, {penalty2, (const void**)&a.pen2, st * nd * 8, false}, {J, (const void**)&a.J, st * ne * n * 8, false},
+    {Tx, (const void**)&a.Tx, st * nt * nx * 8, false}, {X, (const void**)&a.X, si * (N + 1) * nx * 8, false}, {U, (const void**)&a.U, si * N * mb * 8, false},
+    {Lam, (const void**)&a.Lam, si * N * nd * 8, false}, {Eps, (const void**)&a.Eps, si * N * nd * 8, false}, {ndcnt, (const void**)&a.ndcnt, st * i4, false},
+    {necnt, (const void**)&a.necnt, st * i4, false}, {cls_in, (const void**)&a.cls_in, si * N * nd * i4, false},
+    {K0, (const void**)&a.K0, si * mb * nx * 8, true}, {Pi0, (const void**)&a.Pi0, si * nx * nx * 8, true}, {Hn0, (const void**)&a.Hn0, si * nx * nx * 8, true},
+    {cnt0, (const void**)&a.cnt0, si * i4, true}, {info, (const void**)&a.info, si * LQR_CTG_INFO * 8, true}, {cls, (const void**)&a.cls, si * N * nd * i4, true},
+    {strict, (const void**)&a.strict, si * 8, true}, {Kall, (const void**)&a.Kall, si * N * mb * nx * 8, true}, {cntall, (const void**)&a.cntall, si * N * i4, true},
+    {dX, (const void**)&a.dX, si * (N + 1) * nx * nx * 8, true}, {dU, (const void**)&a.dU, si * N * mb * nx * 8, true}};
+  size_t total = 0;
+  for (const Slot& s : slots) if (s.host && s.bytes) total += (s.bytes + 7) & ~(size_t)7;
+  HIPCHK(g_mpc_qp_gain_scratch.reserve(total + 8));
+  char* base = (char*)g_mpc_qp_gain_scratch.p;
+  size_t off = 0;
+  for (const Slot& s : slots) {
+    if (!s.host || !s.bytes) { *s.dev = nullptr; continue; }
+    *s.dev = base + off;
+    if (!s.out) HIPCHK(hipMemcpy(base + off, s.host, s.bytes, hipMemcpyHostToDevice));
+    off += (s.bytes + 7) & ~(size_t)7;
+  }
+  const int rl = mpc_qp_gain_launch(nb, ns, a);
+  if (rl != TMPC_OK) return rl;
+  for (const Slot& s : slots) if (s.out && s.host && s.bytes) HIPCHK(hipMemcpy((void*)s.host, *s.dev, s.bytes, hipMemcpyDeviceToHost));
   return TMPC_OK;
 }
 

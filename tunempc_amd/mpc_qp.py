@@ -23,6 +23,9 @@ per instance, the whole interior-point loop and all steps of the closed loop in 
     mpc_closed_loop_sim(A, B, Q, R, N, x0, horizon, steps, ...)                    -> the reference's log {'x', 'u', 'l', 'h'} (and 'usc' with penalty=)
     slack_penalty(lam_h, active_set, slack_flag, factor)                           the reference's rule for the weights of the soft rows
     about_reference(A, B, H, xref, uref, ...)                                      a deviation problem and a periodic reference -> the absolute-coordinate kwargs
+    mpc_qp_gain_batch(A, B, H, sol, horizon, phase0=0, ...)                        the law at a solved step: K0 = -du0/dx0 at the active set of sol, strict
+    mpc_step_gain(A, B, Q, R, N, sol, horizon, ...)                                one model in the reference's calling style, beside mpc_step
+    mpc_gain_equivalence_batch(A, B, H, Hc, X0, horizon, P=None, ...)              the certificate: both QPs solved, the gains of H and Hc at one active set
 
 The affine problem (offset=, qf=, terminal_rhs=; in the loop plant=, disturbance=) is the reference's controller in ABSOLUTE coordinates -- its cost
 (w - wref)' H (w - wref) + q' w, its terminal row p_operator(x_N - x_ref) = 0, x0 the plant state --, the model x+ = A x + B u + c of a linearisation that is
@@ -843,3 +846,193 @@ def slack_penalty(lam_h, active_set=None, slack_flag='active', factor=1e3):
         if w > 0.0:
             out[i] = w
     return out
+
+
+# ----------------------------------------------------------------------------- the local gain of a solved step and its certificate
+GAIN_STATUS_NAMES = {0: 'Done', 2: 'SingularS', 3: 'NonFinite', 5: 'NoFeasibleSubspace'}
+CLASS_NAMES = {0: 'free', 1: 'equality', 2: 'quadratic'}
+
+
+def gain_lds_bytes(nx, nu, nd=0, ne=0):
+    """mpc_qp_gain_lds_doubles of csrc/tmpc_mpc_qp_gain.h restated: the layout of the constraint-to-go stage (lqr_ctg_lds) with room for ne + nd rows, then
+    nd + 1 doubles for the classes -> bytes of LDS of a workgroup."""
+    nx, nu, nr = int(nx), int(nu), int(ne) + int(nd)
+    n = nx + nu
+    nbd, ms = min(nu, nr + nx), max(nr + nx, nu)
+    ld, ldp, ldc = (n + nbd) | 1, nx | 1, n | 1
+    total = nx * ld + nx * ldp + max(nx, nu + nbd) * ld + (n + nbd) * ld + 2 * ms * ldc + 2 * nx * ldp + 16
+    return 8 * (total + int(nd) + 1)
+
+
+def mpc_qp_gain_batch(A, B, H, sol, horizon, phase0=0, D=None, d=None, ndcnt=None, Pf=None, penalty=None, penalty2=None, J=None, necnt=None, terminal=None,
+                      active=None, rank_tol=1e-9, return_all=False):
+    """The local feedback gain of SOLVED MPC steps: at a strictly complementary solution the QP of mpc_qp_batch is locally affine in x_0,
+    u_0(x_0 + dx) = u_0 - K0 dx, and K0 is the first gain of the equality-constrained LQ problem that keeps the active set (csrc/tmpc_mpc_qp_gain.h: one
+    backward pass of the constraint-to-go stage of horizon_lqr_batch per instance; no row enters at a penalty weight).
+
+    A, B, H, horizon, phase0, D, d, ndcnt, Pf, penalty, penalty2, J, necnt, terminal as in the mpc_qp_batch call that was solved (q, r, offset, qf,
+    terminal_rhs enter only through the solution and are no arguments).  sol: the dict that call returned -- X [nb,ns,N+1,nx], U [nb,ns,N,nu], lam [nb,ns,N,nd]
+    with rows, eps with penalty or penalty2 --, validated like guess=.  The class of row (j, i) follows the solver's activity rules, with g = d_i - D_i z_j:
+        hard row (penalty inf)                   s = g                                  1 if lam > s, else 0
+        pure quadratic (penalty 0, Z > 0)        s = g + lam / Z                        2 if lam > s, else 0
+        0 < penalty < inf                        s = g + e, nu = penalty + Z e - lam    0 if not lam > s; else violated (e > nu): 2 if Z > 0, 0 if Z = 0; else 1
+        rows beyond ndcnt                                                               0
+    0 free: the row drops out; 1 equality: D_i dz_j = 0; 2 quadratic: the stage Hessian gains Z_i D_i' D_i.  The rows of J and the terminal rows always hold.
+    active: int32 [nb,ns,N,nd] with entries 0, 1, 2 replaces the rule (the gain at any active set; 2 on a row without penalty2 counts as 0).
+
+    numpy arrays run through the host entry, torch tensors on a GPU through the device entry; both run the same kernel and agree bit for bit, and the numbers
+    of an instance do not depend on ns or on the other instances.
+
+    Returns dict: K0 [nb,ns,nu,nx], Pi0 [nb,ns,nx,nx] (projected with Pz_0 = I - Hn0' Hn0: the directions dx with Hn0 dx = 0 are those in which the active set
+    can be kept), Hn0 [nb,ns,nx,nx] (cnt0 orthonormal rows, the rest zero), cnt0 int32 [nb,ns], cls int32 [nb,ns,N,nd], nactive int32 [nb,ns,N] (rows of class
+    1 or 2 per stage), strict [nb,ns] = min over the complementarity pairs (lam, s) and (e, nu) of |a - b| / max(|a|, |b|) -- near 1: the active set is
+    unambiguous; near 0: a weakly active row, the derivative is one-sided and K0 means nothing --, status [nb,ns] (0 done, 2 singular stage system, 3
+    non-finite: also an instance whose sol holds NaN, as a failed solve returns, 5 the active set leaves no direction), feas, info [nb,ns,12] as in
+    horizon_lqr_batch.  status >= 2: K0, Pi0, strict NaN, cls -1 at the stages that were not finished.  return_all=True adds Kall [nb,ns,N,nu,nx], cntall
+    [nb,ns,N], and the open-loop sensitivities dX [nb,ns,N+1,nx,nx], dU [nb,ns,N,nu,nx]: X + dX dx, U + dU dx is the solution at x_0 + dx for dx in the
+    feasible subspace while the active set holds.  Not served: sensitivities of the multipliers, the one-sided derivative on a weakly active row.
+    ValueError: shapes, dtypes, mixed numpy / torch, a sol that is no dict or lacks an array, active outside 0 .. 2; NotImplementedError: n > 64, shapes
+    beyond the 160 KB LDS layout (gain_lds_bytes)."""
+    who = 'mpc_qp_gain_batch'
+    if not isinstance(sol, dict):
+        raise ValueError('{}: sol must be a dict as returned by mpc_qp_batch (X, U, lam, and eps where the problem has it), got {}'.format(who, type(sol).__name__))
+    Xs = sol.get('X')
+    if Xs is None or not hasattr(Xs, 'shape') or len(Xs.shape) != 4:
+        raise ValueError("{}: sol['X'] [nb, ns, horizon + 1, nx] expected, got {} (a call with return_traj=False returns no solution)".format(
+            who, None if Xs is None else tuple(getattr(Xs, 'shape', ()))))
+    if penalty2 is not None and penalty is None and hasattr(penalty2, 'shape'):      # every row pure quadratic: penalty is taken as 0
+        penalty = penalty2.new_zeros(tuple(penalty2.shape)) if lqr._is_torch(penalty2) else np.zeros(penalty2.shape)
+    use_torch, nd, N, _, k0 = _validate(who, A, B, H, Xs[:, :, 0], horizon, phase0, D, d, ndcnt, None, Pf, TOL, MAX_ITER, 1, penalty, J, None, necnt, terminal, penalty2)
+    if isinstance(rank_tol, bool) or not isinstance(rank_tol, (int, float, np.floating)) or not (0.0 < float(rank_tol) < 1.0):
+        raise ValueError('{}: 0 < rank_tol < 1 expected, got {!r}'.format(who, rank_tol))
+    nb, p, nx, nu = (int(v) for v in B.shape)
+    ns = int(Xs.shape[1])
+    ne = 0 if J is None else int(J.shape[2])
+    need = gain_lds_bytes(nx, nu, nd, ne)
+    if need > LDS_BYTES:
+        raise NotImplementedError('{}: nx = {}, nu = {} with room for {} + {} rows per stage and a constraint-to-go needs {} bytes of LDS (limit {})'.format(
+            who, nx, nu, ne, nd, need, LDS_BYTES))
+    want = [('X', (nb, ns, N + 1, nx), True), ('U', (nb, ns, N, nu), True), ('lam', (nb, ns, N, nd), nd > 0),
+            ('eps', (nb, ns, N, nd), nd > 0 and (penalty is not None or penalty2 is not None))]
+    got = []
+    for key, shape, needed in want:
+        x = sol.get(key)
+        if not needed:
+            got.append(None)
+            continue
+        if x is None:
+            raise ValueError('{}: sol[{!r}] {} expected, got None (a call with return_traj=False returns no solution)'.format(who, key, shape))
+        if not hasattr(x, 'shape') or tuple(x.shape) != shape:
+            raise ValueError('{}: sol[{!r}] {} expected, got {}'.format(who, key, shape, tuple(x.shape) if hasattr(x, 'shape') else type(x).__name__))
+        got.append(x)
+    _cl._check_kind(who, [('A', A)] + [('sol[%r]' % k, x) for (k, _, _), x in zip(want, got) if x is not None])
+    X, U, Lam, Eps = (lqr._contig(x, use_torch) for x in got)
+    if active is not None:
+        if nd == 0:
+            raise ValueError('{}: active describes the rows of D, which is None'.format(who))
+        if not hasattr(active, 'shape') or lqr._is_torch(active) != use_torch:
+            raise ValueError('{}: active must be {} like A, B, H'.format(who, 'a torch tensor' if use_torch else 'a numpy array'))
+        if tuple(active.shape) != (nb, ns, N, nd) or 'int32' not in str(active.dtype):
+            raise ValueError('{}: active int32 {} expected, got {} {}'.format(who, (nb, ns, N, nd), active.dtype, tuple(active.shape)))
+        if use_torch and (not active.is_cuda or active.device != A.device):
+            raise ValueError('{}: torch tensors must be tensors of one GPU (active: {})'.format(who, active.device))
+        lo, hi = int(active.min()), int(active.max())
+        if lo < 0 or hi > 2:
+            raise ValueError('{}: active in 0 (free), 1 (equality), 2 (quadratic) expected, got {} .. {}'.format(who, lo, hi))
+        active = active.contiguous() if use_torch else np.ascontiguousarray(active)
+    A, B, H, D, d, Pf, penalty, penalty2, J = (lqr._contig(x, use_torch) for x in (A, B, H, D, d, Pf, penalty, penalty2, J))
+    ndcnt, necnt = (None if c is None else (c.contiguous() if use_torch else np.ascontiguousarray(c)) for c in (ndcnt, necnt))
+    term, Tx = (0, None) if terminal is None else (1, None) if isinstance(terminal, str) else (2, lqr._contig(terminal, use_torch))
+    entry = _lib.mpc_qp_gain_batch_device if use_torch else _lib.mpc_qp_gain_batch_host
+    out = entry(A, B, H, Pf, D, ndcnt, d, penalty, penalty2, J, necnt, term, Tx, X, U, Lam, Eps, active, N, k0, float(rank_tol), bool(return_all))
+    info, cls = out['info'], out['cls']
+    if use_torch:
+        import torch
+        out.update(status=info[..., 0].to(torch.int32), feas=info[..., 7].clone(), nactive=(cls > 0).sum(dim=-1).to(torch.int32))
+    else:
+        out.update(status=info[..., 0].astype(np.int32), feas=info[..., 7].copy(), nactive=(cls > 0).sum(axis=-1).astype(np.int32))
+    return out
+
+
+def mpc_step_gain(A, B, Q, R, N, sol, horizon, phase0=0, D=None, d=None, Pf=None, penalty=None, penalty2=None, J=None, terminal=None, active=None,
+                  rank_tol=1e-9):
+    """The local gain of one solved step of one model in the reference's calling style, beside mpc_step: A, B, Q, R, N, D, d, Pf, penalty, penalty2, J,
+    terminal as mpc_step took them; sol a dict with X [horizon+1,nx], U [horizon,nu], lam [horizon,nd] (what mpc_step returned) and eps (its info['eps'])
+    with penalties; active int [horizon,nd] or None.  Returns (K0 [nu,nx], info dict: Pi0, Hn0 [cnt0,nx], cnt0, cls, nactive, strict, status, feas).
+    RuntimeError when the pass ended with a status != 0."""
+    who = 'mpc_step_gain'
+    if not isinstance(sol, dict) or sol.get('X') is None:
+        raise ValueError('{}: sol must be a dict with X, U, lam (and eps where the problem has it)'.format(who))
+    X = _to_array(sol['X']).astype(np.float64)
+    As, Bs, Hs, _, kw = _stack_one(who, A, B, Q, R, N, X[0] if X.ndim == 2 else X, D, d, None, Pf, penalty, penalty2)
+    kw.pop('q')
+    eq = _stack_eq(who, As.shape[1], As.shape[2], As.shape[2] + Bs.shape[3], J, None, terminal)
+    kw.update(J=eq['J'], necnt=eq['necnt'], terminal=eq['terminal'])
+    s = {k: None if sol.get(k) is None else np.ascontiguousarray(_to_array(sol[k]).astype(np.float64)[None, None]) for k in ('X', 'U', 'lam', 'eps')}
+    if s['lam'] is not None and kw['D'] is not None and s['lam'].shape[-1] < kw['D'].shape[2]:
+        raise ValueError('{}: sol[\'lam\'] must hold one column per row of D'.format(who))
+    act = None if active is None else np.ascontiguousarray(np.asarray(_to_array(active)).astype(np.int32)[None, None])
+    res = mpc_qp_gain_batch(As, Bs, Hs, s, horizon, phase0, active=act, rank_tol=rank_tol, **kw)
+    st = int(res['status'][0, 0])
+    if st != 0:
+        raise RuntimeError('{}: the pass ended with status {} ({})'.format(who, st, GAIN_STATUS_NAMES.get(st)))
+    c0 = int(res['cnt0'][0, 0])
+    return res['K0'][0, 0], dict(Pi0=res['Pi0'][0, 0], Hn0=res['Hn0'][0, 0, :c0], cnt0=c0, cls=res['cls'][0, 0], nactive=res['nactive'][0, 0],
+                                 strict=float(res['strict'][0, 0]), status=st, feas=float(res['feas'][0, 0]))
+
+
+def mpc_gain_equivalence_batch(A, B, H, Hc, X0, horizon, P=None, phase0=0, D=None, d=None, ndcnt=None, q=None, Pf=None, tol=TOL, max_iter=MAX_ITER,
+                               penalty=None, penalty2=None, J=None, r=None, necnt=None, terminal=None, rank_tol=1e-9):
+    """The feedback-equivalence certificate of the constrained step: the tracking QP on Hc with the terminal weight Pf and the economic QP on H with
+    Pf + P[(phase0 + N) mod p] (the convention of horizon_equivalence_batch: the two costs differ by x_0' P x_0 - x_N' P x_N, so they are the same problem)
+    are solved from X0 [nb,ns,nx], and the local gains of both sides (mpc_qp_gain_batch) are taken at the active set found on Hc.  Without terminal rows the
+    terminal weights must match, so terminal=None needs P (ValueError without it); the other problem keywords as in mpc_qp_batch.
+
+    An instance that fails on either side (an infeasible x_0: status 1 of the solve, NaN solution, status 3 of the pass) returns NaN / False and its statuses;
+    the other instances of the batch are not affected.
+
+    Returns dict of numpy arrays [nb,ns]: du0 = max|u0(H) - u0(Hc)| and same_active (the classes of the two solutions agree in every row) -- NaN / False where
+    the H side did not converge, e.g. status 2 on an indefinite H --, dK0 = max|K0(H) - K0(Hc)| on the projected gains at the active set of the Hc side,
+    dK0_rel = dK0 / max(1, max|K0(Hc)|), subspace_diff = max|Pz_0(H) - Pz_0(Hc)|, strict (of the Hc solution: dK0 means nothing where it is near 0),
+    status_qp_H, status_qp_Hc (the solves), status_H, status_Hc (the passes); and K0, K0c, cls as the entries returned them."""
+    who = 'mpc_gain_equivalence_batch'
+    if terminal is None and P is None:
+        raise ValueError('{}: without terminal rows the H side must carry the terminal weight Pf + P[(phase0 + N) mod p] for the two problems to be the '
+                         'same: P is needed'.format(who))
+    use_torch = _cl._check_kind(who, [('A', A), ('B', B), ('H', H), ('Hc', Hc), ('X0', X0)] + [(nm, x) for nm, x in (('P', P), ('Pf', Pf)) if x is not None])
+    if tuple(Hc.shape) != tuple(H.shape):
+        raise ValueError('{}: Hc {} expected, got {}'.format(who, tuple(H.shape), tuple(Hc.shape)))
+    if P is not None and tuple(P.shape) != tuple(A.shape):
+        raise ValueError('{}: P {} expected, got {}'.format(who, tuple(A.shape), tuple(P.shape)))
+    PfH = Pf if P is None else (P if Pf is None else Pf + P)
+    rows = dict(D=D, d=d, ndcnt=ndcnt, penalty=penalty, J=J, necnt=necnt, terminal=terminal)
+    if penalty2 is not None:
+        rows['penalty2'] = penalty2
+    qp = dict(q=q, tol=tol, max_iter=max_iter, r=r)
+    sC = _step(who, A, B, Hc, X0, horizon, phase0, Pf=Pf, **rows, **qp)
+    sH = _step(who, A, B, H, X0, horizon, phase0, Pf=PfH, **rows, **qp)
+    gC = mpc_qp_gain_batch(A, B, Hc, sC, horizon, phase0, Pf=Pf, rank_tol=rank_tol, **rows)
+    # the classes of the Hc side as the override of the H side; an instance that failed there (a NaN solution: status 3, or status 5) left -1 at its unfinished
+    # stages: taken as 0 here, that instance ends with status 3 / NaN on its own NaN solution or is masked below, and its neighbours are not touched
+    act = None
+    if gC['cls'].shape[-1]:
+        act = gC['cls'].clamp(min=0) if use_torch else np.maximum(gC['cls'], 0)
+    gH = mpc_qp_gain_batch(A, B, H, sC, horizon, phase0, Pf=PfH, rank_tol=rank_tol, active=act, **rows)
+    gR = mpc_qp_gain_batch(A, B, H, sH, horizon, phase0, Pf=PfH, rank_tol=rank_tol, **rows)      # the H solution through the rule: its classes
+    host = (lambda x: x.cpu().numpy()) if use_torch else (lambda x: np.array(x))
+    nb, ns = int(X0.shape[0]), int(X0.shape[1])
+    flat = lambda x: host(x).reshape(nb, ns, -1)
+    with np.errstate(invalid='ignore'):
+        du0 = np.abs(flat(sH['u0']) - flat(sC['u0'])).max(axis=2)
+        dK0 = np.abs(flat(gH['K0']) - flat(gC['K0'])).max(axis=2)
+        rel = dK0 / np.maximum(1.0, np.abs(flat(gC['K0'])).max(axis=2))
+        PzH = np.einsum('bsji,bsjl->bsil', host(gH['Hn0']), host(gH['Hn0'])); PzC = np.einsum('bsji,bsjl->bsil', host(gC['Hn0']), host(gC['Hn0']))
+        sd = np.abs(PzH - PzC).reshape(nb, ns, -1).max(axis=2)
+    okH = host(sH['status']) == 0
+    same = okH & (host(sC['status']) == 0) & (flat(gR['cls']) == flat(gC['cls'])).all(axis=2) & (host(gR['status']) != 3)
+    du0 = np.where(okH, du0, np.nan)
+    okC = host(gC['status']) == 0                                           # (status 5 on the Hc side: the H side ran at a clamped set, which is no active set)
+    dK0, rel, sd = (np.where(okC, x, np.nan) for x in (dK0, rel, sd))
+    same = same & okC
+    return dict(du0=du0, same_active=same, dK0=dK0, dK0_rel=rel, subspace_diff=sd, strict=host(gC['strict']), status_qp_H=host(sH['status']),
+                status_qp_Hc=host(sC['status']), status_H=host(gH['status']), status_Hc=host(gC['status']), K0=gH['K0'], K0c=gC['K0'], cls=gC['cls'])
