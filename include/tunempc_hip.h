@@ -614,6 +614,47 @@ int tmpc_mpc_qp_gain_batch_device(int nb, int p, int nx, int mb, int nd, int ne,
                                   const double* Lam, const double* Eps, const int32_t* cls_in, double rank_tol, double* K0, double* Pi0, double* Hn0,
                                   int32_t* cnt0, double* info, int32_t* cls, double* strict, double* Kall, int32_t* cntall, double* dX, double* dU);
 
+/* The periodic optimal-control QP on the p-periodic affine model (tmpc_periodic_qp.h; the LQ case of the reference's pocp.py, the QP subproblem of its
+ * sqp_method.Sqp): the orbit that the MPC entries above take as their reference.  Per problem, with N = periods p and k_j = j mod p,
+ *     min  sum_{j<N} (1/2 z_j' H_k z_j + q_k' z_j),   z_j = [x_j; u_j],
+ *     s.t. x_{j+1} = A_k x_j + B_k u_j + c_k,  j = 0 .. N-1,  x_N := x_0  (x_0 is a variable),
+ *          D_k z_j <= d_k (first ndcnt_k rows of the stage),   J_k z_j = r_k (first necnt_k rows of the stage).
+ * Not served (there are no arguments for them): soft and quadratic-slack rows, warm starts, a terminal cost (Pf has no meaning without an end), the
+ * phase-fixing cost of pocp.py, nonlinear dynamics and the SQP outer loop.
+ * Method: the interior-point iteration of the MPC entries (hard rows, equality rows at the weight 1 / rho, Mehrotra's predictor-corrector, one step length,
+ * the same stop rule: tmpc_periodic_qp.h and tests/periodic_qp_reference.py state the rules).  The multiplier of x_N = x_0 is a variable of the iteration; the
+ * Newton system is the Riccati pass plus a border of nx columns and one symmetric quasi-definite system of size 2 nx per iteration.
+ * Inputs: A [nb][p][nx][nx], B [nb][p][nx][mb], H [nb][p][n][n] (used as (H + H') / 2); optional (NULL: zero) q [nb][p][n], offset c [nb][p][nx];
+ * D [nb][p][nd][n], d [nb][p][nd] (both NULL exactly when nd = 0), ndcnt int32 [nb][p] (NULL: all nd rows; a count outside 0 .. nd is clamped to it);
+ * J [nb][p][ne][n] (NULL exactly when ne = 0), r [nb][p][ne] (NULL: zero), necnt int32 [nb][p] (NULL: all ne rows; clamped to 0 .. ne); tol > 0,
+ * max_iter >= 1 (the defaults of the reference statement: 1e-10, 60).
+ * Outputs: required info [nb][8]; optional (NULL: not written) X [nb][N][nx] = x_0 .. x_{N-1}, U [nb][N][mb], Lam [nb][N][nd] (rows beyond ndcnt zero),
+ * Nu [nb][N][ne] (free sign; rows beyond necnt zero), Pi [nb][N][nx]: the multipliers of the dynamics, Pi[0] that of x_N = x_0 and Pi[j] that of
+ * x_j = A x_{j-1} + B u_{j-1} + c, with (H z_j + q + D' lam_j + J' nu_j)_x + A_j' Pi[(j + 1) mod N] = Pi[j]; res [nb][4] = (cost, hres = max(D z - d) over
+ * all stages (-inf without rows), eres = max|J z - r|, per = max|A x_{N-1} + B u_{N-1} + c - x_0|).  info, the fields of the MPC entries:
+ *   [0] status: 0 converged; 1 max_iter reached (contradictory rows end here); 2 a stage matrix, Pi_0 or the border's Schur complement not positive definite
+ *       (not convex along the path, or no unique periodic trajectory: A = I, B = 0, c != 0 ends here -- such a problem never ends with 0); 3 non-finite.
+ *       With status != 0 X, U, Lam, Nu, Pi, res are NaN.  One problem never affects another;
+ *   [1] steps: 1 on success, else 0; [2] = [3] iterations; [4] mu, [5] primal and [6] dual residual at the last stop test; [7] smallest pivot of the
+ *   Cholesky factorisations, those of the border included.
+ * The numbers of a problem do not depend on nb, on the other problems or on the workspace slot it ran in (fixed order of accumulation); the host entry stages
+ * through device buffers and runs the same kernel.  Workspace: the library keeps min(nb, 512) slots of
+ * 8 (2 (N+1) n + 6 N nd + N nx + N mb (n+1) + 2 N ne + N mb nx + N nx) bytes per thread, fewer slots where that would exceed 1 GiB.  LDS: the layout of the
+ * eq entries with nt = 0 plus 8 ldp (2 nx + n + mb + 10) bytes, ldp = nx | 1 (nx 24 / mb 8 / nd 16: 56144 bytes).
+ * TMPC_E_ARG: nb, p, nx, mb, periods < 1, nd, ne < 0, D / d / nd mismatch, ndcnt without D, J / ne mismatch, r or necnt without J, tol <= 0, max_iter < 1,
+ * NULL A, B, H, info.  TMPC_E_UNSUPPORTED (before the device is touched): nx + mb > TMPC_LQR_NMAX, the layout beyond 160 KB of LDS (with the byte count),
+ * periods p beyond 32-bit indices inside a slot. */
+#define TMPC_PERIODIC_QP_INFO 8
+#define TMPC_PERIODIC_QP_RES 4
+int tmpc_periodic_qp_batch_host(int nb, int p, int nx, int mb, int nd, int ne, int periods, const double* A, const double* B, const double* H, const double* q,
+                                const double* offset, const double* D, const int32_t* ndcnt, const double* d, const double* J, const double* r,
+                                const int32_t* necnt, double tol, int max_iter, double* X, double* U, double* Lam, double* Nu, double* Pi, double* info,
+                                double* res);
+int tmpc_periodic_qp_batch_device(int nb, int p, int nx, int mb, int nd, int ne, int periods, const double* A, const double* B, const double* H, const double* q,
+                                  const double* offset, const double* D, const int32_t* ndcnt, const double* d, const double* J, const double* r,
+                                  const int32_t* necnt, double tol, int max_iter, double* X, double* U, double* Lam, double* Nu, double* Pi, double* info,
+                                  double* res);
+
 /* Accumulated hipEvent timings since the last call (ms) when TMPC_FLAG_PROFILE is set, 16 doubles:
  * out[0] stage_pre+ctrl, [1] schur assembly, [2] block factorisation (all kernels of tmpc_cr.h's factor phase), [3] predictor
  * pass, [4] corrector pass + update, [5] number of factorisation phases (= IPM iterations of the chunks), [6] total ms of the

@@ -36,6 +36,7 @@
 #include "tmpc_closed_loop.h"
 #include "tmpc_mpc_qp.h"
 #include "tmpc_mpc_qp_gain.h"
+#include "tmpc_periodic_qp.h"
 #include "tmpc_dd.h"
 #include "tmpc_big.h"
 
@@ -2807,6 +2808,120 @@ int tmpc_mpc_qp_warm_batch_host(int nb, int p, int nx, int mb, int nd, int N, in
                                {offset, qf, terminal_rhs, Ap, Bp, cp, W}, penalty2, warm_flags, warm_floor, Xg, Ug, Lamg, Eg, Nug, NuTg, warmlog, true});
 }
 #undef MPC_QP_ARGS31
+
+// The periodic optimal-control QP (tmpc_periodic_qp.h): one workgroup per problem, min(nb, MQ_SLOTS) workgroups loop over the problems, each with its slot of
+// the workspace.  One record, one check, one launch; the host entry stages every array of the record through one device buffer.
+static_assert(PQ_INFO == TMPC_PERIODIC_QP_INFO && PQ_RES == TMPC_PERIODIC_QP_RES, "tunempc_hip.h: strides of the periodic QP entries");
+
+static int periodic_qp_check(const char* who, int nb, int periods, const PeriodicQpArgs& a) {
+  if (nb < 1 || a.p < 1 || a.nx < 1 || a.mb < 1 || periods < 1 || a.nd < 0 || a.ne < 0 || !a.A || !a.B || !a.H || !a.info) {
+    snprintf(g_err, sizeof(g_err), "%s: bad argument (nb, p, nx, nu, periods >= 1, nd, ne >= 0, non-null A, B, H, info; got periods = %d, nd = %d, ne = %d)", who,
+             periods, a.nd, a.ne);
+    return TMPC_E_ARG;
+  }
+  if (((a.nd > 0) != (a.D != nullptr)) || ((a.nd > 0) != (a.d != nullptr)) || (a.ndcnt && !a.D)) {
+    snprintf(g_err, sizeof(g_err), "%s: bad argument (D and d non-null exactly when nd > 0, the row capacity per stage; ndcnt only with D; got nd = %d)", who, a.nd);
+    return TMPC_E_ARG;
+  }
+  if (((a.ne > 0) != (a.J != nullptr)) || ((a.r || a.necnt) && !a.J)) {
+    snprintf(g_err, sizeof(g_err), "%s: bad argument (J non-null exactly when ne > 0, the equality-row capacity per stage; r and necnt only with J; got ne = %d)",
+             who, a.ne);
+    return TMPC_E_ARG;
+  }
+  if (!(a.tol > 0.0) || a.max_iter < 1) {
+    snprintf(g_err, sizeof(g_err), "%s: bad argument (tol > 0, max_iter >= 1; got tol = %g, max_iter = %d)", who, a.tol, a.max_iter);
+    return TMPC_E_ARG;
+  }
+  if (a.nx + a.mb > LQR_NMAX) {
+    snprintf(g_err, sizeof(g_err), "%s: the periodic QP handles stage blocks up to nx + nu = %d (got %d)", who, LQR_NMAX, a.nx + a.mb);
+    return TMPC_E_UNSUPPORTED;
+  }
+  const long long bytes = (long long)periodic_qp_lds(a.nx, a.mb, a.nd < 65536 ? a.nd : 65536, a.ne < 65536 ? a.ne : 65536).total * (long long)sizeof(double);
+  if (bytes > LQR_LDS_BYTES) {
+    snprintf(g_err, sizeof(g_err), "%s: nx = %d, nu = %d with room for %d rows and %d equality rows per stage needs %lld bytes of LDS (limit %d)", who, a.nx, a.mb,
+             a.nd, a.ne, bytes, LQR_LDS_BYTES);
+    return TMPC_E_UNSUPPORTED;
+  }
+  const long long N = (long long)periods * a.p, n = a.nx + a.mb, widest = std::max<long long>(std::max(a.nd, a.ne), a.mb * (n + 1));
+  if (N > 0x7fffffffLL / 4 || (N + 1) * n > 0x7fffffffLL / 4 || N * widest > 0x7fffffffLL / 4) {
+    snprintf(g_err, sizeof(g_err), "%s: periods * p = %lld stages are too many for this stage shape (32-bit indices inside a slot)", who, N);
+    return TMPC_E_UNSUPPORTED;
+  }
+  return TMPC_OK;
+}
+
+static thread_local EigScratch g_periodic_qp_ws;      // workspace slots, kept between calls and grown on demand
+
+static int periodic_qp_launch(int nb, PeriodicQpArgs a) {
+  const long long per = periodic_qp_ws_doubles(a.nx, a.mb, a.nd, a.ne, a.N) * 8;
+  long long slots = nb < MQ_SLOTS ? nb : MQ_SLOTS;
+  if (slots * per > MQ_WS_CAP_BYTES) slots = MQ_WS_CAP_BYTES / per;
+  if (slots < 1) slots = 1;
+  HIPCHK(g_periodic_qp_ws.reserve((size_t)(slots * per)));
+  HIPCHK(hipFuncSetAttribute((const void*)k_periodic_qp, hipFuncAttributeMaxDynamicSharedMemorySize, LQR_LDS_BYTES));      // (the same value from every thread and call)
+  a.ws = (double*)g_periodic_qp_ws.p;
+  a.nb = nb;
+  a.lcw = 0;
+  while ((1 << a.lcw) < a.nx + a.mb) ++a.lcw;
+  hipLaunchKernelGGL(k_periodic_qp, dim3((unsigned)slots), dim3(LQR_NT), (size_t)periodic_qp_lds(a.nx, a.mb, a.nd, a.ne).total * sizeof(double), 0, a);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(0));
+  return TMPC_OK;
+}
+
+#define PERIODIC_QP_RECORD                                                                                                                                  \
+  PeriodicQpArgs a{};                                                                                                                                       \
+  a.p = p; a.nx = nx; a.mb = mb; a.nd = nd; a.ne = ne; a.N = (int)((long long)periods * p < 0x7fffffffLL ? (long long)periods * p : 0x7fffffffLL);          \
+  a.max_iter = max_iter; a.tol = tol; a.A = A; a.B = B; a.H = H; a.q = q; a.c = offset; a.D = D; a.ndcnt = (const int*)ndcnt; a.d = d; a.J = J; a.r = r;     \
+  a.necnt = (const int*)necnt; a.X = X; a.U = U; a.Lam = Lam; a.Nu = Nu; a.Pi = Pi; a.info = info; a.res = res
+
+int tmpc_periodic_qp_batch_device(int nb, int p, int nx, int mb, int nd, int ne, int periods, const double* A, const double* B, const double* H, const double* q,
+                                  const double* offset, const double* D, const int32_t* ndcnt, const double* d, const double* J, const double* r,
+                                  const int32_t* necnt, double tol, int max_iter, double* X, double* U, double* Lam, double* Nu, double* Pi, double* info,
+                                  double* res) {
+  PERIODIC_QP_RECORD;
+  const int rc = periodic_qp_check("tmpc_periodic_qp_batch_device", nb, periods, a);
+  if (rc != TMPC_OK) return rc;
+  return periodic_qp_launch(nb, a);
+}
+
+static thread_local EigScratch g_periodic_qp_scratch;      // device images of the host entry, kept between calls and grown on demand
+
+int tmpc_periodic_qp_batch_host(int nb, int p, int nx, int mb, int nd, int ne, int periods, const double* A, const double* B, const double* H, const double* q,
+                                const double* offset, const double* D, const int32_t* ndcnt, const double* d, const double* J, const double* r,
+                                const int32_t* necnt, double tol, int max_iter, double* X, double* U, double* Lam, double* Nu, double* Pi, double* info,
+                                double* res) {
+  PERIODIC_QP_RECORD;
+  const int rc = periodic_qp_check("tmpc_periodic_qp_batch_host", nb, periods, a);
+  if (rc != TMPC_OK) return rc;
+  const size_t n = (size_t)nx + mb, st = (size_t)nb * p, sn = (size_t)nb * a.N, i4 = sizeof(int32_t);
+  // every array of the record, inputs then outputs: (host pointer, field of the device record, bytes)
+  struct Slot { const void* host; const void** dev; size_t bytes; bool out; };
+  const Slot slots[] = {
+    {A, (const void**)&a.A, st * nx * nx * 8, false}, {B, (const void**)&a.B, st * nx * mb * 8, false}, {H, (const void**)&a.H, st * n * n * 8, false},
+    {q, (const void**)&a.q, st * n * 8, false}, {offset, (const void**)&a.c, st * nx * 8, false}, {D, (const void**)&a.D, st * nd * n * 8, false},
+    {ndcnt, (const void**)&a.ndcnt, st * i4, false}, {d, (const void**)&a.d, st * nd * 8, false}, {J, (const void**)&a.J, st * ne * n * 8, false},
+    {r, (const void**)&a.r, st * ne * 8, false}, {necnt, (const void**)&a.necnt, st * i4, false},
+    {X, (const void**)&a.X, sn * nx * 8, true}, {U, (const void**)&a.U, sn * mb * 8, true}, {Lam, (const void**)&a.Lam, sn * nd * 8, true},
+    {Nu, (const void**)&a.Nu, sn * ne * 8, true}, {Pi, (const void**)&a.Pi, sn * nx * 8, true}, {info, (const void**)&a.info, (size_t)nb * PQ_INFO * 8, true},
+    {res, (const void**)&a.res, (size_t)nb * PQ_RES * 8, true}};
+  size_t total = 0;
+  for (const Slot& s : slots) if (s.host && s.bytes) total += (s.bytes + 7) & ~(size_t)7;
+  HIPCHK(g_periodic_qp_scratch.reserve(total + 8));
+  char* base = (char*)g_periodic_qp_scratch.p;
+  size_t off = 0;
+  for (const Slot& s : slots) {
+    if (!s.host || !s.bytes) { *s.dev = nullptr; continue; }
+    *s.dev = base + off;
+    if (!s.out) HIPCHK(hipMemcpy(base + off, s.host, s.bytes, hipMemcpyHostToDevice));
+    off += (s.bytes + 7) & ~(size_t)7;
+  }
+  const int rl = periodic_qp_launch(nb, a);
+  if (rl != TMPC_OK) return rl;
+  for (const Slot& s : slots) if (s.out && s.host && s.bytes) HIPCHK(hipMemcpy((void*)s.host, *s.dev, s.bytes, hipMemcpyDeviceToHost));
+  return TMPC_OK;
+}
+#undef PERIODIC_QP_RECORD
 
 int tmpc_tracking_reference_host(tmpc_handle* h, int nstage, const double* Hc, const double* q, const double* wref,
                                  double ts, double* W, double* yref, int32_t* info) {

@@ -773,7 +773,8 @@ def about_reference(A, B, H, xref, uref, q=None, Pf=None, D=None, d=None, J=None
         q_k - H_k wref_k,   d_k + D_k wref_k,   r_k + J_k wref_k,   qf_k = -Pf_k xref_k,   terminal_rhs_k = Tx_k xref_k  (xref_k for terminal='constraint').
     Returns a dict with offset, q, and, where the argument is given, Pf, qf, D, d, J, r, terminal, terminal_rhs: pass it as **kwargs next to A, B, H and the
     ABSOLUTE X0 (and ndcnt, necnt, penalty, penalty2, which do not change: penalty2 passes through like penalty).  The solution is the deviation solution plus the reference with the same multipliers; the
-    cost differs by a constant.  Host-side numpy or torch (all arguments of one kind), no kernel."""
+    cost differs by a constant.  Host-side numpy or torch (all arguments of one kind), no kernel.  A producer of xref, uref is tunempc_amd.periodic_qp:
+    X[:, :p], U[:, :p] of periodic_qp_batch are what this function takes as xref, uref."""
     who = 'about_reference'
     Tx = terminal if hasattr(terminal, 'shape') else None
     if terminal is not None and Tx is None and not (isinstance(terminal, str) and terminal == 'constraint'):
