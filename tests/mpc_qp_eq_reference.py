@@ -77,8 +77,10 @@ def unpack_nu(P, nu):
     return Nu, np.array(nu[ms:], float)
 
 
-def ipm_eq(P, cvec=None, tol=mq.TOL, max_iter=mq.MAX_ITER):
-    """Method (a) -> dict v, lam, s, e, nu (of e >= 0), nue (of the rows of Je), iters, status, mu, rp, rd.  cvec: one weight per row of G (None: all hard)."""
+def ipm_eq(P, cvec=None, tol=mq.TOL, max_iter=mq.MAX_ITER, augmented=False):
+    """Method (a) -> dict v, lam, s, e, nu (of e >= 0), nue (of the rows of Je), iters, status, mu, rp, rd.  cvec: one weight per row of G (None: all hard).
+    augmented: the same Newton system with dnue as an unknown, its rows [Je, -RHO I] kept as rows: no 1 / RHO stands in the matrix, and dnue is not formed as
+    the difference Je dv + req blown up by 1 / RHO (the truth path of tests/qp_path_reference.py); the iteration and its rules are the same."""
     Q, c, Cm, b, G, h, Je, re = (P[k] for k in ('Q', 'c', 'Cm', 'b', 'G', 'h', 'Je', 're'))
     nv, m, ne = len(c), len(h), len(b)
     Nmb = P['N'] * P['mb']
@@ -123,13 +125,21 @@ def ipm_eq(P, cvec=None, tol=mq.TOL, max_iter=mq.MAX_ITER):
             red = Zn.T @ Kmat[:nv, :nv] @ Zn
             if np.linalg.eigvalsh(red).min() <= 0:
                 status = 2; break
+            me = len(re)
+            if augmented:
+                Kaug = np.block([[Q + G.T @ (w[:, None] * G), Cm.T, Je.T], [Cm, np.zeros((ne, ne + me))], [Je, np.zeros((me, ne)), -RHO * np.eye(me)]])
 
             def solve(c1, c2):
                 beta = rpi - s + e + c1 / lam - np.where(soft, c2 / nu, 0.0)
-                dv = np.linalg.solve(Kmat, np.concatenate([-(rdv + G.T @ (w * beta) + Je.T @ (req / RHO)), -rpe]))[:nv]
+                if augmented:
+                    sol = np.linalg.solve(Kaug, np.concatenate([-(rdv + G.T @ (w * beta)), -rpe, -req]))
+                    dv, dn = sol[:nv], sol[nv + ne:]
+                else:
+                    dv = np.linalg.solve(Kmat, np.concatenate([-(rdv + G.T @ (w * beta) + Je.T @ (req / RHO)), -rpe]))[:nv]
+                    dn = (Je @ dv + req) / RHO
                 dl = w * (beta + G @ dv)
                 de = np.where(soft, -e + c2 / nu + (e / nu) * dl, 0.0)
-                return dv, dl, -rpi - G @ dv + de + RHO * dl, de, (Je @ dv + req) / RHO
+                return dv, dl, -rpi - G @ dv + de + RHO * dl, de, dn
 
             def length(dl, ds, de):
                 a = 1e300

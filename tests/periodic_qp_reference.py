@@ -104,10 +104,12 @@ def adjoint(P, g, piper):
     return piv.reshape(-1)
 
 
-def newton_dense(P, v, lam, s, nue, piper, c1):
-    """The Newton direction at an iterate from the dense KKT matrix -> dv, dlam, ds, dnue, dpi_per, or None when the system has no unique solution."""
+def newton_dense(P, v, lam, s, nue, piper, c1, augmented=False):
+    """The Newton direction at an iterate from the dense KKT matrix -> dv, dlam, ds, dnue, dpi_per, or None when the system has no unique solution.
+    augmented: the same system with dnue as an unknown, its rows [Je, -RHO I] kept as rows: no 1 / RHO stands in the matrix, and dnue is not formed as
+    the difference Je dv + req blown up by 1 / RHO (the truth path of tests/qp_path_reference.py)."""
     Q, c, Cm, b, G, h, Je, re = (P[k] for k in ('Q', 'c', 'Cm', 'b', 'G', 'h', 'Je', 're'))
-    nv, nq = len(c), len(b)
+    nv, nq, me = len(c), len(b), len(re)
     g = Q @ v + c + G.T @ lam + Je.T @ nue
     rdv = g + Cm.T @ adjoint(P, g, piper)
     rpe = Cm @ v - b; rpi = G @ v + s - h; req = Je @ v - re
@@ -123,6 +125,12 @@ def newton_dense(P, v, lam, s, nue, piper, c1):
     if Zn.shape[1] and np.linalg.eigvalsh(Zn.T @ Hb @ Zn).min() <= 0:
         return None
     beta = rpi - s + c1 / lam
+    if augmented:
+        Kaug = np.block([[Q + G.T @ (w[:, None] * G), Cm.T, Je.T], [Cm, np.zeros((nq, nq + me))], [Je, np.zeros((me, nq)), -RHO * np.eye(me)]])
+        sol = np.linalg.solve(Kaug, np.concatenate([-(rdv + G.T @ (w * beta)), -rpe, -req]))
+        dv, dn = sol[:nv], sol[nv + nq:]
+        dl = w * (beta + G @ dv)
+        return dv, dl, -rpi - G @ dv + RHO * dl, dn, sol[nv:nv + nq][-P['nx']:]
     sol = np.linalg.solve(Kmat, np.concatenate([-(rdv + G.T @ (w * beta) + Je.T @ (req / RHO)), -rpe]))
     dv = sol[:nv]
     dl = w * (beta + G @ dv)
@@ -136,12 +144,16 @@ def newton_border(P, v, lam, s, nue, piper, c1):
         [ Pi_0       M_0 - I ] [dx_0]     [ a   ]
         [ M_0' - I   -Gamma  ] [dpi ] = - [ phi ]
     by Pi_0 = R0' R0, W = R0^-T (M_0 - I), (Gamma + W' W) dpi = phi - W' R0^-T a, dx_0 = -R0^-1 (R0^-T a + W dpi); the forward sweep
-    du = -R^-1 (Y dx + y + Gy dpi), dx+ = E dz + r_dyn.  -> dv, dpi."""
+    du = -R^-1 (Y dx + y + Gy dpi), dx+ = E dz + r_dyn.  -> dv, dpi, pivots: the elimination pivots the kernel feeds to pivmin, the squares of the
+    diagonals of (the R of the stages j = N-1 .. 0, one array; R0 then R2, one array): the first set belongs to pass 1 of the iterate, the second to
+    the border system that only an iterate that takes a step factors; rows: (dlam, ds, dnue) from the forward sweep, stage by stage, with the residuals
+    r_in and r_eq that entered the right-hand side: dlam = w (r_in - s + c1 / lam + D dz), ds = -r_in - D dz + RHO dlam, dnu = (1 / RHO)(J dz + r_eq)."""
     N, nx, mb = P['N'], P['nx'], P['mb']
     X, U, _, _, _ = unpack(P, v)
     w = lam / (s + RHO * lam)
     Pi = np.zeros((nx, nx)); pv = np.array(piper, float); M = np.eye(nx); Gam = np.zeros((nx, nx)); phi = np.zeros(nx)
     fac = [None] * N
+    spiv = []
     for j in range(N - 1, -1, -1):
         S = P['stages'][j]
         E, z = S['E'], np.concatenate([X[j], U[j]])
@@ -159,31 +171,67 @@ def newton_border(P, v, lam, s, nue, piper, c1):
         M = T[:nx] - Y.T @ Gy
         Pi = 0.5 * (Hb[:nx, :nx] + Hb[:nx, :nx].T) - Y.T @ Y
         pv = hh[:nx] - Y.T @ y
-        fac[j] = (R, Y, y, Gy, rdyn)
+        fac[j] = (R, Y, y, Gy, rdyn, rin, rq)
+        spiv.append(np.diag(R) ** 2)
     a = pv - piper
     R0 = np.linalg.cholesky(Pi).T
     W = np.linalg.solve(R0.T, M - np.eye(nx)); wv = np.linalg.solve(R0.T, a)
-    dpi = np.linalg.solve(Gam + W.T @ W, phi - W.T @ wv)
+    R2 = np.linalg.cholesky(Gam + W.T @ W).T
+    dpi = np.linalg.solve(R2, np.linalg.solve(R2.T, phi - W.T @ wv))
     dx = -np.linalg.solve(R0, wv + W @ dpi)
     dX = np.zeros((N, nx)); dU = np.zeros((N, mb))
+    dl = np.zeros(len(lam)); ds = np.zeros(len(lam)); dn = np.zeros(len(nue))
     for j in range(N):
-        R, Y, y, Gy, rdyn = fac[j]
+        R, Y, y, Gy, rdyn, rin, rq = fac[j]
+        S = P['stages'][j]
         du = -np.linalg.solve(R, Y @ dx + y + Gy @ dpi)
         dX[j], dU[j] = dx, du
-        dx = P['stages'][j]['E'] @ np.concatenate([dx, du]) + rdyn
-    return np.concatenate([dX.reshape(-1), dU.reshape(-1)]), dpi
+        dz = np.concatenate([dx, du])
+        gi, ei = P['stage'] == j, P['estage'] == j
+        Dz = S['D'] @ dz
+        dl[gi] = w[gi] * (rin - s[gi] + c1[gi] / lam[gi] + Dz)
+        ds[gi] = -rin - Dz + RHO * dl[gi]
+        dn[ei] = (S['J'] @ dz + rq) / RHO
+        dx = S['E'] @ dz + rdyn
+    return np.concatenate([dX.reshape(-1), dU.reshape(-1)]), dpi, (np.concatenate(spiv), np.concatenate([np.diag(R0) ** 2, np.diag(R2) ** 2])), (dl, ds, dn)
 
 
-def ipm(P, tol=TOL, max_iter=MAX_ITER):
-    """Method (a) -> dict v, lam, s, nue, pi (the N blocks of Cm), piper, iters, status, mu, rp, rd."""
+def newton_staged(P, v, lam, s, nue, piper, c1, reuse=True):
+    """newton_border as the tuple of newton_dense -> dv, dlam, ds, dnue, dpi_per.  reuse=True: the rows of its forward sweep, as the kernel computes them.
+    reuse=False: dlam, ds, dnue by the same formulas from residuals G v + s - h and Je v - re EVALUATED AGAIN on the dense problem.  They differ from the
+    residuals inside the right-hand side by one rounding (another order of summation), 1e-16, and the formulas multiply that by w <= 1 / RHO = 1e12: the
+    multipliers then carry a noise of 1e-4 that no later step removes, and r_d stalls there (test_qp_path_cpu.py shows both)."""
+    dv, dpi, _, rows = newton_border(P, v, lam, s, nue, piper, c1)
+    if reuse:
+        return (dv,) + rows + (dpi,)
+    G, h, Je, re = (P[k] for k in ('G', 'h', 'Je', 're'))
+    w = lam / (s + RHO * lam)
+    rpi = G @ v + s - h
+    dl = w * (rpi - s + c1 / lam + G @ dv)
+    return dv, dl, -rpi - G @ dv + RHO * dl, (Je @ dv + (Je @ v - re)) / RHO, dpi
+
+
+def ipm(P, tol=TOL, max_iter=MAX_ITER, augmented=False, staged=False, pivots=False, reuse=True):
+    """Method (a) -> dict v, lam, s, nue, pi (the N blocks of Cm), piper, iters, status, mu, rp, rd.  augmented: the directions from newton_dense(augmented=True);
+    staged: from newton_staged(reuse=reuse) (the kernel's elimination) -- the iteration and its rules are the same, only the linear algebra of the step differs.  pivots: also
+    pivmin, the smallest elimination pivot of newton_border the way the kernel collects it: over pass 1 of every iterate reached, the last included, and over
+    the border systems of the iterates that took a step."""
     Q, c, Cm, b, G, h, Je, re = (P[k] for k in ('Q', 'c', 'Cm', 'b', 'G', 'h', 'Je', 're'))
     nv, m, nx, Nnx = len(c), len(h), P['nx'], P['N'] * P['nx']
     v = np.zeros(nv); s = np.maximum(P['d0'], 1.0) if m else np.zeros(0); lam = np.ones(m); nue = np.zeros(len(re)); piper = np.zeros(nx)
     status, it = 1, 0
     mu = rp = rd = np.nan
     piv = np.zeros(Nnx)
+    pivmin = np.inf
+    if staged:
+        newton = lambda *a: newton_staged(P, *a, reuse=reuse)
+    else:
+        newton = lambda *a: newton_dense(P, *a, augmented=augmented)
     with np.errstate(all='ignore'):
         for it in range(max_iter + 1):
+            if pivots:
+                _, _, (spiv, bpiv), _ = newton_border(P, v, lam, s, nue, piper, np.zeros(m))
+                pivmin = min(pivmin, spiv.min())
             g = Q @ v + c + G.T @ lam + Je.T @ nue
             piv = adjoint(P, g, piper)
             rdv = g + Cm.T @ piv
@@ -201,9 +249,11 @@ def ipm(P, tol=TOL, max_iter=MAX_ITER):
                 break
             if not (np.isfinite(Q).all() and np.isfinite(Cm).all() and np.isfinite(G).all() and np.isfinite(Je).all()):
                 status = 3; break
-            step = newton_dense(P, v, lam, s, nue, piper, np.zeros(m))
+            step = newton(v, lam, s, nue, piper, np.zeros(m))
             if step is None:
                 status = 2; break
+            if pivots:
+                pivmin = min(pivmin, bpiv.min())
 
             def length(dl, ds):
                 a = 1e300
@@ -216,10 +266,13 @@ def ipm(P, tol=TOL, max_iter=MAX_ITER):
             if m:
                 aa = min(1.0, length(dl, ds))
                 sigmu = (float((lam + aa * dl) @ (s + aa * ds)) / m / mu) ** 3 * mu
-                dv, dl, ds, dn, dp = newton_dense(P, v, lam, s, nue, piper, sigmu - ds * dl)
+                dv, dl, ds, dn, dp = newton(v, lam, s, nue, piper, sigmu - ds * dl)
             al = min(1.0, mq.STEP_BACK * length(dl, ds))
             v = v + al * dv; lam = lam + al * dl; s = s + al * ds; nue = nue + al * dn; piper = piper + al * dp
-    return dict(v=v, lam=lam, s=s, nue=nue, pi=piv, piper=piper, iters=it, status=status, mu=mu, rp=rp, rd=rd)
+    out = dict(v=v, lam=lam, s=s, nue=nue, pi=piv, piper=piper, iters=it, status=status, mu=mu, rp=rp, rd=rd)
+    if pivots:
+        out['pivmin'] = pivmin
+    return out
 
 
 def polish(P, active):

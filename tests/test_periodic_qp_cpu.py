@@ -95,7 +95,7 @@ def test_border_elimination_equals_the_dense_newton_direction():
         v = 0.3 * rng.standard_normal(len(P['c'])); lam = rng.uniform(0.5, 2.0, m); s = rng.uniform(0.5, 2.0, m)
         nue = rng.standard_normal(me); pp = rng.standard_normal(P['nx']); c1 = rng.standard_normal(m)
         dd = pq.newton_dense(P, v, lam, s, nue, pp, c1)
-        dv, dpi = pq.newton_border(P, v, lam, s, nue, pp, c1)
+        dv, dpi, _, _ = pq.newton_border(P, v, lam, s, nue, pp, c1)
         ev = np.abs(dd[0] - dv).max() / max(1.0, np.abs(dd[0]).max()); ep = np.abs(dd[4] - dpi).max() / max(1.0, np.abs(dd[4]).max())
         print(c['name'], 'dv %.1e dpi %.1e' % (ev, ep))
         assert max(ev, ep) <= (1e-3 if me else 1e-11), c['name']
