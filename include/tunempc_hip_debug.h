@@ -28,6 +28,9 @@ extern "C" {
 /* Debug bit: the generic per-stage kernels of stage blocks wider than 32 (tmpc_big.h; with them the <true> forms of the multiplier and Step 3 kernels) also at n <= 32, so that they can be
  * compared with the tuned kernels on the same inputs. */
 #define TMPC_DEBUG_FLAG_GENERIC_STAGE 64
+/* Debug bit: only the multiplier kernels (csrc/tmpc_phi.h) take their forms for stage blocks wider than 32 (k_phi_pre<true, *>, k_phi_rhs<true>, kb_phi_dm + k_phi_dir<true>)
+ * at n <= 32; the stage kernels stay the tuned ones, so both forms see the same inputs bit for bit and must return the same bits (tests/test_gpu_phi_kernels.py). */
+#define TMPC_DEBUG_FLAG_GENERIC_ROWS 128
 
 /* C (M x N) <op> A (M x K) * B (N x K)' with the fp64 MFMA tile GEMMs of the factorisation; mode 0: C -= AB', 1: C = AB', 2: C = -AB'.
  * mode + 0: the register-staged core (tmpc_factor.h, one workgroup walks all tiles); + 16: the LDS-DMA tile core (tmpc_gemm_dma.h, one
@@ -92,6 +95,11 @@ int tmpc_debug_get_multipliers(tmpc_handle* h, int nb, int nr, double* phi, doub
  *   33 c1   34 c2 [B,p,n,n] (Mehrotra term sym(dX dS S^-1) of pass 1)   35 L1i   36 L2i   37 LX1i   38 LX2i [B,p,n,n] (inverse Cholesky factors of S_r and X_r, lower
  *   triangular, written by k_stage_pre)   39 Wm [B,p,4,n,n] (step-length matrices; slot 2r: L_r^-1 dS_r L_r^-T, slot 2r+1: LX_r^-1 dX_r LX_r^-T)   40 eigmin [B,p,4] (their
  *   smallest eigenvalues, or the bound -1/theta of k_eigmin's pre-test)   41 TU [B,p,dp,2] (T^-1 U of the last factorisation)
+ *   the stage-local multipliers (csrc/tmpc_phi.h; handles with rows only; phi, z, dphi, dz: tmpc_debug_get_multipliers):   42 G [B,p,nr,n] (rows of [G_k; C_k] as the last host-buffer call staged them, row stride nr of that call)
+ *   43 corrp [B,p,nr] (Mehrotra term dz dphi / phi of pass 1)   44 at   45 adt [B,p,2] (epigraph variables of the norm terms, their directions)
+ *   46 aX   47 adX   48 acor   49 aSi   50 aLi   51 aLXi [B,p,2,AE] (arrow blocks, AE = 32 x 32 with row stride 32: X, dX, sym(dX dS S^-1), S^-1, L_S^-1, L_X^-1)
+ *   52 asum [B,p,5] (<dX,S>, <X,dS>, <dX,dS>, smallest eigenvalue dual / primal of the arrow blocks)   53 prs [B,p,4,nr,nr] (Gram products g_i' X_r g_j (slots 0, 1),
+ *   g_i' S_r^-1 g_j (2, 3) of handles with room for more than 32 rows per stage; absent otherwise)
  * A code whose array this handle does not have is TMPC_E_ARG. */
 int tmpc_debug_get_array(tmpc_handle* h, int which, uint64_t offset, uint64_t count, double* out);
 /* The integer state, LANE 0 ONLY like tmpc_debug_get_array: `count` ints from `offset` of iprob [B,24] (per problem: 0 phase (0 main, 1 centering, 2 done), 1 iterations,

@@ -250,6 +250,11 @@ def _check(lib, rc, what):
         raise RuntimeError(f"tunempc_amd: {what} failed with code {rc}: {lib.tmpc_last_error().decode()}")
 
 
+# which-codes of tmpc_debug_get_array for the row state of the multiplier kernels (csrc/tmpc_phi.h); the arrow arrays are [B,p,2,ARROW_LD,ARROW_LD]
+DEBUG_ARRAY_CODES = dict(psm=0, pvec=1, G=42, corrp=43, at=44, adt=45, aX=46, adX=47, acor=48, aSi=49, aLi=50, aLXi=51, asum=52, prs=53)
+ARROW_LD = 32
+
+
 class HipConvexifier:
     """Handle for batched convexification of problems of one shape (p, nx, mb) on the current HIP device."""
 
@@ -345,6 +350,8 @@ class HipConvexifier:
         return out
 
     def debug_array(self, which, offset, count):
+        """`count` doubles from `offset` of workspace array `which` of lane 0 (tunempc_hip_debug.h: tmpc_debug_get_array; DEBUG_ARRAY_CODES names the codes of
+        the stage-local multipliers).  A code whose array the handle does not have raises RuntimeError (TMPC_E_ARG)."""
         out = np.empty(int(count))
         _check(self.lib, self.lib.tmpc_debug_get_array(self._h, int(which), int(offset), int(count), _dptr(out)), 'tmpc_debug_get_array')
         return out

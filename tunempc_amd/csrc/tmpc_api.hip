@@ -734,7 +734,8 @@ static int run_chunk(tmpc_handle* h, Lane* ln, int nb, const double* dA, const d
   const size_t t3_lds = (size_t)(3 * (dm.nT + 1) + 8) * sizeof(double);
   const bool big = dm.n > NMAX || (h->flags & TMPC_DEBUG_FLAG_GENERIC_STAGE);      // generic per-stage kernels (tmpc_big.h)
   const size_t t3_schur_lds = (size_t)((big ? 0 : 9 * 32 * T3_LD) + 2 * (dm.nT + 1)) * sizeof(double) + (size_t)(2 * (dm.nT + 1) + 2 * (dm.d + 1)) * sizeof(short) + 64;
-  if (big && !ln->ws.bscr) {                 // (debug flag at n <= 32: the scratch is not part of the workspace)
+  const bool bigphi = big || (h->flags & TMPC_DEBUG_FLAG_GENERIC_ROWS);            // <BIGN> forms of the multiplier kernels (tmpc_phi.h) with kb_phi_dm
+  if (bigphi && !ln->ws.bscr) {              // (debug flags at n <= 32: the scratch is not part of the workspace)
     if (hipMalloc(&ln->big_scr, (size_t)h->dm.B * dm.p * BIG_SCR * dm.n * dm.n * sizeof(double)) != hipSuccess) { snprintf(g_err, sizeof(g_err), "hipMalloc of the generic-stage scratch failed"); return TMPC_E_NOMEM; }
     ln->ws.bscr = (double*)ln->big_scr;
   }
@@ -846,8 +847,8 @@ static int run_chunk(tmpc_handle* h, Lane* ln, int nb, const double* dA, const d
     else TMPC_STAGE_LAUNCH(k_stage_pre, slots_bytes(PRE_SLOTS), st, w, dm);
     if (eq) {        // <n above 32, more than 32 rows per stage>
       const bool bigr = dm.nr > NRS;
-      if (big && bigr) hipLaunchKernelGGL((k_phi_pre<true, true>), dim3(BP), dim3(64), (size_t)phi_pre_lds(true, true) * sizeof(double), st, w, dm, 1);
-      else if (big) hipLaunchKernelGGL((k_phi_pre<true, false>), dim3(BP), dim3(64), (size_t)phi_pre_lds(true, false) * sizeof(double), st, w, dm, 1);
+      if (bigphi && bigr) hipLaunchKernelGGL((k_phi_pre<true, true>), dim3(BP), dim3(64), (size_t)phi_pre_lds(true, true) * sizeof(double), st, w, dm, 1);
+      else if (bigphi) hipLaunchKernelGGL((k_phi_pre<true, false>), dim3(BP), dim3(64), (size_t)phi_pre_lds(true, false) * sizeof(double), st, w, dm, 1);
       else if (bigr) hipLaunchKernelGGL((k_phi_pre<false, true>), dim3(BP), dim3(64), (size_t)phi_pre_lds(false, true) * sizeof(double), st, w, dm, 1);
       else hipLaunchKernelGGL((k_phi_pre<false, false>), dim3(BP), dim3(64), (size_t)phi_pre_lds(false, false) * sizeof(double), st, w, dm, 1);
     }
@@ -879,8 +880,12 @@ static int run_chunk(tmpc_handle* h, Lane* ln, int nb, const double* dA, const d
     if (stop_here && h->stop_point == TMPC_DEBUG_STOP_ASSEMBLED) {   // debug (tunempc_hip_debug.h; tests/tools/step3_asm_check.py, tests/test_gpu_schur_assembly.py): stop with the assembled, unfactored system of iteration stop_it (default: the first) in the workspace
       if (big) hipLaunchKernelGGL(kb_stage_rhs, dim3(BP), dim3(256), 0, st, w, dm, 1);
       else TMPC_STAGE_LAUNCH(k_stage_rhs, slots_bytes(RHS_SLOTS), st, w, dm, 1);
+      // (with rows: r_loc of pass 1 and the tails of W3 / U, in the order of the loop below -- the stop means the same for these models as for the plain one)
+      if (eq && bigphi) hipLaunchKernelGGL(k_phi_rhs<true>, dim3(BP), dim3(64), slots_bytes(2), st, w, dm, 1, 1);
+      else if (eq) hipLaunchKernelGGL(k_phi_rhs<false>, dim3(BP), dim3(64), slots_bytes(2), st, w, dm, 1, 1);
       if (t3) hipLaunchKernelGGL(k_t3_rhs, dim3(BP), dim3(64), t3_lds, st, w, dm, 1);
       hipLaunchKernelGGL(k_gather, dim3(BP), dim3(64), 0, st, w, dm, 1);
+      if (eq) hipLaunchKernelGGL(k_aug_gather, dim3(BP), dim3(64), 0, st, w, dm, 1);
       if (t3) hipLaunchKernelGGL(k_t3_gather, dim3(BP), dim3(64), 0, st, w, dm, 1);
       HIPCHK(hipStreamSynchronize(st));
       HIPCHK(hipGetLastError());
@@ -893,7 +898,7 @@ static int run_chunk(tmpc_handle* h, Lane* ln, int nb, const double* dA, const d
     if (fuse1) {
       if (big) hipLaunchKernelGGL(kb_stage_rhs, dim3(BP), dim3(256), 0, st, w, dm, 1);
       else TMPC_STAGE_LAUNCH(k_stage_rhs, slots_bytes(RHS_SLOTS), st, w, dm, 1);
-      if (eq && big) hipLaunchKernelGGL(k_phi_rhs<true>, dim3(BP), dim3(64), slots_bytes(2), st, w, dm, 1, 1);
+      if (eq && bigphi) hipLaunchKernelGGL(k_phi_rhs<true>, dim3(BP), dim3(64), slots_bytes(2), st, w, dm, 1, 1);
       else if (eq) hipLaunchKernelGGL(k_phi_rhs<false>, dim3(BP), dim3(64), slots_bytes(2), st, w, dm, 1, 1);
       hipLaunchKernelGGL(k_gather, dim3(BP), dim3(64), 0, st, w, dm, 1);
       if (eq) hipLaunchKernelGGL(k_aug_gather, dim3(BP), dim3(64), 0, st, w, dm, 1);
@@ -906,7 +911,7 @@ static int run_chunk(tmpc_handle* h, Lane* ln, int nb, const double* dA, const d
       const bool fused = (pass == 1 && fuse1);
       if (!fused && big) hipLaunchKernelGGL(kb_stage_rhs, dim3(BP), dim3(256), 0, st, w, dm, pass);
       else if (!fused) TMPC_STAGE_LAUNCH(k_stage_rhs, slots_bytes(RHS_SLOTS), st, w, dm, pass);
-      if (eq && !fused && big) hipLaunchKernelGGL(k_phi_rhs<true>, dim3(BP), dim3(64), slots_bytes(2), st, w, dm, pass, 1);
+      if (eq && !fused && bigphi) hipLaunchKernelGGL(k_phi_rhs<true>, dim3(BP), dim3(64), slots_bytes(2), st, w, dm, pass, 1);
       else if (eq && !fused) hipLaunchKernelGGL(k_phi_rhs<false>, dim3(BP), dim3(64), slots_bytes(2), st, w, dm, pass, 1);
       if (t3) hipLaunchKernelGGL(k_t3_rhs, dim3(BP), dim3(64), t3_lds, st, w, dm, pass);
       if (!fused) hipLaunchKernelGGL(k_gather, dim3(BP), dim3(64), 0, st, w, dm, pass);
@@ -915,7 +920,7 @@ static int run_chunk(tmpc_handle* h, Lane* ln, int nb, const double* dA, const d
       if (ddm) { const int rc_ = dd_solve(w, dm, h->sched, h->d_sched, alist, active, st, pass, nb); if (rc_ != TMPC_OK) return rc_; }
       else cr_solve(w, dm, h->sched, h->d_sched, alist, active, st, pass, fused);
       hipLaunchKernelGGL(k_solve_border, dim3(active), dim3(256), 0, st, w, dm, (const int*)alist, pass);
-      if (eq && big) {
+      if (eq && bigphi) {
         hipLaunchKernelGGL(kb_phi_dm, dim3(BP), dim3(256), 0, st, w, dm, pass);
         hipLaunchKernelGGL(k_phi_dir<true>, dim3(BP), dim3(64), (size_t)PHI_DIR_LDS * sizeof(double), st, w, dm, pass, 1);
       } else if (eq) hipLaunchKernelGGL(k_phi_dir<false>, dim3(BP), dim3(64), (size_t)PHI_DIR_LDS * sizeof(double), st, w, dm, pass, 1);
@@ -1233,7 +1238,7 @@ int tmpc_get_chunk(tmpc_handle* h) { return h ? h->chunk : TMPC_E_ARG; }
 
 int tmpc_set_options(tmpc_handle* h, double tol, double center_tol, int max_iter, int center_iter, int flags) {
   if (!h) return TMPC_E_ARG;
-  if (flags & ~(TMPC_FLAG_NO_MFMA | TMPC_FLAG_PROFILE | TMPC_FLAG_FAST_EXIT | TMPC_DEBUG_FLAG_STOP_ASSEMBLED | TMPC_DEBUG_FLAG_NO_LIFT | TMPC_DEBUG_FLAG_NO_DMA | TMPC_DEBUG_FLAG_GENERIC_STAGE)) {
+  if (flags & ~(TMPC_FLAG_NO_MFMA | TMPC_FLAG_PROFILE | TMPC_FLAG_FAST_EXIT | TMPC_DEBUG_FLAG_STOP_ASSEMBLED | TMPC_DEBUG_FLAG_NO_LIFT | TMPC_DEBUG_FLAG_NO_DMA | TMPC_DEBUG_FLAG_GENERIC_STAGE | TMPC_DEBUG_FLAG_GENERIC_ROWS)) {
     snprintf(g_err, sizeof(g_err), "tmpc_set_options: unknown flag bits 0x%x (TMPC_FLAG_NO_MFMA = 1, TMPC_FLAG_PROFILE = 2, TMPC_FLAG_FAST_EXIT = 4)", flags);
     return TMPC_E_ARG;
   }
@@ -1420,6 +1425,18 @@ int tmpc_debug_get_array(tmpc_handle* h, int which, uint64_t offset, uint64_t co
     case 39: src = ws.Wm; break;
     case 40: src = ws.eigmin; break;
     case 41: src = ws.TU; break;
+    case 42: src = h->lane[0].dG; break;       // the lane's staging of the rows (the workspace only holds a per-call pointer)
+    case 43: src = ws.corrp; break;
+    case 44: src = ws.at; break;
+    case 45: src = ws.adt; break;
+    case 46: src = ws.aX; break;
+    case 47: src = ws.adX; break;
+    case 48: src = ws.acor; break;
+    case 49: src = ws.aSi; break;
+    case 50: src = ws.aLi; break;
+    case 51: src = ws.aLXi; break;
+    case 52: src = ws.asum; break;
+    case 53: src = ws.prs; break;
     default: return TMPC_E_ARG;
   }
   if (!src) return TMPC_E_ARG;

@@ -164,6 +164,7 @@ constexpr int phi_pre_lds(bool bign, bool bigr) {
 // keep the four LDS slots.  Same arithmetic in the same order: at n <= 32 both forms return the same bits.
 // BIGR (handles with room for more than NRS = 32 rows per stage, up to 31 + 31): the per-row vectors stay in their place of pvec and the
 // Gram products in WS::prs (global memory) -- only T_loc,loc (64 x 129) and the arrow slots are in LDS.
+// The Gram products are summed per lane in the order of the wave reduction of the LDS form: a handle with room for more than NRS rows returns the bits of one without.
 template <bool BIGN, bool BIGR>
 __global__ void __launch_bounds__(64) k_phi_pre(WS w, Dims dm, int aug) {
   extern __shared__ __attribute__((aligned(16))) double sm[];
@@ -232,12 +233,25 @@ __global__ void __launch_bounds__(64) k_phi_pre(WS w, Dims dm, int aug) {
       double wu = (lane < n) ? wi[lane] * ui[lane] : 0.0;
       wu = wave_sum(wu);
       if (lane == 0) { cal[i] += hu; if (r == 1) ctl[i] = -wu; }
-      if (BIGR) {        // one lane per column j (up to 62 of them): a serial dot product each instead of 2 ng wave reductions per row
+      if (BIGR) {        // one lane per column j (up to 62 of them): a dot product each instead of 2 ng wave reductions per row -- summed in the ORDER of
+        // wave_sum (rounded products of the 64 lanes, zero beyond n, then the xor butterfly 32, 16, .. 1), so that this form returns the bits of the LDS form
         if (lane < ng) {
           const double* wj = WV(r, lane); const double* uj = UV(r, lane);
-          double x = 0.0, y = 0.0;
-          for (int c = 0; c < n; ++c) { const double g = mG[i * ldg + c]; x = fma(g, wj[c], x); y = fma(g, uj[c], y); }
-          GXG[(r * gs + i) * gs + lane] = x; GSG[(r * gs + i) * gs + lane] = y;
+          double px[32], py[32];
+#pragma unroll
+          for (int c = 0; c < 32; ++c) {
+            const double g0 = (c < n) ? mG[i * ldg + c] : 0.0, g1 = (c + 32 < n) ? mG[i * ldg + c + 32] : 0.0;
+            const double w0 = (c < n) ? wj[c] : 0.0, w1 = (c + 32 < n) ? wj[c + 32] : 0.0;
+            const double u0 = (c < n) ? uj[c] : 0.0, u1 = (c + 32 < n) ? uj[c + 32] : 0.0;
+            px[c] = __dadd_rn(__dmul_rn(g0, w0), __dmul_rn(g1, w1));
+            py[c] = __dadd_rn(__dmul_rn(g0, u0), __dmul_rn(g1, u1));
+          }
+#pragma unroll
+          for (int o = 16; o > 0; o >>= 1) {
+#pragma unroll
+            for (int c = 0; c < o; ++c) { px[c] = __dadd_rn(px[c], px[c + o]); py[c] = __dadd_rn(py[c], py[c + o]); }
+          }
+          GXG[(r * gs + i) * gs + lane] = px[0]; GSG[(r * gs + i) * gs + lane] = py[0];
         }
       } else
       for (int j = 0; j < ng; ++j) {
