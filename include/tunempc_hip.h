@@ -619,8 +619,8 @@ int tmpc_mpc_qp_gain_batch_device(int nb, int p, int nx, int mb, int nd, int ne,
  *     min  sum_{j<N} (1/2 z_j' H_k z_j + q_k' z_j),   z_j = [x_j; u_j],
  *     s.t. x_{j+1} = A_k x_j + B_k u_j + c_k,  j = 0 .. N-1,  x_N := x_0  (x_0 is a variable),
  *          D_k z_j <= d_k (first ndcnt_k rows of the stage),   J_k z_j = r_k (first necnt_k rows of the stage).
- * Not served (there are no arguments for them): soft and quadratic-slack rows, warm starts, a terminal cost (Pf has no meaning without an end), the
- * phase-fixing cost of pocp.py, nonlinear dynamics and the SQP outer loop.
+ * Soft and quadratic-slack rows: the tmpc_periodic_qp_soft_batch pair below.  Not served (there are no arguments for them): warm starts, a terminal cost
+ * (Pf has no meaning without an end), the phase-fixing cost of pocp.py, nonlinear dynamics and the SQP outer loop.
  * Method: the interior-point iteration of the MPC entries (hard rows, equality rows at the weight 1 / rho, Mehrotra's predictor-corrector, one step length,
  * the same stop rule: tmpc_periodic_qp.h and tests/periodic_qp_reference.py state the rules).  The multiplier of x_N = x_0 is a variable of the iteration; the
  * Newton system is the Riccati pass plus a border of nx columns and one symmetric quasi-definite system of size 2 nx per iteration.
@@ -654,6 +654,31 @@ int tmpc_periodic_qp_batch_device(int nb, int p, int nx, int mb, int nd, int ne,
                                   const double* offset, const double* D, const int32_t* ndcnt, const double* d, const double* J, const double* r,
                                   const int32_t* necnt, double tol, int max_iter, double* X, double* U, double* Lam, double* Nu, double* Pi, double* info,
                                   double* res);
+
+/* The periodic QP with soft and quadratic-slack rows (k_periodic_qp<true> of tmpc_periodic_qp.h): the arguments of the pair above plus
+ * penalty = c and penalty2 = Z, each [nb][p][nd] or NULL, read per row as the tmpc_mpc_qp_quad entries read them:
+ *     c = inf (Z = 0)  the hard row;            c > 0, Z = 0  D_i z - e <= d_i, e >= 0, cost c e (exact L1);
+ *     c > 0, Z > 0     cost c e + 1/2 Z e^2;    c = 0, Z > 0  cost 1/2 Z e^2, e = lam / Z (pure quadratic, one complementarity pair).
+ * penalty NULL with penalty2: every row is pure quadratic (c = 0); penalty2 NULL with penalty: Z = 0.  With both NULL the call runs the kernel of the pair
+ * above and writes its bits, with zeros in Eps, nviol, pcost and emax.  The slacks are eliminated per row (start values, weights, corrector terms, step length
+ * and stop rule are those of the MPC entries; the border of the periodic Newton system is unchanged).  A problem whose rows contradict each other and are all
+ * soft converges to the least-penalised violation instead of ending with status 1.
+ * Outputs beyond those of the pair above (each or NULL): Eps [nb][N][nd], the slack of every soft row (lam / Z on a pure row, 0 on hard and absent rows);
+ * nviol int32 [nb], over all N stages the two-pair rows with e > nu plus the pure rows with lam > s; res [nb][6] = (cost, hres, eres, per, pcost, emax):
+ * cost is the total and includes pcost = sum c e + 1/2 Z e^2, emax = max e, hres stays max(D z - d) and is positive when a row is violated.
+ * An invalid weight (c negative or NaN; Z negative or non-finite; Z != 0 on a hard row; c = 0 with Z = 0) gives that problem status 3 before its first
+ * iteration.  With status != 0 the floating-point outputs are NaN and nviol is -1.
+ * Workspace per slot: that of the pair above plus 8 (4 N nd) bytes.  LDS: that of the pair above plus 8 (4 nd) bytes (nx 24 / mb 8 / nd 16: 56656 bytes).
+ * TMPC_E_ARG as above, and a non-NULL penalty or penalty2 with nd = 0.  TMPC_E_UNSUPPORTED as above, with the byte count of the soft layout. */
+#define TMPC_PERIODIC_QP_SOFT_RES 6
+int tmpc_periodic_qp_soft_batch_host(int nb, int p, int nx, int mb, int nd, int ne, int periods, const double* A, const double* B, const double* H,
+                                     const double* q, const double* offset, const double* D, const int32_t* ndcnt, const double* d, const double* penalty,
+                                     const double* penalty2, const double* J, const double* r, const int32_t* necnt, double tol, int max_iter, double* X,
+                                     double* U, double* Lam, double* Eps, double* Nu, double* Pi, int32_t* nviol, double* info, double* res);
+int tmpc_periodic_qp_soft_batch_device(int nb, int p, int nx, int mb, int nd, int ne, int periods, const double* A, const double* B, const double* H,
+                                       const double* q, const double* offset, const double* D, const int32_t* ndcnt, const double* d, const double* penalty,
+                                       const double* penalty2, const double* J, const double* r, const int32_t* necnt, double tol, int max_iter, double* X,
+                                       double* U, double* Lam, double* Eps, double* Nu, double* Pi, int32_t* nviol, double* info, double* res);
 
 /* Accumulated hipEvent timings since the last call (ms) when TMPC_FLAG_PROFILE is set, 16 doubles:
  * out[0] stage_pre+ctrl, [1] schur assembly, [2] block factorisation (all kernels of tmpc_cr.h's factor phase), [3] predictor

@@ -29,7 +29,7 @@ EXPORTS = [
     'tmpc_mpc_qp_soft_batch_host', 'tmpc_mpc_qp_soft_batch_device', 'tmpc_mpc_qp_eq_batch_host', 'tmpc_mpc_qp_eq_batch_device',
     'tmpc_mpc_qp_aff_batch_host', 'tmpc_mpc_qp_aff_batch_device', 'tmpc_mpc_qp_quad_batch_host', 'tmpc_mpc_qp_quad_batch_device',
     'tmpc_mpc_qp_warm_batch_host', 'tmpc_mpc_qp_warm_batch_device', 'tmpc_mpc_qp_gain_batch_host', 'tmpc_mpc_qp_gain_batch_device',
-    'tmpc_periodic_qp_batch_host', 'tmpc_periodic_qp_batch_device',
+    'tmpc_periodic_qp_batch_host', 'tmpc_periodic_qp_batch_device', 'tmpc_periodic_qp_soft_batch_host', 'tmpc_periodic_qp_soft_batch_device',
     'tmpc_last_error', 'tmpc_version',
 ]
 # ... and in include/tunempc_hip_debug.h (unit-test / diagnostic entries)
@@ -189,6 +189,10 @@ def load_library():
     lib.tmpc_periodic_qp_batch_host.argtypes = [C.c_int] * 7 + [dp] * 6 + [ip, dp, dp, dp, ip, C.c_double, C.c_int] + [dp] * 7
     lib.tmpc_periodic_qp_batch_device.restype = C.c_int
     lib.tmpc_periodic_qp_batch_device.argtypes = [C.c_int] * 7 + [vp] * 11 + [C.c_double, C.c_int] + [vp] * 7
+    lib.tmpc_periodic_qp_soft_batch_host.restype = C.c_int
+    lib.tmpc_periodic_qp_soft_batch_host.argtypes = [C.c_int] * 7 + [dp] * 6 + [ip, dp, dp, dp, dp, dp, ip, C.c_double, C.c_int] + [dp] * 6 + [ip, dp, dp]
+    lib.tmpc_periodic_qp_soft_batch_device.restype = C.c_int
+    lib.tmpc_periodic_qp_soft_batch_device.argtypes = [C.c_int] * 7 + [vp] * 13 + [C.c_double, C.c_int] + [vp] * 9
     lib.tmpc_get_profile.restype = C.c_int
     lib.tmpc_get_profile.argtypes = [vp, dp]
     lib.tmpc_get_trace.restype = C.c_int
@@ -243,6 +247,7 @@ CLOSED_LOOP_INFO_STRIDE = 4
 MPC_QP_INFO_STRIDE = 8
 PERIODIC_QP_INFO_STRIDE = 8
 PERIODIC_QP_RES_STRIDE = 4
+PERIODIC_QP_SOFT_RES_STRIDE = 6
 
 
 def _check(lib, rc, what):
@@ -1222,3 +1227,35 @@ def periodic_qp_batch_host(*args):
 def periodic_qp_batch_device(*args):
     """tmpc_periodic_qp_batch_device on torch tensors of one GPU: _periodic_qp_call; the inputs never leave HBM."""
     return _periodic_qp_call(_DeviceArrays, *args)
+
+
+def _periodic_qp_soft_call(kind, A, B, H, q, offset, D, ndcnt, d, penalty, penalty2, J, r, necnt, periods, tol, max_iter):
+    """tmpc_periodic_qp_soft_batch_<host or device> on validated, contiguous arrays of `kind` (as _periodic_qp_call; penalty, penalty2 [nb,p,nd] or None) ->
+    dict X, U, lam, eps [nb,N,nd], nu, pi, nviol int32 [nb], info [nb,8], res [nb,6]."""
+    lib = load_library()
+    xp = kind(A)
+    name = 'tmpc_periodic_qp_soft_batch_%s' % xp.entry
+    nb, p, nx, mb = B.shape
+    nd = 0 if D is None else D.shape[2]
+    ne = 0 if J is None else J.shape[2]
+    N = int(periods) * p
+    X, U, Lam, Eps, Nu, Pi = xp.f64(nb, N, nx), xp.f64(nb, N, mb), xp.f64(nb, N, nd), xp.f64(nb, N, nd), xp.f64(nb, N, ne), xp.f64(nb, N, nx)
+    nviol, info, res = xp.i32(nb), xp.zeros(nb, PERIODIC_QP_INFO_STRIDE), xp.zeros(nb, PERIODIC_QP_SOFT_RES_STRIDE)
+    ptr = xp.ptr
+    args = [nb, p, nx, mb, nd, ne, int(periods)] + [ptr(a) for a in (A, B, H, q, offset, D, ndcnt, d, penalty, penalty2, J, r, necnt)]
+    args += [float(tol), int(max_iter)] + [ptr(a) for a in (X, U, Lam, Eps, Nu, Pi, nviol, info, res)]
+    rc = xp.call(getattr(lib, name), args)
+    if rc == -1:      # TMPC_E_ARG: the library's message names the argument
+        raise ValueError(lib.tmpc_last_error().decode())
+    _check_lqr(lib, rc, name)
+    return dict(X=X, U=U, lam=Lam, eps=Eps, nu=Nu, pi=Pi, nviol=nviol, info=info, res=res)
+
+
+def periodic_qp_soft_batch_host(*args):
+    """tmpc_periodic_qp_soft_batch_host on numpy arrays: _periodic_qp_soft_call."""
+    return _periodic_qp_soft_call(_HostArrays, *args)
+
+
+def periodic_qp_soft_batch_device(*args):
+    """tmpc_periodic_qp_soft_batch_device on torch tensors of one GPU: _periodic_qp_soft_call; the inputs never leave HBM."""
+    return _periodic_qp_soft_call(_DeviceArrays, *args)

@@ -2830,7 +2830,11 @@ int tmpc_mpc_qp_warm_batch_host(int nb, int p, int nx, int mb, int nd, int N, in
 // the workspace.  One record, one check, one launch; the host entry stages every array of the record through one device buffer.
 static_assert(PQ_INFO == TMPC_PERIODIC_QP_INFO && PQ_RES == TMPC_PERIODIC_QP_RES, "tunempc_hip.h: strides of the periodic QP entries");
 
-static int periodic_qp_check(const char* who, int nb, int periods, const PeriodicQpArgs& a) {
+static int periodic_qp_check(const char* who, int nb, int periods, const PeriodicQpArgs& a, bool soft = false) {
+  if (soft && a.nd == 0) {
+    snprintf(g_err, sizeof(g_err), "%s: bad argument (penalty and penalty2 describe the rows of D: both NULL when nd = 0)", who);
+    return TMPC_E_ARG;
+  }
   if (nb < 1 || a.p < 1 || a.nx < 1 || a.mb < 1 || periods < 1 || a.nd < 0 || a.ne < 0 || !a.A || !a.B || !a.H || !a.info) {
     snprintf(g_err, sizeof(g_err), "%s: bad argument (nb, p, nx, nu, periods >= 1, nd, ne >= 0, non-null A, B, H, info; got periods = %d, nd = %d, ne = %d)", who,
              periods, a.nd, a.ne);
@@ -2853,7 +2857,8 @@ static int periodic_qp_check(const char* who, int nb, int periods, const Periodi
     snprintf(g_err, sizeof(g_err), "%s: the periodic QP handles stage blocks up to nx + nu = %d (got %d)", who, LQR_NMAX, a.nx + a.mb);
     return TMPC_E_UNSUPPORTED;
   }
-  const long long bytes = (long long)periodic_qp_lds(a.nx, a.mb, a.nd < 65536 ? a.nd : 65536, a.ne < 65536 ? a.ne : 65536).total * (long long)sizeof(double);
+  const int ndc = a.nd < 65536 ? a.nd : 65536, nec = a.ne < 65536 ? a.ne : 65536;
+  const long long bytes = (long long)(soft ? periodic_qp_soft_lds(a.nx, a.mb, ndc, nec) : periodic_qp_lds(a.nx, a.mb, ndc, nec)).total * (long long)sizeof(double);
   if (bytes > LQR_LDS_BYTES) {
     snprintf(g_err, sizeof(g_err), "%s: nx = %d, nu = %d with room for %d rows and %d equality rows per stage needs %lld bytes of LDS (limit %d)", who, a.nx, a.mb,
              a.nd, a.ne, bytes, LQR_LDS_BYTES);
@@ -2875,12 +2880,12 @@ static int periodic_qp_launch(int nb, PeriodicQpArgs a) {
   if (slots * per > MQ_WS_CAP_BYTES) slots = MQ_WS_CAP_BYTES / per;
   if (slots < 1) slots = 1;
   HIPCHK(g_periodic_qp_ws.reserve((size_t)(slots * per)));
-  HIPCHK(hipFuncSetAttribute((const void*)k_periodic_qp, hipFuncAttributeMaxDynamicSharedMemorySize, LQR_LDS_BYTES));      // (the same value from every thread and call)
+  HIPCHK(hipFuncSetAttribute((const void*)k_periodic_qp<false>, hipFuncAttributeMaxDynamicSharedMemorySize, LQR_LDS_BYTES));      // (the same value from every thread and call)
   a.ws = (double*)g_periodic_qp_ws.p;
   a.nb = nb;
   a.lcw = 0;
   while ((1 << a.lcw) < a.nx + a.mb) ++a.lcw;
-  hipLaunchKernelGGL(k_periodic_qp, dim3((unsigned)slots), dim3(LQR_NT), (size_t)periodic_qp_lds(a.nx, a.mb, a.nd, a.ne).total * sizeof(double), 0, a);
+  hipLaunchKernelGGL(k_periodic_qp<false>, dim3((unsigned)slots), dim3(LQR_NT), (size_t)periodic_qp_lds(a.nx, a.mb, a.nd, a.ne).total * sizeof(double), 0, a);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(0));
   return TMPC_OK;
@@ -2938,6 +2943,91 @@ int tmpc_periodic_qp_batch_host(int nb, int p, int nx, int mb, int nd, int ne, i
   for (const Slot& s : slots) if (s.out && s.host && s.bytes) HIPCHK(hipMemcpy((void*)s.host, *s.dev, s.bytes, hipMemcpyDeviceToHost));
   return TMPC_OK;
 }
+
+// The soft entries (soft and quadratic-slack rows: k_periodic_qp<true>): the record above plus penalty, penalty2, Eps, nviol and the six fields of res.  With
+// neither penalty the launch is k_periodic_qp<false>, the kernel of the entries above: its four fields of res go to a strip behind the workspace and are
+// copied into the first four of six; Eps, nviol, pcost and emax are zero.
+static_assert(PQ_RES_SOFT == TMPC_PERIODIC_QP_SOFT_RES, "tunempc_hip.h: strides of the soft periodic QP entries");
+
+static int periodic_qp_soft_launch(int nb, PeriodicQpArgs a) {
+  const bool soft = a.pen || a.pen2;
+  const long long per = (soft ? periodic_qp_soft_ws_doubles(a.nx, a.mb, a.nd, a.ne, a.N) : periodic_qp_ws_doubles(a.nx, a.mb, a.nd, a.ne, a.N)) * 8;
+  long long slots = nb < MQ_SLOTS ? nb : MQ_SLOTS;
+  if (slots * per > MQ_WS_CAP_BYTES) slots = MQ_WS_CAP_BYTES / per;
+  if (slots < 1) slots = 1;
+  const size_t strip = !soft && a.res ? (size_t)nb * PQ_RES * 8 : 0;
+  HIPCHK(g_periodic_qp_ws.reserve((size_t)(slots * per) + strip));
+  a.ws = (double*)g_periodic_qp_ws.p;
+  a.nb = nb;
+  a.lcw = 0;
+  while ((1 << a.lcw) < a.nx + a.mb) ++a.lcw;
+  if (soft) {
+    HIPCHK(hipFuncSetAttribute((const void*)k_periodic_qp<true>, hipFuncAttributeMaxDynamicSharedMemorySize, LQR_LDS_BYTES));
+    hipLaunchKernelGGL(k_periodic_qp<true>, dim3((unsigned)slots), dim3(LQR_NT), (size_t)periodic_qp_soft_lds(a.nx, a.mb, a.nd, a.ne).total * sizeof(double), 0, a);
+    HIPCHK(hipGetLastError());
+  } else {
+    double* res6 = a.res;
+    if (a.Eps && a.nd > 0) HIPCHK(hipMemsetAsync(a.Eps, 0, (size_t)nb * a.N * a.nd * 8, 0));
+    if (a.nviol) HIPCHK(hipMemsetAsync(a.nviol, 0, (size_t)nb * sizeof(int), 0));
+    if (res6) { HIPCHK(hipMemsetAsync(res6, 0, (size_t)nb * PQ_RES_SOFT * 8, 0)); a.res = (double*)((char*)g_periodic_qp_ws.p + slots * per); }
+    HIPCHK(hipFuncSetAttribute((const void*)k_periodic_qp<false>, hipFuncAttributeMaxDynamicSharedMemorySize, LQR_LDS_BYTES));
+    hipLaunchKernelGGL(k_periodic_qp<false>, dim3((unsigned)slots), dim3(LQR_NT), (size_t)periodic_qp_lds(a.nx, a.mb, a.nd, a.ne).total * sizeof(double), 0, a);
+    HIPCHK(hipGetLastError());
+    if (res6) HIPCHK(hipMemcpy2DAsync(res6, PQ_RES_SOFT * 8, a.res, PQ_RES * 8, PQ_RES * 8, (size_t)nb, hipMemcpyDeviceToDevice, 0));
+  }
+  HIPCHK(hipStreamSynchronize(0));
+  return TMPC_OK;
+}
+
+#define PERIODIC_QP_SOFT_RECORD PERIODIC_QP_RECORD; a.pen = penalty; a.pen2 = penalty2; a.Eps = Eps; a.nviol = (int*)nviol
+
+int tmpc_periodic_qp_soft_batch_device(int nb, int p, int nx, int mb, int nd, int ne, int periods, const double* A, const double* B, const double* H,
+                                       const double* q, const double* offset, const double* D, const int32_t* ndcnt, const double* d, const double* penalty,
+                                       const double* penalty2, const double* J, const double* r, const int32_t* necnt, double tol, int max_iter, double* X,
+                                       double* U, double* Lam, double* Eps, double* Nu, double* Pi, int32_t* nviol, double* info, double* res) {
+  PERIODIC_QP_SOFT_RECORD;
+  const int rc = periodic_qp_check("tmpc_periodic_qp_soft_batch_device", nb, periods, a, penalty || penalty2);
+  if (rc != TMPC_OK) return rc;
+  return periodic_qp_soft_launch(nb, a);
+}
+
+int tmpc_periodic_qp_soft_batch_host(int nb, int p, int nx, int mb, int nd, int ne, int periods, const double* A, const double* B, const double* H,
+                                     const double* q, const double* offset, const double* D, const int32_t* ndcnt, const double* d, const double* penalty,
+                                     const double* penalty2, const double* J, const double* r, const int32_t* necnt, double tol, int max_iter, double* X,
+                                     double* U, double* Lam, double* Eps, double* Nu, double* Pi, int32_t* nviol, double* info, double* res) {
+  PERIODIC_QP_SOFT_RECORD;
+  const int rc = periodic_qp_check("tmpc_periodic_qp_soft_batch_host", nb, periods, a, penalty || penalty2);
+  if (rc != TMPC_OK) return rc;
+  const size_t n = (size_t)nx + mb, st = (size_t)nb * p, sn = (size_t)nb * a.N, i4 = sizeof(int32_t);
+  // every array of the record, inputs then outputs: (host pointer, field of the device record, bytes)
+  struct Slot { const void* host; const void** dev; size_t bytes; bool out; };
+  const Slot slots[] = {
+    {A, (const void**)&a.A, st * nx * nx * 8, false}, {B, (const void**)&a.B, st * nx * mb * 8, false}, {H, (const void**)&a.H, st * n * n * 8, false},
+    {q, (const void**)&a.q, st * n * 8, false}, {offset, (const void**)&a.c, st * nx * 8, false}, {D, (const void**)&a.D, st * nd * n * 8, false},
+    {ndcnt, (const void**)&a.ndcnt, st * i4, false}, {d, (const void**)&a.d, st * nd * 8, false}, {penalty, (const void**)&a.pen, st * nd * 8, false},
+    {penalty2, (const void**)&a.pen2, st * nd * 8, false}, {J, (const void**)&a.J, st * ne * n * 8, false}, {r, (const void**)&a.r, st * ne * 8, false},
+    {necnt, (const void**)&a.necnt, st * i4, false},
+    {X, (const void**)&a.X, sn * nx * 8, true}, {U, (const void**)&a.U, sn * mb * 8, true}, {Lam, (const void**)&a.Lam, sn * nd * 8, true},
+    {Eps, (const void**)&a.Eps, sn * nd * 8, true}, {Nu, (const void**)&a.Nu, sn * ne * 8, true}, {Pi, (const void**)&a.Pi, sn * nx * 8, true},
+    {nviol, (const void**)&a.nviol, (size_t)nb * i4, true}, {info, (const void**)&a.info, (size_t)nb * PQ_INFO * 8, true},
+    {res, (const void**)&a.res, (size_t)nb * PQ_RES_SOFT * 8, true}};
+  size_t total = 0;
+  for (const Slot& s : slots) if (s.host && s.bytes) total += (s.bytes + 7) & ~(size_t)7;
+  HIPCHK(g_periodic_qp_scratch.reserve(total + 8));
+  char* base = (char*)g_periodic_qp_scratch.p;
+  size_t off = 0;
+  for (const Slot& s : slots) {
+    if (!s.host || !s.bytes) { *s.dev = nullptr; continue; }
+    *s.dev = base + off;
+    if (!s.out) HIPCHK(hipMemcpy(base + off, s.host, s.bytes, hipMemcpyHostToDevice));
+    off += (s.bytes + 7) & ~(size_t)7;
+  }
+  const int rl = periodic_qp_soft_launch(nb, a);
+  if (rl != TMPC_OK) return rl;
+  for (const Slot& s : slots) if (s.out && s.host && s.bytes) HIPCHK(hipMemcpy((void*)s.host, *s.dev, s.bytes, hipMemcpyDeviceToHost));
+  return TMPC_OK;
+}
+#undef PERIODIC_QP_SOFT_RECORD
 #undef PERIODIC_QP_RECORD
 
 int tmpc_tracking_reference_host(tmpc_handle* h, int nstage, const double* Hc, const double* q, const double* wref,

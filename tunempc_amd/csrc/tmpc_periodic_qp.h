@@ -3,7 +3,8 @@
 //   min  sum_{j<N} (1/2 z_j' H_k z_j + q_k' z_j),   z_j = [x_j; u_j],
 //   s.t. x_{j+1} = A_k x_j + B_k u_j + c_k,  j = 0 .. N-1,  x_N := x_0  (x_0 is a variable),
 //        D_k z_j <= d_k (first ndcnt_k rows),   J_k z_j = r_k (first necnt_k rows).
-// Not served: soft and quadratic-slack rows, warm starts, a terminal cost (Pf has no meaning without an end), the phase-fixing cost of pocp.py.
+// Not served: warm starts, a terminal cost (Pf has no meaning without an end), the phase-fixing cost of pocp.py.  Soft and quadratic-slack rows are served
+// by the SOFT instantiation (below).
 //
 // Conventions: those stated at the top of tmpc_mpc_qp.h -- one 256-thread workgroup per problem, fp64 on the vector ALU, the whole interior-point loop in
 // one launch, the operands of a stage in LDS, per-stage factors and the iterate in a slot of a global workspace, min(nb, MQ_SLOTS) workgroups that loop over
@@ -40,6 +41,27 @@
 // Gy [mb x ldp] and PQ_NVEC vectors of ldp doubles, ldp = nx | 1; R0 lies where Pi_0 lay.  Two shapes, in bytes: nx 24 / nu 8 / nd 16 / ne 0: 56144;
 // nx 3 / nu 2 / nd 4 / ne 1: 2760.  Workspace per slot (periodic_qp_ws_doubles): the hard / EQ workspace with nt = 0, then GY [N][mb][nx] and PI [N][nx]
 // (PI[0] is pi_per, PI[j] the adjoint pi_j of the last pass 1).
+//
+// Soft and quadratic-slack rows (k_periodic_qp<true>; the reference's pocp.py carries slacked constraints, sys['g'] and the us variables).  The row kind is
+// read per row from c = penalty and Z = penalty2, as the QUAD instantiations of tmpc_mpc_qp.h read it (tests/periodic_qp_soft_reference.py states the same
+// rules on the dense problem):
+//   c = inf (Z = 0)  the hard row;      c > 0, Z = 0  exact L1 (D_i z - e <= d, e >= 0, cost c e);      c > 0, Z > 0  L1 + L2 (cost c e + 1/2 Z e^2, stationarity
+//   c + Z e - lam - nu = 0);      c = 0, Z > 0  pure quadratic, one pair, a hard row with the dual regularisation rho + 1 / Z, slack lam / Z.
+// Taken from the "Soft rows" and "Quadratic slack penalties" sections of tmpc_mpc_qp.h unchanged: the start values, r_in, the weights w and beta, the corrector
+// terms c1 / c2, dnu = Z de - dlam, mu and sigma over every pair once, the step length over s, lam, e, nu, the stop rule with max lam over lam alone.
+// Where they stand here: pass 1 block A (row residual, w, bsv), so block B (hp and the D' w D term of Hb) reads them as it read the hard ones; the corrector
+// (the COR column, C2 = c2 / nu or c2 / nut for the forward sweep); the forward sweep (dlam, ds, de, amin); the step and the start block.
+// The border is untouched: M, T, Gamma, Gy, phi, R0, W, R2 and border_solve see a soft row only through a row's weight and right-hand side.
+// Invalid weights (c negative or NaN; Z negative or non-finite; Z != 0 on a hard row; c = 0 with Z = 0) give status 3 before the first iteration.
+// Outputs: Eps [nb][N][nd] (e; lam / Z on a pure row; 0 on hard and absent rows), nviol [nb] (over all N stages the two-pair rows with e > nu plus the pure
+// rows with lam > s), res [nb][6] = cost, hres, eres, per, pcost, emax: pcost = sum c e + 1/2 Z e^2 over the reported slacks, cost includes it, emax is their
+// maximum, hres stays max(D z - d).  A failed problem returns NaN in the floating-point outputs and -1 in nviol.
+// LDS (periodic_qp_soft_lds): the order of mpc_qp_quad_eq_layout -- the hard layout, the vectors e, nu, c, Z of the stage [nd] each, the EQ part -- then the
+// border as above: 32 nd bytes more than periodic_qp_lds.  The soft layout of the two shapes above, in bytes: 56656 and 2888.  Workspace
+// (periodic_qp_soft_ws_doubles): E, NU, dE, C2 [N][nd] each after FAC, then NUe, REQ, GY, PI: 4 N nd doubles more; nx 24 / nu 8 / nd 16 / ne 0 / N 6: 4432
+// doubles, nx 3 / nu 2 / nd 4 / ne 1 / N 3: 238.
+// With SOFT = false the kernel is the one it was, statement by statement: every statement of SOFT stands behind `if (SOFT)` or is a value selected by it at
+// compile time; MQ_QUAD_BLOCK keeps the blocks of the rows with Z > 0 apart from the statements beside them.
 #pragma once
 #include "tmpc_mpc_qp.h"
 
@@ -47,6 +69,7 @@ namespace tmpc {
 
 constexpr int PQ_INFO = 8;                   // doubles of info per problem: the fields of MQ_INFO (TMPC_PERIODIC_QP_INFO)
 constexpr int PQ_RES = 4;                    // doubles of res per problem: cost, hres, eres, per (TMPC_PERIODIC_QP_RES)
+constexpr int PQ_RES_SOFT = 6;               // the soft entries: cost (pcost included), hres, eres, per, pcost, emax (TMPC_PERIODIC_QP_SOFT_RES)
 constexpr int PQ_NVEC = 10;                  // vector slots of the border (seven in use: pi_per, dpi, dx_0, a and phi of the predictor and of the corrector)
 
 struct PeriodicQpLds { MpcQpEqLds e; int ldp, oM, oT, oG, oGy, oBv, total; };      // offsets in doubles
@@ -65,6 +88,23 @@ __host__ __device__ inline long long periodic_qp_ws_doubles(int nx, int mb, int 
   return mpc_qp_eq_ws_doubles(nx, mb, nd, N, ne, 0, false) + (long long)N * mb * nx + (long long)N * nx;
 }
 
+// The SOFT instantiation: the layout of mpc_qp_quad_eq_layout (the hard layout, the vectors e, nu, c, Z of the stage [nd] each, then the EQ part), then the
+// border as above; the workspace of the soft EQ kernel (E, NU, dE, C2 [N][nd] each after FAC, then NUe, REQ), then GY and PI.
+__host__ __device__ inline PeriodicQpLds periodic_qp_soft_lds(int nx, int mb, int nd, int ne) {
+  PeriodicQpLds l;
+  l.e = mpc_qp_quad_eq_layout(nx, mb, nd, ne);
+  l.ldp = nx | 1;
+  const long long ldp = l.ldp, oM = l.e.total, oT = oM + nx * ldp, oG = oT + (long long)(nx + mb) * ldp, oGy = oG + nx * ldp, oBv = oGy + mb * ldp;
+  const long long total = oBv + PQ_NVEC * ldp;
+  const bool big = total > 0x7fffffffLL / 8;
+  l.oM = big ? 0 : (int)oM; l.oT = big ? 0 : (int)oT; l.oG = big ? 0 : (int)oG; l.oGy = big ? 0 : (int)oGy; l.oBv = big ? 0 : (int)oBv;
+  l.total = big ? 0x7fffffff / 8 : (int)total;
+  return l;
+}
+__host__ __device__ inline long long periodic_qp_soft_ws_doubles(int nx, int mb, int nd, int ne, int N) {
+  return mpc_qp_eq_ws_doubles(nx, mb, nd, N, ne, 0, true) + (long long)N * mb * nx + (long long)N * nx;
+}
+
 // A [nb][p][nx][nx], B [nb][p][nx][mb], H [nb][p][n][n]; each or null: q [nb][p][n], c [nb][p][nx], D [nb][p][nd][n] and d [nb][p][nd] (null when nd = 0),
 // ndcnt [nb][p] (null: all nd rows; clamped to 0 .. nd), J [nb][p][ne][n] (null when ne = 0), r [nb][p][ne] (null: zero), necnt [nb][p] (null: all ne rows;
 // clamped).  ws: gridDim.x slots of periodic_qp_ws_doubles.  Outputs: info [nb][8]; each or null: X [nb][N][nx], U [nb][N][mb], Lam [nb][N][nd],
@@ -76,16 +116,19 @@ struct PeriodicQpArgs {
   const double* A; const double* B; const double* H; const double* q; const double* c; const double* D; const int* ndcnt; const double* d;
   const double* J; const double* r; const int* necnt;
   double* ws; double* X; double* U; double* Lam; double* Nu; double* Pi; double* info; double* res;
+  const double* pen; const double* pen2; double* Eps; int* nviol;            // (SOFT) penalty, penalty2 [nb][p][nd] (one may be null), Eps [nb][N][nd], nviol [nb]; res [nb][6]
 };
 
-// grid: min(nb, MQ_SLOTS) workgroups.
+// grid: min(nb, MQ_SLOTS) workgroups.  SOFT: the instantiation with soft and quadratic-slack rows (the header comment); it reads pen, pen2 (one of them may
+// be null) and writes Eps, nviol and six fields of res.  Without SOFT the four are not read or written and res has four fields.
+template <bool SOFT>
 __global__ void __launch_bounds__(LQR_NT) k_periodic_qp(PeriodicQpArgs a) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
   const int p = a.p, nx = a.nx, mb = a.mb, nd = a.nd, ne = a.ne, N = a.N, lcw = a.lcw, max_iter = a.max_iter;
   const double tol = a.tol;
   const int n = nx + mb;
   const MpcQpLds Ly = mpc_qp_lds(nx, mb, nd);
-  const PeriodicQpLds Lp = periodic_qp_lds(nx, mb, nd, ne);
+  const PeriodicQpLds Lp = SOFT ? periodic_qp_soft_lds(nx, mb, nd, ne) : periodic_qp_lds(nx, mb, nd, ne);
   const int ld = Ly.ld, ldp = Ly.ldp, lv = Ly.lv;
   double* El = lds + Ly.oE; double* Pl = lds + Ly.oP; double* Wl = lds + Ly.oW; double* Hl = lds + Ly.oH; double* Dl = lds + Ly.oD; double* red = lds + Ly.oR;
   double* V = lds + Ly.oV;
@@ -101,14 +144,16 @@ __global__ void __launch_bounds__(LQR_NT) k_periodic_qp(PeriodicQpArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int cw = 1 << lcw, tx = tid & (cw - 1), ty = tid >> lcw, rs = LQR_NT >> lcw;
   const double qnan = __longlong_as_double(0x7ff8000000000000LL);
-  const long long wsn = periodic_qp_ws_doubles(nx, mb, nd, ne, N);
+  const long long wsn = SOFT ? periodic_qp_soft_ws_doubles(nx, mb, nd, ne, N) : periodic_qp_ws_doubles(nx, mb, nd, ne, N);
   double* ws = a.ws + (size_t)blockIdx.x * wsn;
   double* Z = ws; double* dZ = Z + (size_t)(N + 1) * n; double* Sg = dZ + (size_t)(N + 1) * n; double* Lg = Sg + (size_t)N * nd; double* dSg = Lg + (size_t)N * nd;
   double* dLg = dSg + (size_t)N * nd; double* RIN = dLg + (size_t)N * nd; double* COR = RIN + (size_t)N * nd; double* RDYN = COR + (size_t)N * nd;
   double* FAC = RDYN + (size_t)N * nx;
   const int fs = mb * (n + 1);                                               // doubles of [Y | R | y] per stage
-  double* NUe = ws + mpc_qp_ws_doubles(nx, mb, nd, N); double* REQ = NUe + (size_t)N * ne;
-  double* GY = ws + mpc_qp_eq_ws_doubles(nx, mb, nd, N, ne, 0, false); double* PI = GY + (size_t)N * mb * nx;
+  double* NUe = ws + (SOFT ? mpc_qp_soft_ws_doubles(nx, mb, nd, N) : mpc_qp_ws_doubles(nx, mb, nd, N)); double* REQ = NUe + (size_t)N * ne;
+  double* GY = ws + mpc_qp_eq_ws_doubles(nx, mb, nd, N, ne, 0, SOFT); double* PI = GY + (size_t)N * mb * nx;
+  double* Eg = FAC + (size_t)N * fs; double* NUg = Eg + (size_t)N * nd; double* dEg = NUg + (size_t)N * nd; double* C2g = dEg + (size_t)N * nd;   // (SOFT only)
+  double* ev = lds + Ly.total; double* nuv = ev + nd; double* cv = nuv + nd; double* zqv = cv + nd;                                            // (SOFT only)
 
   // dx_0 and dpi of the right-hand sides aa (a) and ph (phi) with R0 (in Pl), W (in Ml) and R2 (in Gl): triangular solves column by column inside one wave
   auto border_solve = [&](const double* aa, const double* ph) {
@@ -160,8 +205,25 @@ __global__ void __launch_bounds__(LQR_NT) k_periodic_qp(PeriodicQpArgs a) {
     const int* necnt = a.necnt ? a.necnt + (size_t)b * p : nullptr;
     auto erows_of = [&](int k) { return ne > 0 ? (necnt ? max(0, min(ne, necnt[k])) : ne) : 0; };
 
+    // (SOFT) c_of, z_of: penalty and penalty2 of row i of phase k (penalty absent: every row pure quadratic, c = 0; penalty2 absent: Z = 0)
+    const double* pen = SOFT && a.pen ? a.pen + (size_t)b * p * nd : nullptr; const double* pen2 = SOFT && a.pen2 ? a.pen2 + (size_t)b * p * nd : nullptr;
+    auto c_of = [&](int k, int i) { return pen ? pen[k * nd + i] : 0.0; };
+    auto z_of = [&](int k, int i) { return pen2 ? pen2[k * nd + i] : 0.0; };
+    // (SOFT) soft_at(e): entry e = j nd + i of the [N][nd] arrays is a row with two pairs; pure_at(e): a pure quadratic row (one pair); zq_at(e): its Z
+    auto soft_at = [&](int e) { const int j = e / nd, i = e - j * nd, k = j % p; return i < rows_of(k) && c_of(k, i) < INFINITY && c_of(k, i) > 0.0; };
+    auto pure_at = [&](int e) { const int j = e / nd, i = e - j * nd, k = j % p; return i < rows_of(k) && c_of(k, i) == 0.0; };
+    auto zq_at = [&](int e) { const int j = e / nd, i = e - j * nd; return z_of(j % p, i); };
+
     int status = MQ_OK, its = 0;
     double mu = 0.0, rp = 0.0, rd = 0.0, pivmin = INFINITY;
+    if (SOFT) {                                                              // an invalid weight: the problem ends before its first iteration
+      double bad = 0.0;
+      for (int e = tid; e < p * nd; e += LQR_NT) {                           // Z >= 0 and finite, 0 on a hard row; c > 0, or c = 0 with Z > 0
+        const double c = c_of(e / nd, e % nd), z = z_of(e / nd, e % nd);
+        if (!(z >= 0.0 && z < INFINITY) || !(c > 0.0 || (c == 0.0 && z > 0.0)) || (c == INFINITY && z != 0.0)) bad = 1.0;
+      }
+      if (mq_block<1>(bad, red, tid) > 0.0) status = MQ_NONFINITE;
+    }
     // ---- start: z = 0 including x_0, s = max(d, 1), lam = 1, nu = 0, pi_per = 0, no direction
     int mt = 0;
     for (int j = 0; j < N; ++j) mt += rows_of(j % p);
@@ -171,13 +233,27 @@ __global__ void __launch_bounds__(LQR_NT) k_periodic_qp(PeriodicQpArgs a) {
       const bool on = i < rows_of(k);
       Sg[e] = on ? fmax(dd[k * nd + i], 1.0) : 1.0; Lg[e] = on ? 1.0 : 0.0;
       dSg[e] = 0.0; dLg[e] = 0.0; RIN[e] = 0.0; COR[e] = 0.0;
+      if (SOFT) {                                                            // two pairs: lam = nu = (c + Z e) / 2, e = s; zero on the other rows (a pure row keeps lam = 1)
+        const bool sf = on && c_of(k, i) < INFINITY && c_of(k, i) > 0.0;
+        double hc = sf ? 0.5 * c_of(k, i) : 0.0;
+        if (sf && z_of(k, i) > 0.0) { MQ_QUAD_BLOCK; hc = 0.5 * (c_of(k, i) + z_of(k, i) * Sg[e]); }
+        if (sf) Lg[e] = hc;
+        NUg[e] = hc; Eg[e] = sf ? Sg[e] : 0.0; dEg[e] = 0.0; C2g[e] = 0.0;
+      }
     }
     for (int e = tid; e < N * ne; e += LQR_NT) { NUe[e] = 0.0; REQ[e] = 0.0; }
     for (int e = tid; e < N * nx; e += LQR_NT) PI[e] = 0.0;
+    int mp = mt;                                                             // complementarity pairs: one per row, one more per row with two pairs
+    if (SOFT) {
+      double cnt = 0.0;
+      for (int e = tid; e < N * nd; e += LQR_NT) if (soft_at(e)) cnt += 1.0;
+      mp = mt + (int)mq_block<0>(cnt, red, tid);
+    }
     __syncthreads();
 
     for (int it = 0;; ++it) {
       its = it;
+      if (SOFT) if (status != MQ_OK) break;                                  // (uniform: status is the same in every thread)
       // ================================================================== pass 1: residuals, factorisation and the border columns, j = N-1 .. 0
       if (tx < nx) for (int r = ty; r < nx; r += rs) { Pl[r * ldp + tx] = 0.0; Ml[r * ldp + tx] = r == tx ? 1.0 : 0.0; Gl[r * ldp + tx] = 0.0; }
       if (tid < nx) { const double v = PI[tid]; pip[tid] = v; pin[tid] = v; pv[tid] = v; phiv[tid] = 0.0; }
@@ -190,6 +266,7 @@ __global__ void __launch_bounds__(LQR_NT) k_periodic_qp(PeriodicQpArgs a) {
         if (tid < n) { zv[tid] = Z[(size_t)j * n + tid]; qv[tid] = q ? q[k * n + tid] : 0.0; }
         if (tid >= 64 && tid < 64 + nx) xn[tid - 64] = Z[(size_t)jn * n + tid - 64];
         for (int i = tid; i < m; i += LQR_NT) { lamv[i] = Lg[(size_t)j * nd + i]; sv[i] = Sg[(size_t)j * nd + i]; ddv[i] = dd[k * nd + i]; }
+        if (SOFT) for (int i = tid; i < m; i += LQR_NT) { ev[i] = Eg[(size_t)j * nd + i]; nuv[i] = NUg[(size_t)j * nd + i]; cv[i] = c_of(k, i); zqv[i] = z_of(k, i); }
         const int me = erows_of(k);
         if (tx < n) for (int i = ty; i < me; i += rs) Jl[i * ld + tx] = J[((size_t)k * ne + i) * n + tx];
         for (int i = tid; i < me; i += LQR_NT) { nuev[i] = NUe[(size_t)j * ne + i]; rrv[i] = rq ? rq[k * ne + i] : 0.0; }
@@ -198,9 +275,29 @@ __global__ void __launch_bounds__(LQR_NT) k_periodic_qp(PeriodicQpArgs a) {
         for (int e = tid; e < m + nx + n; e += LQR_NT) {
           if (e < m) {
             const double lam = lamv[e], s = sv[e];
-            const double r = mq_dot(Dl + e * ld, zv, n) + s - ddv[e];
-            const double w = lam / (s + MQ_RHO * lam);
-            rinv[e] = r; wv_[e] = w; bsv[e] = w * (r + MQ_RHO * lam);
+            double r = mq_dot(Dl + e * ld, zv, n) + s - ddv[e];
+            double w = lam / (s + MQ_RHO * lam);
+            double bs = w * (r + MQ_RHO * lam);
+            if (SOFT) if (cv[e] < INFINITY && cv[e] > 0.0) {                 // two pairs: lam + w beta of the predictor, beta = r_in - s + e
+              const double ee = ev[e];
+              r = mq_dot(Dl + e * ld, zv, n) - ee + s - ddv[e];
+              w = 1.0 / (s / lam + ee / nuv[e] + MQ_RHO);
+              bs = lam + w * (r - s + ee);
+            }
+            if (SOFT) if (cv[e] < INFINITY && cv[e] > 0.0 && zqv[e] > 0.0) { // L1 + L2: nut = nu + Z e, beta = r_in - s + e nu / nut
+              MQ_QUAD_BLOCK;
+              const double ee = ev[e], nut = nuv[e] + zqv[e] * ee;
+              w = 1.0 / (s / lam + ee / nut + MQ_RHO);
+              bs = lam + w * (r - s + ee * nuv[e] / nut);
+            }
+            if (SOFT) if (cv[e] == 0.0) {                                    // pure quadratic: the hard row with rho + 1 / Z, r_in = D z - lam / Z + s - d
+              MQ_QUAD_BLOCK;
+              const double zi = 1.0 / zqv[e], rz = MQ_RHO + zi;
+              r = mq_dot(Dl + e * ld, zv, n) - lam * zi + s - ddv[e];
+              w = lam / (s + rz * lam);
+              bs = w * (r + rz * lam);
+            }
+            rinv[e] = r; wv_[e] = w; bsv[e] = bs;
             RIN[(size_t)j * nd + e] = r;
             a_rp = cl_absmax(a_rp, r / fmax(1.0, fabs(ddv[e]))); a_lam = cl_absmax(a_lam, lam);
           } else if (e < m + nx) {
@@ -340,11 +437,12 @@ __global__ void __launch_bounds__(LQR_NT) k_periodic_qp(PeriodicQpArgs a) {
       // ---- the figures of the iterate and the stop test
       double part = 0.0;
       for (int e = tid; e < N * nd; e += LQR_NT) part = fma(Lg[e], Sg[e], part);
+      if (SOFT) for (int e = tid; e < N * nd; e += LQR_NT) if (soft_at(e)) part = fma(Eg[e], NUg[e], part);
       const double sumc = mq_block<0>(part, red, tid);
       const double xmax = mq_block<1>(a_x, red, tid), lmax = mq_block<1>(a_lam, red, tid), gmax = mq_block<1>(a_g, red, tid);
       rp = fmax(mq_block<1>(a_rp, red, tid), mq_block<1>(a_dyn, red, tid) / fmax(1.0, xmax));
       rd = mq_block<1>(a_rd, red, tid) / fmax(1.0, gmax);
-      mu = mt > 0 ? sumc / mt : 0.0;
+      mu = mt > 0 ? sumc / (SOFT ? mp : mt) : 0.0;
       if (!(rp < INFINITY && rd < INFINITY && fabs(mu) < INFINITY && lmax < INFINITY && xmax < INFINITY)) { status = MQ_NONFINITE; break; }
       if (rp <= tol && rd <= tol && mu <= MQ_MU_FACTOR * tol * fmax(1.0, lmax)) break;
       if (facfail) { status = MQ_NOT_CONVEX; break; }
@@ -416,11 +514,27 @@ __global__ void __launch_bounds__(LQR_NT) k_periodic_qp(PeriodicQpArgs a) {
           const double aa = fmin(1.0, alpha);
           part = 0.0;
           for (int e = tid; e < N * nd; e += LQR_NT) part = fma(Lg[e] + aa * dLg[e], Sg[e] + aa * dSg[e], part);
-          const double r3 = mq_block<0>(part, red, tid) / mt / mu;
+          if (SOFT) for (int e = tid; e < N * nd; e += LQR_NT) if (soft_at(e)) {
+            if (zq_at(e) > 0.0) { MQ_QUAD_BLOCK; part = fma(Eg[e] + aa * dEg[e], NUg[e] + aa * (zq_at(e) * dEg[e] - dLg[e]), part); }      // dnu = Z de - dlam
+            else part = fma(Eg[e] + aa * dEg[e], NUg[e] - aa * dLg[e], part);
+          }
+          const double r3 = mq_block<0>(part, red, tid) / (SOFT ? mp : mt) / mu;
           const double sigmu = r3 * r3 * r3 * mu;
           for (int e = tid; e < N * nd; e += LQR_NT) {
             const int j = e / nd, i = e - j * nd;
             COR[e] = i < rows_of(j % p) ? (sigmu - dSg[e] * dLg[e]) / (Sg[e] + MQ_RHO * Lg[e]) : 0.0;
+            if (SOFT) if (soft_at(e)) {                                      // w (c1 / lam - c2 / nu), and c2 / nu (C2) for the forward sweep
+              double c2 = (sigmu + dEg[e] * dLg[e]) / NUg[e];
+              COR[e] = ((sigmu - dSg[e] * dLg[e]) / Lg[e] - c2) / (Sg[e] / Lg[e] + Eg[e] / NUg[e] + MQ_RHO);
+              if (zq_at(e) > 0.0) {                                          // c2 = sigma mu - de_aff dnu_aff, over nut
+                MQ_QUAD_BLOCK;
+                const double z = zq_at(e), nut = NUg[e] + z * Eg[e];
+                c2 = (sigmu - dEg[e] * (z * dEg[e] - dLg[e])) / nut;
+                COR[e] = ((sigmu - dSg[e] * dLg[e]) / Lg[e] - c2) / (Sg[e] / Lg[e] + Eg[e] / nut + MQ_RHO);
+              }
+              C2g[e] = c2;
+            }
+            if (SOFT) if (pure_at(e)) { MQ_QUAD_BLOCK; COR[e] = (sigmu - dSg[e] * dLg[e]) / (Sg[e] + (MQ_RHO + 1.0 / zq_at(e)) * Lg[e]); }
           }
           if (tid < nx) { dxa[tid] = 0.0; phic[tid] = phiv[tid]; }           // dp_N = 0: dpi is carried by the border columns
           __syncthreads();
@@ -484,6 +598,7 @@ __global__ void __launch_bounds__(LQR_NT) k_periodic_qp(PeriodicQpArgs a) {
           for (int i = tid; i < m; i += LQR_NT) {
             lamv[i] = Lg[(size_t)j * nd + i]; sv[i] = Sg[(size_t)j * nd + i]; rinv[i] = RIN[(size_t)j * nd + i]; corv[i] = sweep ? COR[(size_t)j * nd + i] : 0.0;
           }
+          if (SOFT) for (int i = tid; i < m; i += LQR_NT) { ev[i] = Eg[(size_t)j * nd + i]; nuv[i] = NUg[(size_t)j * nd + i]; cv[i] = c_of(k, i); zqv[i] = z_of(k, i); }
           if (tid >= 64 && tid < 64 + nx) rdynv[tid - 64] = RDYN[(size_t)j * nx + tid - 64];
           __syncthreads();
           if (wave == 0) {                                                   // du = -R^-1 (Y dx + y + Gy dpi), column by column inside one wave
@@ -503,8 +618,36 @@ __global__ void __launch_bounds__(LQR_NT) k_periodic_qp(PeriodicQpArgs a) {
             if (e < m) {
               const double lam = lamv[e], s = sv[e], Dz = mq_dot(Dl + e * ld, dzv, n);
               const double w = lam / (s + MQ_RHO * lam);
-              const double dl = corv[e] - w * s + w * (rinv[e] + Dz);
-              const double ds = -rinv[e] - Dz + MQ_RHO * dl;
+              double dl = corv[e] - w * s + w * (rinv[e] + Dz);
+              double ds = -rinv[e] - Dz + MQ_RHO * dl;
+              if (SOFT) if (cv[e] < INFINITY && cv[e] > 0.0 && !(zqv[e] > 0.0)) {      // L1: de = -e + c2 / nu + (e / nu) dlam, dnu = -dlam
+                const double ee = ev[e], nu = nuv[e];
+                const double ws_ = 1.0 / (s / lam + ee / nu + MQ_RHO);
+                dl = corv[e] + ws_ * (rinv[e] - s + ee + Dz);
+                const double de = -ee + (sweep ? C2g[(size_t)j * nd + e] : 0.0) + (ee / nu) * dl;
+                ds = -rinv[e] - Dz + de + MQ_RHO * dl;
+                dEg[(size_t)j * nd + e] = de;
+                if (de < 0.0) amin = fmin(amin, -ee / de);
+                if (dl > 0.0) amin = fmin(amin, nu / dl);
+              }
+              if (SOFT) if (cv[e] < INFINITY && cv[e] > 0.0 && zqv[e] > 0.0) {         // L1 + L2: de = (c2 - e nu + e dlam) / nut, dnu = Z de - dlam
+                MQ_QUAD_BLOCK;
+                const double ee = ev[e], nu = nuv[e], nut = nu + zqv[e] * ee, enu = ee * nu / nut;
+                const double ws_ = 1.0 / (s / lam + ee / nut + MQ_RHO);
+                dl = corv[e] + ws_ * (rinv[e] - s + enu + Dz);
+                const double de = -enu + (sweep ? C2g[(size_t)j * nd + e] : 0.0) + (ee / nut) * dl;
+                ds = -rinv[e] - Dz + de + MQ_RHO * dl;
+                dEg[(size_t)j * nd + e] = de;
+                const double dnu = zqv[e] * de - dl;
+                if (de < 0.0) amin = fmin(amin, -ee / de);
+                if (dnu < 0.0) amin = fmin(amin, -nu / dnu);
+              }
+              if (SOFT) if (cv[e] == 0.0) {                                  // pure quadratic: the hard row with rho + 1 / Z
+                MQ_QUAD_BLOCK;
+                const double rz = MQ_RHO + 1.0 / zqv[e], wz = lam / (s + rz * lam);
+                dl = corv[e] - wz * s + wz * (rinv[e] + Dz);
+                ds = -rinv[e] - Dz + rz * dl;
+              }
               dLg[(size_t)j * nd + e] = dl; dSg[(size_t)j * nd + e] = ds;
               if (ds < 0.0) amin = fmin(amin, -s / ds);
               if (dl < 0.0) amin = fmin(amin, -lam / dl);
@@ -522,6 +665,10 @@ __global__ void __launch_bounds__(LQR_NT) k_periodic_qp(PeriodicQpArgs a) {
       // ==================================================================== the step
       const double al = fmin(1.0, MQ_STEP_BACK * alpha);
       for (int e = tid; e < N * n; e += LQR_NT) Z[e] = fma(al, dZ[e], Z[e]);
+      if (SOFT) for (int e = tid; e < N * nd; e += LQR_NT) if (soft_at(e)) {
+        if (zq_at(e) > 0.0) { MQ_QUAD_BLOCK; NUg[e] = fma(al, zq_at(e) * dEg[e] - dLg[e], NUg[e]); Eg[e] = fma(al, dEg[e], Eg[e]); }
+        else { Eg[e] = fma(al, dEg[e], Eg[e]); NUg[e] = fma(-al, dLg[e], NUg[e]); }
+      }
       for (int e = tid; e < N * nd; e += LQR_NT) { Sg[e] = fma(al, dSg[e], Sg[e]); Lg[e] = fma(al, dLg[e], Lg[e]); }
       for (int e = tid; e < N * ne; e += LQR_NT) NUe[e] = fma(al, REQ[e], NUe[e]);
       if (tid < nx) PI[tid] = fma(al, dpi[tid], PI[tid]);
@@ -532,6 +679,8 @@ __global__ void __launch_bounds__(LQR_NT) k_periodic_qp(PeriodicQpArgs a) {
     __syncthreads();
     const bool ok = status == MQ_OK;
     double cost = qnan, hres = qnan, eres = qnan, per = qnan;
+    double pcost = qnan, emax = qnan;                                        // (SOFT)
+    int nviol = -1;                                                          // (SOFT)
     if (ok) {
       double csum = 0.0, hmax = -INFINITY, em = 0.0, pm = 0.0;
       for (int j = 0; j < N; ++j) {
@@ -548,7 +697,22 @@ __global__ void __launch_bounds__(LQR_NT) k_periodic_qp(PeriodicQpArgs a) {
         __syncthreads();
       }
       cost = mq_block<0>(csum, red, tid); hres = mq_block<1>(hmax, red, tid); eres = mq_block<1>(em, red, tid); per = mq_block<1>(pm, red, tid);
+      if (SOFT) {                                                            // the slacks: e (lam / Z on a pure row), their cost c e + 1/2 Z e^2, the violated rows
+        double pc = 0.0, emx = 0.0, cnt = 0.0;
+        for (int e = tid; e < N * nd; e += LQR_NT) {
+          const int j = e / nd, i = e - j * nd, k = j % p;
+          double ee = 0.0;
+          if (soft_at(e)) { ee = Eg[e]; if (Eg[e] > NUg[e]) cnt += 1.0; }
+          if (pure_at(e)) { ee = Lg[e] / z_of(k, i); if (Lg[e] > Sg[e]) cnt += 1.0; }
+          if (soft_at(e) || pure_at(e)) pc += c_of(k, i) * ee + 0.5 * z_of(k, i) * ee * ee;
+          emx = fmax(emx, ee);
+          if (a.Eps) a.Eps[(size_t)b * N * nd + e] = ee;
+        }
+        pcost = mq_block<0>(pc, red, tid); emax = mq_block<1>(emx, red, tid); nviol = (int)mq_block<0>(cnt, red, tid);
+        cost = cost + pcost;
+      }
     }
+    if (SOFT) if (!ok) if (a.Eps) for (int e = tid; e < N * nd; e += LQR_NT) a.Eps[(size_t)b * N * nd + e] = qnan;
     const size_t bb = (size_t)b;
     if (a.X) for (int e = tid; e < N * nx; e += LQR_NT) { const int j = e / nx; a.X[bb * N * nx + e] = ok ? Z[(size_t)j * n + e - j * nx] : qnan; }
     if (a.U) for (int e = tid; e < N * mb; e += LQR_NT) { const int j = e / mb; a.U[bb * N * mb + e] = ok ? Z[(size_t)j * n + nx + e - j * mb] : qnan; }
@@ -558,7 +722,11 @@ __global__ void __launch_bounds__(LQR_NT) k_periodic_qp(PeriodicQpArgs a) {
     if (tid == 0) {
       double* o = a.info + bb * PQ_INFO;
       o[0] = status; o[1] = ok ? 1.0 : 0.0; o[2] = its; o[3] = its; o[4] = mu; o[5] = rp; o[6] = rd; o[7] = pivmin;
-      if (a.res) { double* r = a.res + bb * PQ_RES; r[0] = cost; r[1] = hres; r[2] = eres; r[3] = per; }
+      if (!SOFT) if (a.res) { double* r = a.res + bb * PQ_RES; r[0] = cost; r[1] = hres; r[2] = eres; r[3] = per; }
+      if (SOFT) {
+        if (a.res) { double* r = a.res + bb * PQ_RES_SOFT; r[0] = cost; r[1] = hres; r[2] = eres; r[3] = per; r[4] = pcost; r[5] = emax; }
+        if (a.nviol) a.nviol[bb] = nviol;
+      }
     }
     __syncthreads();
   }

@@ -7,14 +7,21 @@ N = periods p and k_j = j mod p,
     s.t.  x_{j+1} = A_k x_j + B_k u_j + c_k,  j = 0 .. N-1,  x_N := x_0  (x_0 is a variable),
           D_k z_j <= d_k (first ndcnt_k rows),   J_k z_j = r_k (first necnt_k rows).
 
-q, c (offset), d, r make the answer non-zero; each is optional.  Rows are hard.
+q, c (offset), d, r make the answer non-zero; each is optional.  Rows are hard unless penalty= (c) or penalty2= (Z) is given; then row i of stage k is read
+as the MPC step reads it (tunempc_amd.mpc_qp, the reference's slacked constraints sys['g'] / us of pocp.py):
 
-Not served: soft rows (penalty), quadratic slack penalties (penalty2), warm starts (guess), a terminal cost (Pf has no meaning without an end): these
-keywords are refused with a ValueError.  Neither are the SQP outer loop, nonlinear dynamics or the phase-fixing cost of pocp.py.
+    c = inf (Z = 0)  hard;    c > 0, Z = 0  D_i z - e <= d_i, e >= 0, cost c e (exact L1: the hard orbit while c exceeds the row's multiplier);
+    c > 0, Z > 0     cost c e + 1/2 Z e^2;    c = 0, Z > 0  cost 1/2 Z e^2 (pure quadratic).
+penalty2 without penalty: every row pure quadratic; penalty without penalty2: Z = 0.  A periodic problem whose bounds cannot all be met then returns the
+least-penalised orbit instead of status 1 and NaN.  The weights are checked on the device, problem by problem: an invalid one (c negative or NaN, Z negative
+or non-finite, Z != 0 on a hard row, c = 0 with Z = 0) gives that member status 3 and leaves the others alone.
+
+Not served: warm starts (guess), a terminal cost (Pf has no meaning without an end): these keywords are refused with a ValueError.  Neither are the SQP
+outer loop, nonlinear dynamics or the phase-fixing cost of pocp.py.
 
     periodic_qp_batch(A, B, H, ...)     the batch entry, numpy or torch (device tensors never leave the GPU)
     periodic_qp(A, B, Q, R, N, ...)     one model in the reference's calling style -> xref, uref as lists
-    lds_bytes(nx, nu, nd, ne)           the LDS layout of the header restated
+    lds_bytes(nx, nu, nd, ne, soft)     the LDS layout of the header restated (soft: the layout of a call with penalty or penalty2)
 
 Statuses are those of the MPC step: 0 Converged, 1 MaxIter, 2 NotConvex (also: no unique periodic trajectory, e.g. A = I, B = 0, c != 0), 3 NonFinite.  A
 problem that does not converge returns NaN in its outputs; it never returns status 0.
@@ -31,32 +38,37 @@ STATUS_NAMES = _mq.STATUS_NAMES
 LDS_BYTES = _mq.LDS_BYTES
 TOL, MAX_ITER = _mq.TOL, _mq.MAX_ITER
 INFO_FIELDS = _mq.INFO_FIELDS
-REFUSED_KEYWORDS = ('penalty', 'penalty2', 'Pf', 'guess')
+REFUSED_KEYWORDS = ('Pf', 'guess')
 
 
-def lds_bytes(nx, nu, nd=0, ne=0):
+def lds_bytes(nx, nu, nd=0, ne=0, soft=False):
     """periodic_qp_lds of csrc/tmpc_periodic_qp.h restated: the bytes of LDS of a workgroup -- the hard / EQ layout of the MPC step (nt = 0), then M [nx x ldp],
-    T [n x ldp], Gamma [nx x ldp], Gy [nu x ldp] and 10 vectors of ldp doubles, ldp = nx | 1."""
+    T [n x ldp], Gamma [nx x ldp], Gy [nu x ldp] and 10 vectors of ldp doubles, ldp = nx | 1.  soft: periodic_qp_soft_lds, the vectors e, nu, c, Z of the
+    stage [nd] each after the hard layout (32 nd bytes more)."""
     nx, nu, nd, ne = int(nx), int(nu), int(nd), int(ne)
     ldp = nx | 1
-    return _mq.lds_layout(nx, nu, nd, ne=ne)['bytes'] + 8 * ldp * (2 * nx + (nx + nu) + nu + 10)
+    return _mq.lds_layout(nx, nu, nd, ne=ne)['bytes'] + 8 * ldp * (2 * nx + (nx + nu) + nu + 10) + (32 * nd if soft else 0)
 
 
-def ws_doubles(nx, nu, nd, ne, N):
-    """periodic_qp_ws_doubles restated: doubles of workspace per slot."""
-    return _mq.lds_layout(nx, nu, nd, ne=ne)['ws_doubles'](N) + N * nu * nx + N * nx
+def ws_doubles(nx, nu, nd, ne, N, soft=False):
+    """periodic_qp_ws_doubles restated: doubles of workspace per slot.  soft: periodic_qp_soft_ws_doubles, E, NU, dE, C2 [N][nd] more."""
+    return _mq.lds_layout(nx, nu, nd, ne=ne)['ws_doubles'](N) + N * nu * nx + N * nx + (4 * int(N) * int(nd) if soft else 0)
 
 
 def _refuse(who, extra):
     bad = [k for k in REFUSED_KEYWORDS if k in extra]
     if bad:
-        raise ValueError('{}: {} not served by the periodic QP (rows are hard, every start is cold, there is no terminal cost)'.format(who, ', '.join(bad)))
+        raise ValueError('{}: {} not served by the periodic QP (every start is cold, there is no terminal cost)'.format(who, ', '.join(bad)))
     if extra:
         raise TypeError('{}() got an unexpected keyword argument {!r}'.format(who, sorted(extra)[0]))
 
 
-def _validate(who, A, B, H, q, offset, D, d, ndcnt, J, r, necnt, periods, tol, max_iter):
-    named = [('A', A), ('B', B), ('H', H)] + [(nm, x) for nm, x in (('q', q), ('offset', offset), ('D', D), ('d', d), ('J', J), ('r', r)) if x is not None]
+def _validate(who, A, B, H, q, offset, D, d, ndcnt, J, r, necnt, periods, tol, max_iter, penalty=None, penalty2=None):
+    named = [('A', A), ('B', B), ('H', H)] + [(nm, x) for nm, x in (('q', q), ('offset', offset), ('D', D), ('d', d), ('J', J), ('r', r), ('penalty', penalty),
+                                                                     ('penalty2', penalty2)) if x is not None]
+    for nm, x in (('penalty', penalty), ('penalty2', penalty2)):
+        if x is not None and not hasattr(x, 'shape'):
+            raise ValueError('{}: {} must be an fp64 array [nb, p, nd] of the kind of A'.format(who, nm))
     use_torch = _cl._check_kind(who, named)
     if len(A.shape) != 4 or A.shape[2] != A.shape[3]:
         raise ValueError('{}: A [nb, p, nx, nx] expected, got {}'.format(who, tuple(A.shape)))
@@ -81,6 +93,9 @@ def _validate(who, A, B, H, q, offset, D, d, ndcnt, J, r, necnt, periods, tol, m
         raise ValueError('{}: {} describes the rows of J, which is None'.format(who, 'r' if r is not None else 'necnt'))
     if D is None and ndcnt is not None:
         raise ValueError('{}: ndcnt describes the rows of D, which is None'.format(who))
+    for nm, x in (('penalty', penalty), ('penalty2', penalty2)):
+        if D is None and x is not None:
+            raise ValueError('{}: {} describes the rows of D, which is None'.format(who, nm))
 
     def counts(nm, cnt, cap):
         if not hasattr(cnt, 'shape') or lqr._is_torch(cnt) != use_torch:
@@ -101,6 +116,9 @@ def _validate(who, A, B, H, q, offset, D, d, ndcnt, J, r, necnt, periods, tol, m
             raise ValueError('{}: d {} expected, got {}'.format(who, (nb, p, nd), tuple(d.shape)))
         if ndcnt is not None:
             counts('ndcnt', ndcnt, nd)
+        for nm, x in (('penalty', penalty), ('penalty2', penalty2)):
+            if x is not None and tuple(x.shape) != (nb, p, nd):
+                raise ValueError('{}: {} {} expected, got {}'.format(who, nm, (nb, p, nd), tuple(x.shape)))
     if J is not None:
         if len(J.shape) != 4 or tuple(J.shape[:2]) != (nb, p) or int(J.shape[3]) != n or int(J.shape[2]) < 1:
             raise ValueError('{}: J [nb, p, ne, nx + nu] = [{}, {}, ne >= 1, {}] expected, got {}'.format(who, nb, p, n, tuple(J.shape)))
@@ -115,14 +133,16 @@ def _validate(who, A, B, H, q, offset, D, d, ndcnt, J, r, necnt, periods, tol, m
         raise ValueError('{}: max_iter must be an int >= 1, got {!r}'.format(who, max_iter))
     if n > 64:
         raise NotImplementedError('{}: the periodic QP handles stage blocks up to nx + nu = 64 (got {})'.format(who, n))
-    need = lds_bytes(nx, nu, nd, ne)
+    soft = penalty is not None or penalty2 is not None
+    need = lds_bytes(nx, nu, nd, ne, soft)
     if need > LDS_BYTES:
-        raise NotImplementedError('{}: nx = {}, nu = {} with room for {} rows and {} equality rows per stage needs {} bytes of LDS (limit {})'.format(
-            who, nx, nu, nd, ne, need, LDS_BYTES))
+        raise NotImplementedError('{}: nx = {}, nu = {} with room for {} {}rows and {} equality rows per stage needs {} bytes of LDS (limit {})'.format(
+            who, nx, nu, nd, 'soft ' if soft else '', ne, need, LDS_BYTES))
     return use_torch
 
 
-def periodic_qp_batch(A, B, H, q=None, offset=None, D=None, d=None, ndcnt=None, J=None, r=None, necnt=None, periods=1, tol=TOL, max_iter=MAX_ITER, **refused):
+def periodic_qp_batch(A, B, H, q=None, offset=None, D=None, d=None, ndcnt=None, J=None, r=None, necnt=None, periods=1, tol=TOL, max_iter=MAX_ITER, penalty=None,
+                      penalty2=None, **refused):
     """The periodic QP of the module docstring for nb problems in one launch.  A [nb,p,nx,nx], B [nb,p,nx,nu], H [nb,p,n,n] (used as (H + H') / 2); optional
     q [nb,p,n], offset c [nb,p,nx], D [nb,p,nd,n] with d [nb,p,nd] and ndcnt int32 [nb,p] (None: all nd rows), J [nb,p,ne,n] with r [nb,p,ne] (None: zero) and
     necnt int32 [nb,p]; periods: the horizon is N = periods p.  numpy arrays (staged through device buffers) or torch fp64 tensors of one GPU (the device entry:
@@ -132,14 +152,24 @@ def periodic_qp_batch(A, B, H, q=None, offset=None, D=None, d=None, ndcnt=None, 
         cost [nb], status int32 [nb], iters int32 [nb], the info fields by name (status .. pivmin as float [nb]; steps is 1 on success),
         hres = max(D z - d) over all stages (-inf without rows), eres = max|J z - r|, per = max|A x_{N-1} + B u_{N-1} + c - x_0|   [nb] each.
     X[:, :p], U[:, :p] are what tunempc_amd.mpc_qp.about_reference takes as xref, uref (with periods = 1: X, U themselves).
-    penalty, penalty2, Pf and guess are refused with a ValueError (Not served, module docstring); shapes beyond the LDS layout raise NotImplementedError
-    before the library is touched."""
+    penalty, penalty2 [nb,p,nd] fp64 of the kind of A (module docstring: the row kinds; one of them may be None): with either the call goes through the soft
+    entry and the dict gains eps [nb,N,nd] (the slack of every soft row, lam / Z on a pure quadratic row, 0 on hard and absent rows), nviol int32 [nb] (over
+    all stages the two-pair rows with e > nu plus the pure rows with lam > s; -1 on a failed member), pcost [nb] (sum c e + 1/2 Z e^2; cost includes it) and
+    emax [nb] (max e); hres stays max(D z - d), positive when a row is violated.  An invalid weight gives that member status 3.  Without them the call is
+    the hard one, through the hard entry, and returns the keys above only.
+    Pf and guess are refused with a ValueError (Not served, module docstring); shapes beyond the LDS layout (with a penalty: the soft layout) raise
+    NotImplementedError before the library is touched."""
     who = 'periodic_qp_batch'
     _refuse(who, refused)
-    use_torch = _validate(who, A, B, H, q, offset, D, d, ndcnt, J, r, necnt, periods, tol, max_iter)
+    use_torch = _validate(who, A, B, H, q, offset, D, d, ndcnt, J, r, necnt, periods, tol, max_iter, penalty, penalty2)
     cont = (lambda x: None if x is None else x.contiguous()) if use_torch else (lambda x: None if x is None else np.ascontiguousarray(x))
-    args = [cont(x) for x in (A, B, H, q, offset, D, ndcnt, d, J, r, necnt)]
-    fn = _lib.periodic_qp_batch_device if use_torch else _lib.periodic_qp_batch_host
+    soft = penalty is not None or penalty2 is not None
+    if soft:
+        args = [cont(x) for x in (A, B, H, q, offset, D, ndcnt, d, penalty, penalty2, J, r, necnt)]
+        fn = _lib.periodic_qp_soft_batch_device if use_torch else _lib.periodic_qp_soft_batch_host
+    else:
+        args = [cont(x) for x in (A, B, H, q, offset, D, ndcnt, d, J, r, necnt)]
+        fn = _lib.periodic_qp_batch_device if use_torch else _lib.periodic_qp_batch_host
     out = fn(*args, int(periods), float(tol), int(max_iter))
     info, res = out.pop('info'), out.pop('res')
     for i, nm in enumerate(INFO_FIELDS):
@@ -150,18 +180,29 @@ def periodic_qp_batch(A, B, H, q=None, offset=None, D=None, d=None, ndcnt=None, 
     else:
         out['status'] = info[:, 0].astype(np.int32); out['iters'] = info[:, 2].astype(np.int32)
     out.update(cost=res[:, 0], hres=res[:, 1], eres=res[:, 2], per=res[:, 3])
+    if soft:
+        out.update(pcost=res[:, 4], emax=res[:, 5])
     return out
 
 
-def periodic_qp(A, B, Q, R, N, q=None, offset=None, D=None, d=None, J=None, r=None, periods=1, tol=TOL, max_iter=MAX_ITER, **refused):
+def periodic_qp(A, B, Q, R, N, q=None, offset=None, D=None, d=None, J=None, r=None, periods=1, tol=TOL, max_iter=MAX_ITER, penalty=None, penalty2=None, **refused):
     """The periodic QP of one model in the reference's calling style: A, B, Q, R, N (the cross term) single matrices (p = 1) or lists of length p as in
     mpc_step; q, offset one vector or a list of p; D, d and J, r single arrays or ragged lists of p (None entries: no rows at that stage; r None: zero).
     Returns (xref, uref, info): xref, uref lists of periods p arrays (x_0 .. x_{N-1}, u_0 .. u_{N-1}), info a dict with X, U, lam, nu, pi, cost, status,
     iters, hres, eres, per and the info fields of periodic_qp_batch for this problem.  xref[:p], uref[:p] stacked are the xref, uref of
-    tunempc_amd.mpc_qp.about_reference.  RuntimeError when the solve did not converge (no periodic trajectory, contradictory rows, not convex)."""
+    tunempc_amd.mpc_qp.about_reference.  penalty, penalty2: the weights of the soft rows as mpc_step takes them -- one vector (every stage) or a ragged list
+    of p vectors with one entry per row of D_k (None stages and np.inf entries are hard; penalty2 without penalty: the rows with Z > 0 are pure quadratic, the
+    others hard) -- or one scalar for every row; info then gains eps, nviol, pcost, emax.  RuntimeError when the solve did not converge (no periodic
+    trajectory, contradictory hard rows, not convex)."""
     who = 'periodic_qp'
     _refuse(who, refused)
-    As, Bs, Hs, _, kw = _mq._stack_one(who, A, B, Q, R, N, np.zeros(np.atleast_2d(_to_array(A[0] if isinstance(A, (list, tuple)) else A)).shape[0]), D, d, q, None)
+
+    def rowwise(w):      # a scalar weight: that weight on every row of every stage
+        if w is None or D is None or isinstance(w, (list, tuple)) or np.ndim(w) != 0:
+            return w
+        return [None if m is None else np.full(np.atleast_2d(_to_array(m)).shape[0], float(w)) for m in (D if isinstance(D, (list, tuple)) else [D] * len(A if isinstance(A, (list, tuple)) else [A]))]
+    As, Bs, Hs, _, kw = _mq._stack_one(who, A, B, Q, R, N, np.zeros(np.atleast_2d(_to_array(A[0] if isinstance(A, (list, tuple)) else A)).shape[0]), D, d, q, None,
+                                       rowwise(penalty), rowwise(penalty2))
     p, nx, nu = As.shape[1], As.shape[2], Bs.shape[3]
     eq = _mq._stack_eq(who, p, nx, nx + nu, J, r, None)
     cs = None
@@ -171,7 +212,7 @@ def periodic_qp(A, B, Q, R, N, q=None, offset=None, D=None, d=None, J=None, r=No
             raise ValueError('{}: offset must be one vector of nx = {} entries or a list of p = {} of them'.format(who, nx, p))
         cs = np.ascontiguousarray(np.stack(cl)[None])
     res = periodic_qp_batch(As, Bs, Hs, q=kw['q'], offset=cs, D=kw['D'], d=kw['d'], ndcnt=kw['ndcnt'], J=eq['J'], r=eq['r'], necnt=eq['necnt'], periods=periods,
-                            tol=tol, max_iter=max_iter)
+                            tol=tol, max_iter=max_iter, **{k: kw[k] for k in ('penalty', 'penalty2') if kw.get(k) is not None})
     st = int(res['status'][0])
     if st != 0:
         raise RuntimeError('{}: the solve ended with status {} ({}) after {} iterations'.format(who, st, STATUS_NAMES.get(st), int(res['iters'][0])))
