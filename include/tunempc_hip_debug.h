@@ -15,7 +15,7 @@ extern "C" {
 #endif
 
 /* Debug bit for tmpc_set_options(flags): the solve stops after ASSEMBLING the Schur system of the first iteration (of iteration k after
- * tmpc_debug_set_stop_iteration(h, k)), which then sits unfactored in the workspace for tmpc_debug_get_array (tests/tools/step3_asm_check.py,
+ * tmpc_debug_set_stop_iteration(h, k)), which then sits unfactored in the workspace for tmpc_debug_get_array (tests/test_gpu_t3_kernels.py,
  * tests/test_gpu_schur_assembly.py).  The outputs of such a call are NOT a solution -- never set it in product code. */
 #define TMPC_DEBUG_FLAG_STOP_ASSEMBLED 8
 /* Debug bit: no relative lift of the Schur diagonal after frozen pivots (REG_MAX = 0): frozen pivots in the centering phase then go straight to the
@@ -29,7 +29,8 @@ extern "C" {
  * compared with the tuned kernels on the same inputs. */
 #define TMPC_DEBUG_FLAG_GENERIC_STAGE 64
 /* Debug bit: only the multiplier kernels (csrc/tmpc_phi.h) take their forms for stage blocks wider than 32 (k_phi_pre<true, *>, k_phi_rhs<true>, kb_phi_dm + k_phi_dir<true>)
- * at n <= 32; the stage kernels stay the tuned ones, so both forms see the same inputs bit for bit and must return the same bits (tests/test_gpu_phi_kernels.py). */
+ * at n <= 32; the stage kernels stay the tuned ones, so both forms see the same inputs bit for bit and must return the same bits (tests/test_gpu_phi_kernels.py).
+ * In a Step 3 call the bit also selects k_t3_schur<true> (csrc/tmpc_t3.h) at n <= 32, under the same rule (tests/test_gpu_t3_kernels.py). */
 #define TMPC_DEBUG_FLAG_GENERIC_ROWS 128
 
 /* C (M x N) <op> A (M x K) * B (N x K)' with the fp64 MFMA tile GEMMs of the factorisation; mode 0: C -= AB', 1: C = AB', 2: C = -AB'.
@@ -100,7 +101,12 @@ int tmpc_debug_get_multipliers(tmpc_handle* h, int nb, int nr, double* phi, doub
  *   46 aX   47 adX   48 acor   49 aSi   50 aLi   51 aLXi [B,p,2,AE] (arrow blocks, AE = 32 x 32 with row stride 32: X, dX, sym(dX dS S^-1), S^-1, L_S^-1, L_X^-1)
  *   52 asum [B,p,5] (<dX,S>, <X,dS>, <dX,dS>, smallest eigenvalue dual / primal of the arrow blocks)   53 prs [B,p,4,nr,nr] (Gram products g_i' X_r g_j (slots 0, 1),
  *   g_i' S_r^-1 g_j (2, 3) of handles with room for more than 32 rows per stage; absent otherwise)
- * A code whose array this handle does not have is TMPC_E_ARG. */
+ *   the regularisation T_k of Step 3 (csrc/tmpc_t3.h; handles with room for T, after a Step 3 call; m = n (n + 1) / 2 entries (a <= b) of T_k, row-major upper triangle):
+ *   54 th   55 z   56 dth   57 dz [B,p,m] (theta, its dual and their directions)   58 cth [B,p,m] (Mehrotra term dz dth / th of pass 1)
+ *   59 x   60 dx [B,p,m+1] (multiplier of the norm cone and its direction)   61 cq [B,p,m+1] (Mehrotra term of the cone, pass 1)   62 g [B,p,m+1] (sig s^-1 - x - cq: k_t3_rhs)
+ *   63 v   64 lam [B,p,m+1] (Nesterov-Todd scaling W = beta (2 v v' - J) and lambda = W x, written by k_t3_pre)   65 t   66 dt   67 beta [B,p] (epigraph variable, its direction, beta)
+ *   68 t3psi   69 t3phi [B,p,n,n] (sym(X_2 S_2^-1) and sum_r sym(X_r Hb S_r^-1): what the theta rows of the border columns read)
+ * A code whose array this handle does not have is TMPC_E_ARG; so are the codes of Step 3 after a call that ran without it (a handle with room for T also serves the other models). */
 int tmpc_debug_get_array(tmpc_handle* h, int which, uint64_t offset, uint64_t count, double* out);
 /* The integer state, LANE 0 ONLY like tmpc_debug_get_array: `count` ints from `offset` of iprob [B,24] (per problem: 0 phase (0 main, 1 centering, 2 done), 1 iterations,
  * 5 I_NSHIFT, 9 I_SHIFT0, 12 I_REG, 13 I_CHORD, 19 I_LOWP, ...: the I_* enum of csrc/tmpc_common.h). */
@@ -127,6 +133,10 @@ int tmpc_debug_set_stop_point(tmpc_handle* h, int k, int point);
 int tmpc_debug_min_eig(tmpc_handle* h, int nmat, int n, const double* W, double* out);
 /* The same for n <= 8 by the one-thread-per-matrix routine the small shapes use (lane_min_eig8: Householder + Laguerre in registers; round 5). */
 int tmpc_debug_min_eig_lane(tmpc_handle* h, int nmat, int n, const double* W, double* out);
+
+/* The step length into the second-order cone (soc_step_eig of csrc/tmpc_t3.h, as k_t3_steps calls it) for nvec pairs (u, du) [nvec][m1], u in the interior of Q^m1:
+ * out[i] = -1/theta of the largest theta with u + theta du in Q, or 0 if the ray never leaves the cone.  One wave per pair. */
+int tmpc_debug_soc_step(tmpc_handle* h, int nvec, int m1, const double* u, const double* du, double* out);
 
 /* Isolated timing of the block factorisation and of one single-right-hand-side solve on nb copies of one random SPD system:
  * ms_out2[0] = factorisation, [1] = solve (averages over `reps`). */

@@ -10,8 +10,8 @@ blocks are held by their residual against the condition number; step-length eige
 rounding bound, so the stage-local rows of the Newton equations are held against a dense fp64 LAPACK solve of the system assembled at s0 (NEWTON_RESIDUAL_FACTOR of
 tests/test_gpu_step_kernels.py).  Cases: tests/phi_kernel_cases.py.
 
-Not covered here: a chord step's local Newton rows (its system is not in the workspace: D holds the factor of an earlier iterate), Step 3 (tmpc_t3.h), the
-double-double assembly (k_dd_aug_fill) and the persistent kernel."""
+Not covered here: a chord step's local Newton rows (its system is not in the workspace: D holds the factor of an earlier iterate), the
+double-double assembly (k_dd_aug_fill) and the persistent kernel.  Step 3 (tmpc_t3.h) with and without these rows: tests/test_gpu_t3_kernels.py."""
 import numpy as np
 import pytest
 

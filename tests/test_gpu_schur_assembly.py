@@ -10,8 +10,8 @@ at each assert), `bound` the same formula on the absolute values of the inputs, 
 tmpc_debug_get_array reads lane 0 only: the handle is created with chunk = batch size and lanes = 1 (tmpc_create_ex), so the whole batch is one chunk on that lane
 and problem b sits at index b of every array.
 
-The rows of the G / C multipliers (k_phi_pre, k_aug_fill, k_phi_rhs, k_aug_gather) are in tests/test_gpu_phi_kernels.py.  Not covered here: the rows of Step 3
-(tmpc_t3.h), the double-double assembly of the tight mode (k_dd_aug_fill with it), and the one-wave schur_body inside the persistent kernel
+The rows of the G / C multipliers (k_phi_pre, k_aug_fill, k_phi_rhs, k_aug_gather) are in tests/test_gpu_phi_kernels.py, the rows of Step 3
+(tmpc_t3.h) in tests/test_gpu_t3_kernels.py.  Not covered here: the double-double assembly of the tight mode (k_dd_aug_fill with it), and the one-wave schur_body inside the persistent kernel
 (test_gpu_batch_parity.py::test_persistent_small_kernel_parity).  Centering iterates (three-column pass 2, chord steps) and everything after the block solve
 -- pass-2 right-hand side, border solve, directions, step lengths, update -- are in tests/test_gpu_step_kernels.py."""
 import numpy as np

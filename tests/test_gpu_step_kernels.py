@@ -10,7 +10,7 @@ entrywise, with m derived at each assert (tests/test_gpu_schur_assembly.py expla
 tests/schur_assembly_cases.py, the small ones once more with the generic stage kernels.  Centering cases: the first centering iteration and the first chord step
 of three shapes, found by a scouting run on the same handle configuration (pass 1 is skipped, pass 2 solves three columns, the pre-test asks two thresholds).
 
-The rows of the G / C multipliers (k_phi_dir, k_phi_steps, k_phi_update) are in tests/test_gpu_phi_kernels.py.  Not covered here: Step 3 (tmpc_t3.h), the
+The rows of the G / C multipliers (k_phi_dir, k_phi_steps, k_phi_update) are in tests/test_gpu_phi_kernels.py, those of Step 3 (k_t3_dir, k_t3_steps, k_t3_update) in tests/test_gpu_t3_kernels.py.  Not covered here: the
 double-double tight phase (k_dd_aug_fill with it), the bodies as instantiated inside the persistent kernel, and the decisions of k_ctrl_d."""
 import numpy as np
 import pytest

@@ -37,6 +37,7 @@ DEBUG_EXPORTS = [
     'tmpc_debug_gemm_nt', 'tmpc_debug_block_solve', 'tmpc_debug_cr_schedule', 'tmpc_debug_get_multipliers', 'tmpc_debug_get_array',
     'tmpc_debug_min_eig', 'tmpc_debug_min_eig_lane', 'tmpc_debug_factor_bench', 'tmpc_debug_block_factor',
     'tmpc_debug_last_trsm_pairs', 'tmpc_debug_set_stop_iteration', 'tmpc_debug_set_stop_point', 'tmpc_debug_get_iprob',
+    'tmpc_debug_soc_step',
 ]
 FLAG_DEBUG_NO_DMA = 32      # tunempc_hip_debug.h: TMPC_DEBUG_FLAG_NO_DMA
 # mode bits of tmpc_debug_block_factor (tunempc_hip_debug.h)
@@ -219,6 +220,8 @@ def load_library():
     lib.tmpc_debug_last_trsm_pairs.argtypes = []
     lib.tmpc_debug_min_eig.restype = C.c_int
     lib.tmpc_debug_min_eig.argtypes = [vp, C.c_int, C.c_int, dp, dp]
+    lib.tmpc_debug_soc_step.restype = C.c_int
+    lib.tmpc_debug_soc_step.argtypes = [vp, C.c_int, C.c_int, dp, dp, dp]
     lib.tmpc_debug_min_eig_lane.restype = C.c_int
     lib.tmpc_debug_min_eig_lane.argtypes = [vp, C.c_int, C.c_int, dp, dp]
     lib.tmpc_last_error.restype = C.c_char_p
@@ -626,6 +629,15 @@ class HipConvexifier:
         out = np.empty(nmat)
         fn = self.lib.tmpc_debug_min_eig_lane if lane else self.lib.tmpc_debug_min_eig
         _check(self.lib, fn(self._h, nmat, n, _dptr(W), _dptr(out)), 'tmpc_debug_min_eig')
+        return out
+
+    def debug_soc_step(self, u, du):
+        """the step length into the second-order cone for pairs (u, du) [nvec, m1] as the "eigenvalue" -1/theta, 0 if unbounded (soc_step_eig of csrc/tmpc_t3.h)"""
+        u = np.ascontiguousarray(u, dtype=np.float64); du = np.ascontiguousarray(du, dtype=np.float64)
+        nvec, m1 = u.shape
+        assert du.shape == u.shape
+        out = np.empty(nvec)
+        _check(self.lib, self.lib.tmpc_debug_soc_step(self._h, nvec, m1, _dptr(u), _dptr(du), _dptr(out)), 'tmpc_debug_soc_step')
         return out
 
     def tracking_reference(self, Hc, q, wref, ts):

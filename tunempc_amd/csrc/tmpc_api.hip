@@ -129,6 +129,7 @@ struct Lane {
   double prof[16];               // see tmpc_get_profile
   std::vector<hipEvent_t> kev;   // profile mode: event pairs around the launches of one factorisation (class = index % 3)
   int last_nb;                   // problems this lane solved in the last wave (trace / multiplier read-back)
+  int last_nT;                   // entries of T_k per stage of the last call (0: a call without Step 3, or none yet): row stride of the Step 3 state (tmpc_debug_get_array, codes 54 ..)
   int o32_dp;                    // block width of the last call that wrote float32 O copies (0: none yet, the array is all zero): a call with another width finds stale data where its zero padding should be
   std::unordered_map<std::string, hipGraphExec_t>* graphs;   // launch-bound shapes: one IPM iteration as a captured graph, keyed by every launch argument (run_chunk)
   char err[512];                 // error text of the lane's worker thread
@@ -446,6 +447,13 @@ __global__ void __launch_bounds__(64) k_debug_min_eig_lane(const double* W, doub
   if (i < nmat) out[i] = lane_min_eig8(W + (size_t)i * n * n, n);
 }
 
+// the step-length routine of the second-order cone (tmpc_t3.h) on nvec pairs (u, du) of length m1: one wave per pair, soc_step_eig as k_t3_steps calls it
+__global__ void __launch_bounds__(64) k_debug_soc_step(const double* u, const double* du, double* out, int m1) {
+  const size_t i = blockIdx.x;
+  const double e = soc_step_eig(u + i * m1, du + i * m1, m1, threadIdx.x);
+  if (threadIdx.x == 0) out[i] = e;
+}
+
 template <bool USE_MFMA>
 __global__ void __launch_bounds__(256, 2) k_debug_gemm(double* C, const double* A, const double* B, int M, int N, int K, int mode, int lower) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
@@ -718,6 +726,7 @@ static int run_chunk(tmpc_handle* h, Lane* ln, int nb, const double* dA, const d
   Dims dm = h->dm;
   dm.B = nb;
   if (!step3) dm.nT = 0;                  // a handle with room for T also serves the other models
+  ln->last_nT = dm.nT;
   // a handle created with room for G / C rows also serves calls without them; Step 2 (constr) when the C counts are given
   if (!dG) { dm.ng = 0; dm.nr = 0; dm.nz = 0; }
   // rho == 0 with C counts: the beta-only objective (the other reading of convexifier.py:276-283, see tunempc_hip.h): the rows of C_k are
@@ -733,8 +742,8 @@ static int run_chunk(tmpc_handle* h, Lane* ln, int nb, const double* dA, const d
   dm.flags = (h->flags & TMPC_FLAG_NO_MFMA) | (h->tune_small ? 0 : DF_NO_SMALL) | ((h->flags & TMPC_DEBUG_FLAG_NO_DMA) ? DF_NO_DMA : 0);
   const size_t t3_lds = (size_t)(3 * (dm.nT + 1) + 8) * sizeof(double);
   const bool big = dm.n > NMAX || (h->flags & TMPC_DEBUG_FLAG_GENERIC_STAGE);      // generic per-stage kernels (tmpc_big.h)
-  const size_t t3_schur_lds = (size_t)((big ? 0 : 9 * 32 * T3_LD) + 2 * (dm.nT + 1)) * sizeof(double) + (size_t)(2 * (dm.nT + 1) + 2 * (dm.d + 1)) * sizeof(short) + 64;
-  const bool bigphi = big || (h->flags & TMPC_DEBUG_FLAG_GENERIC_ROWS);            // <BIGN> forms of the multiplier kernels (tmpc_phi.h) with kb_phi_dm
+  const bool bigphi = big || (h->flags & TMPC_DEBUG_FLAG_GENERIC_ROWS);            // <BIGN> forms of the multiplier kernels (tmpc_phi.h) with kb_phi_dm, and of k_t3_schur (tmpc_t3.h)
+  const size_t t3_schur_lds = (size_t)((bigphi ? 0 : 9 * 32 * T3_LD) + 2 * (dm.nT + 1)) * sizeof(double) + (size_t)(2 * (dm.nT + 1) + 2 * (dm.d + 1)) * sizeof(short) + 64;
   if (bigphi && !ln->ws.bscr) {              // (debug flags at n <= 32: the scratch is not part of the workspace)
     if (hipMalloc(&ln->big_scr, (size_t)h->dm.B * dm.p * BIG_SCR * dm.n * dm.n * sizeof(double)) != hipSuccess) { snprintf(g_err, sizeof(g_err), "hipMalloc of the generic-stage scratch failed"); return TMPC_E_NOMEM; }
     ln->ws.bscr = (double*)ln->big_scr;
@@ -872,12 +881,12 @@ static int run_chunk(tmpc_handle* h, Lane* ln, int nb, const double* dA, const d
     }
     if (eq && nfac > 0 && ddm) hipLaunchKernelGGL(k_dd_aug_fill, dim3(nfac * dm.p), dim3(256), (size_t)dd_aug_lds_doubles(dm.nr, dm.n, dm.nx) * sizeof(double), st, wf, dm, 0);
     else if (eq && nfac > 0) hipLaunchKernelGGL(k_aug_fill, dim3(nfac * dm.p), dim3(64), 0, st, wf, dm);
-    if (t3 && nfac > 0 && big) hipLaunchKernelGGL(k_t3_schur<true>, dim3(nfac * dm.p), dim3(256), t3_schur_lds, st, wf, dm);
+    if (t3 && nfac > 0 && bigphi) hipLaunchKernelGGL(k_t3_schur<true>, dim3(nfac * dm.p), dim3(256), t3_schur_lds, st, wf, dm);
     else if (t3 && nfac > 0) hipLaunchKernelGGL(k_t3_schur<false>, dim3(nfac * dm.p), dim3(256), t3_schur_lds, st, wf, dm);
     if (t3 && eq && nfac > 0) hipLaunchKernelGGL(k_t3_cross, dim3(nfac * dm.p), dim3(64), 0, st, wf, dm);
     // debug (tunempc_hip_debug.h): this is the iteration the call stops in; stop_point says where (0: right here, with the assembled system)
     const bool stop_here = (h->flags & TMPC_DEBUG_FLAG_STOP_ASSEMBLED) && it + 1 >= h->stop_it;
-    if (stop_here && h->stop_point == TMPC_DEBUG_STOP_ASSEMBLED) {   // debug (tunempc_hip_debug.h; tests/tools/step3_asm_check.py, tests/test_gpu_schur_assembly.py): stop with the assembled, unfactored system of iteration stop_it (default: the first) in the workspace
+    if (stop_here && h->stop_point == TMPC_DEBUG_STOP_ASSEMBLED) {   // debug (tunempc_hip_debug.h; tests/test_gpu_t3_kernels.py, tests/test_gpu_schur_assembly.py): stop with the assembled, unfactored system of iteration stop_it (default: the first) in the workspace
       if (big) hipLaunchKernelGGL(kb_stage_rhs, dim3(BP), dim3(256), 0, st, w, dm, 1);
       else TMPC_STAGE_LAUNCH(k_stage_rhs, slots_bytes(RHS_SLOTS), st, w, dm, 1);
       // (with rows: r_loc of pass 1 and the tails of W3 / U, in the order of the loop below -- the stop means the same for these models as for the plain one)
@@ -1196,7 +1205,7 @@ static int create_handle(tmpc_handle** out, int chunk, int p, int nx, int mb, in
   }
   int rc = cr_upload(h->sched, &h->d_sched);
   bool ok = (rc == TMPC_OK) && hipEventCreateWithFlags(&h->ev_in, hipEventDisableTiming) == hipSuccess;
-  for (int l = 0; l < MAXL; ++l) { Lane& ln = h->lane[l]; ln.big_scr = nullptr; ln.o32_dp = 0; ln.graphs = nullptr; ln.st = nullptr; for (int i = 0; i < 8; ++i) ln.ev[i] = nullptr; memset(ln.prof, 0, sizeof(ln.prof)); ln.last_nb = 0; ln.err[0] = 0; }
+  for (int l = 0; l < MAXL; ++l) { Lane& ln = h->lane[l]; ln.big_scr = nullptr; ln.o32_dp = 0; ln.graphs = nullptr; ln.st = nullptr; for (int i = 0; i < 8; ++i) ln.ev[i] = nullptr; memset(ln.prof, 0, sizeof(ln.prof)); ln.last_nb = 0; ln.last_nT = 0; ln.err[0] = 0; }
   for (int l = 0; l < nl && ok; ++l) {
     Lane& ln = h->lane[l];
     carve(ln.ws, h->dm, (char*)h->slab + (size_t)l * lane_bytes, &ln);
@@ -1437,8 +1446,25 @@ int tmpc_debug_get_array(tmpc_handle* h, int which, uint64_t offset, uint64_t co
     case 51: src = ws.aLXi; break;
     case 52: src = ws.asum; break;
     case 53: src = ws.prs; break;
+    case 54: src = ws.t3th; break;
+    case 55: src = ws.t3z; break;
+    case 56: src = ws.t3dth; break;
+    case 57: src = ws.t3dz; break;
+    case 58: src = ws.t3cth; break;
+    case 59: src = ws.t3x; break;
+    case 60: src = ws.t3dx; break;
+    case 61: src = ws.t3cq; break;
+    case 62: src = ws.t3g; break;
+    case 63: src = ws.t3v; break;
+    case 64: src = ws.t3lam; break;
+    case 65: src = ws.t3t; break;
+    case 66: src = ws.t3dt; break;
+    case 67: src = ws.t3beta; break;
+    case 68: src = ws.t3psi; break;
+    case 69: src = ws.t3phi; break;
     default: return TMPC_E_ARG;
   }
+  if (which >= 54 && h->lane[0].last_nT == 0) return TMPC_E_ARG;      // the last call ran without Step 3: nothing of it stands in these arrays
   if (!src) return TMPC_E_ARG;
   HIPCHK(hipMemcpy(out, src + offset, count * sizeof(double), hipMemcpyDeviceToHost));
   return TMPC_OK;
@@ -3103,6 +3129,21 @@ int tmpc_debug_min_eig_lane(tmpc_handle* h, int nmat, int n, const double* W, do
   hipLaunchKernelGGL(k_debug_min_eig_lane, dim3((nmat + 63) / 64), dim3(64), 0, 0, bW.as<double>(), bO.as<double>(), n, nmat);
   HIPCHK(hipDeviceSynchronize());
   HIPCHK(hipMemcpy(out, bO.p, (size_t)nmat * 8, hipMemcpyDeviceToHost));
+  return TMPC_OK;
+}
+
+// largest step into the second-order cone as the "eigenvalue" -1/theta (0: unbounded) for nvec pairs (u, du) of length m1 (soc_step_eig of tmpc_t3.h)
+int tmpc_debug_soc_step(tmpc_handle* h, int nvec, int m1, const double* u, const double* du, double* out) {
+  if (!h || nvec < 1 || m1 < 2 || !u || !du || !out) return TMPC_E_ARG;
+  ON_DEVICE(h);
+  DevBuf bU, bD, bO;
+  const size_t bytes = (size_t)nvec * m1 * 8;
+  HIPCHK(bU.alloc(bytes)); HIPCHK(bD.alloc(bytes)); HIPCHK(bO.alloc((size_t)nvec * 8));
+  HIPCHK(hipMemcpy(bU.p, u, bytes, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(bD.p, du, bytes, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_debug_soc_step, dim3(nvec), dim3(64), 0, 0, bU.as<double>(), bD.as<double>(), bO.as<double>(), m1);
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(out, bO.p, (size_t)nvec * 8, hipMemcpyDeviceToHost));
   return TMPC_OK;
 }
 

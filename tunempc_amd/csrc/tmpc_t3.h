@@ -39,8 +39,11 @@ __device__ __forceinline__ double soc_step_eig(const double* u, const double* du
   else {
     const double disc = bq * bq - a * c;
     if (disc >= 0.0) {
+      // the two roots as q / a and c / q with q = -bq -+ sqrt(disc) summed without cancellation: for du close to the boundary of -Q (a -> 0+, bq < 0) the exit is
+      // c / q -> c / (2 |bq|), which the textbook form (|bq| - sqrt(disc)) / a loses to rounding (a itself carries few digits there)
       const double sq = sqrt(disc);
-      const double r1 = (-bq - sq) / a, r2 = (-bq + sq) / a;
+      const double q = (bq < 0.0) ? (-bq + sq) : (-bq - sq);
+      const double r1 = q / a, r2 = (q != 0.0) ? c / q : -1.0;
       if (r1 > 0.0) th = fmin(th, r1);
       if (r2 > 0.0) th = fmin(th, r2);
     }
